@@ -11,6 +11,11 @@ depth cap 5) unless --config says otherwise.  Each launch writes the f64 RGB fra
 reference's FrameBuffer) and its display bytes (`to_vec`, what the UI blits) to HBM; inputs
 (the scene) are uploaded before the timed region.
 
+A plain run sets up, warms up, times exactly K steps and prints the line.  --full also
+measures what the line carries beside the metric (the CPU baseline, the other configs,
+rm_render into host memory, the camera on the move); --dump-outputs DIR writes the frame(s)
+of the timed path's last step as DIR/<name>.npy, so that two builds can be compared.
+
 N > 1: the frame is sharded by 32-row patch rows (cyclic ownership: rank r
 renders patch rows r, r+N, ...) and ONE exchange per frame, inside the timed region, completes
 the display frame (--payload u8, the default) or the f64 frame itself (--payload f64) at the
@@ -101,10 +106,18 @@ def parse_args(argv=None):
                          "exact-incidence pixels differently from the reference -- not the parity configuration")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise RCCL and run the per-frame collective even at world size 1 (smoke test of the N > 1 code path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the line carries beside the metric: the CPU baseline, the other configs, "
+                         "rm_render into host memory and the camera on the move (each can be left out with its --no-* option); "
+                         "without it a run times the metric's steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float64 / float32, at most 64 MB in all: a larger output is a fixed, seeded sample of its elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-sizes", action="store_true",
-                    help="skip the extras reported beside the metric (other configs, rm_render into host memory)")
-    ap.add_argument("--no-motion", action="store_true", help="skip the camera_on_the_move leg (the camera moving before every launch)")
+                    help="with --full: skip the extras reported beside the metric (other configs, rm_render into host memory)")
+    ap.add_argument("--no-motion", action="store_true",
+                    help="with --full: skip the camera_on_the_move leg (the camera moving before every launch)")
     ap.add_argument("--check", action="store_true", help="also compare the frame with the oracle")
     ap.add_argument("--deadline", type=float, default=900.,
                     help="self-spawned runs (--gpus N > 1 without a launcher): seconds after which the rank processes are killed")
@@ -112,7 +125,41 @@ def parse_args(argv=None):
                     help="no GPU: the ranks rendezvous over gloo and go through the step / barrier / max-over-ranks / JSON "
                          "plumbing with an empty step; prints a line marked dry_run with value null (CPU test of the spawn path)")
     ap.add_argument("--dry-hang-rank", type=int, default=-1, help=argparse.SUPPRESS)   # test hook: this rank never finishes
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+# --dump-outputs: bytes each output may take (62 MB in all, under the 64 MB cap with the .npy headers)
+DUMP_BYTES = {"frame": 50_000_000, "display": 12_000_000}
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, outputs):
+    """Writes each output (a torch tensor, on the device or not) as out_dir/<name>.npy: f64 as float64,
+    anything else as float32.  One larger than its share of DUMP_BYTES is replaced by the elements at a
+    fixed, seeded sample of its flat indices (sorted, so the same positions in every run and build of a
+    given shape).  -> {name: what was written}"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in outputs.items():
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        flat = t.reshape(-1)
+        keep = DUMP_BYTES[name] // (8 if dtype == torch.float64 else 4)
+        sampled = flat.numel() > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), keep, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].to(dtype).cpu().numpy()
+        else:
+            a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(t.shape), "dtype": str(a.dtype),
+                      "sample": "%d of %d elements (flat indices drawn with seed %#x, sorted)" % (keep, flat.numel(), DUMP_SEED)
+                      if sampled else None}
+    return info
 
 
 # ------------------------------------------------------------------------------------------
@@ -463,9 +510,10 @@ def rank_main(args):
             return False
         return True
 
-    def run_workload(cfg_id, steps, warmup, extras=False, motion=False):
+    def run_workload(cfg_id, steps, warmup, extras=False, motion=False, keep_outputs=False):
         """Warm-up, then `steps` frames of one workload between fences -- at N > 1 once per
-        exchange path; returns the timings and what rank 0 holds afterwards."""
+        exchange path; returns the timings and what rank 0 holds afterwards (`keep_outputs`:
+        and a device copy of what the chosen path's last step handed its caller)."""
         cfg = workloads.CONFIGS[cfg_id]
         w, h, depth = cfg["width"], cfg["height"], cfg["max_depth"]
         n_rows = h // 32
@@ -639,12 +687,29 @@ def rank_main(args):
             return {"elapsed": elapsed, "ms_per_step": elapsed / n * 1e3, "kernel_ms": kernel_ms,
                     "mpx": (w * h) * n / elapsed / 1e6}
 
+        def last_outputs(n_slots):
+            """What the caller of the path just timed holds after its last step: at N = 1 the f64
+            frame and its display bytes; at N > 1 the consumer's (rank 0's) frame in image order --
+            the display bytes, or the f64 rows with --payload f64.  Copied on the device before
+            anything else is rendered into the slots."""
+            if not keep_outputs:
+                return {}
+            if not use_dist:
+                return {"frame": frames[0][:h].clone(), "display": frames8[0].clone()}
+            if rank != 0:
+                return {}
+            img = images[(counter[0] - 1) % n_slots][:n_rows * 32].clone()
+            return {"frame" if unit == 8 else "display": img}
+
         paths = {}
         chosen = "none"
+        outputs = {}
         if not use_dist:
             paths["none"] = timed(step_single, False)
+            outputs = last_outputs(1)
         else:
             paths["torch"] = dict(timed(step_torch, False), frames_in_flight=n_buf_torch)
+            outputs = last_outputs(n_buf_torch)
             chosen = "torch"
             if cfg_id == args.config:
                 note_partial("torch_path", dict(paths["torch"], workload=cfg_id, n_gpus=world))
@@ -669,6 +734,7 @@ def rank_main(args):
                     else:
                         paths["direct"] = dict(timed(step_direct, True), frames_in_flight=n_buf,
                                                rccl_sees=dict(zip(("rank", "world", "communicators"), ctx.comm_info())))
+                        direct_outputs = last_outputs(n_buf)
                         # device times of one frame on its stream (stamped frames, outside the timed region)
                         ctx.frame_timing_enable(True)
                         counter[0] = 0
@@ -680,6 +746,7 @@ def rank_main(args):
                         paths["direct"]["one_frame_on_its_stream_ms"] = {"kernel": t.kernel_ms, "gather": t.gather_ms, "total": t.total_ms}
                         if paths["direct"]["mpx"] >= paths["torch"]["mpx"]:
                             chosen = "direct"                   # `value` is the faster of the two valid exchanges
+                            outputs = direct_outputs
                 except pkg.BackendError as e:
                     if e.status != pkg._lib.RM_ERR_TIMEOUT:
                         raise
@@ -859,7 +926,8 @@ def rank_main(args):
             if u8 is not None:
                 checks["display_bytes_differing_from_oracle"] = int((u8.cpu().numpy().reshape(-1) != O.to_vec(ref.copy())).sum())
         res = dict(cfg=cfg, paths=paths, chosen=chosen, kernel_name=kernel_name, n_owned=n_owned, c_rows=c_rows, cyclic=cyclic,
-                   host=host, piped=piped, checks=checks, px_launch=px_launch, best=best, tiles=tiles, moving=moving)
+                   host=host, piped=piped, checks=checks, px_launch=px_launch, best=best, tiles=tiles, moving=moving,
+                   outputs=outputs)
         ctx.close()
         torch.cuda.empty_cache()
         return res
@@ -937,12 +1005,15 @@ def rank_main(args):
         json_out.write(json.dumps(out) + "\n")
         json_out.flush()
 
-    r = run_workload(args.config, args.steps, args.warmup, extras=not args.no_sizes, motion=not args.no_motion)
+    # a run without --full does only what the metric needs: everything beside it is measured with --full
+    sizes = args.full and not args.no_sizes
+    r = run_workload(args.config, args.steps, args.warmup, extras=sizes, motion=args.full and not args.no_motion,
+                     keep_outputs=bool(args.dump_outputs))
     # north star: "Mpixels/sec on synthetic 1080p/4K/8K frames", and the other GPU configs of
     # BASELINE.json (cornell C3, synthetic C5): a short run each (same sharding and collective),
     # reported beside the metric with their own kernel and roofline fraction
     other = []
-    if args.config == "C2" and not args.no_sizes:
+    if args.config == "C2" and sizes:
         for cid in ("C2_4K", "C4", "C3", "C5"):
             k = max(5, min(args.steps, 20 if cid != "C3" else 100))
             o = run_workload(cid, k, 3, motion=(cid == "C3"))
@@ -967,7 +1038,7 @@ def rank_main(args):
     if rank == 0:
         out = result(r["cfg"], r["paths"], r["chosen"], None, r["kernel_name"], r["n_owned"], r["c_rows"], r["cyclic"],
                      r["host"], r["piped"], r["checks"], other, r["tiles"], r["moving"])
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             O = G.load_oracle()
             out["cpu_baseline"] = cpu_baseline(O, workloads, r["cfg"])
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
@@ -982,6 +1053,8 @@ def rank_main(args):
             if (e2e.get("display_only") or {}).get("frames_per_s"):
                 at_seam["rm_render_display_display_bytes"] = e2e["display_only"]["frames_per_s"] * (r["cfg"]["width"] * r["cfg"]["height"]) / 1e6 / cpu_v
             out["speedup_vs_cpu_baseline_at_the_seam"] = at_seam
+        if args.dump_outputs:
+            out["outputs_dumped"] = dump_outputs(args.dump_outputs, r["outputs"])
         emit(out)
 
     if use_dist:

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 while read -r cfg line; do
   [ -z "$cfg" ] && continue
-  env $line python3 $R/bench.py --config $cfg --steps 100 --warmup 10 --no-cpu-baseline --no-sizes "$@" 2>/tmp/ab_err.log | LINE="$cfg $line" python3 -c "
+  env $line python3 $R/bench.py --config $cfg --steps 100 --warmup 10 --full --no-cpu-baseline --no-sizes "$@" 2>/tmp/ab_err.log | LINE="$cfg $line" python3 -c "
 import json,sys,os
 t=sys.stdin.read()
 try:

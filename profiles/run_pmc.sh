@@ -2,13 +2,13 @@
 # Collects rocprofv3 PMC counters for bench.py's launches, one --pmc pass per counter group
 # (separate runs, kernel-trace only -- never combined with sys traces).
 # usage (on the GPU box, from the repo root):  bash profiles/run_pmc.sh <tag> [bench args]
-# -> gpurun_out/pmc_<tag>/summary.csv: mean counter value per launch, for the render kernel
+# -> $RM_PROFILE_OUT/pmc_<tag>/summary.csv (default profiles/raw/): mean counter value per launch, for the render kernel
 #    (rm_render_static) and for the classification kernel in front of it (rm_classify_tiles_kernel)
 set -u
 TAG=${1:-run}; shift || true
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 BENCH=${BENCH:-$R/bench.py}     # BENCH=build/old/bench.py profiles the bench of another tree
-OUT=$R/gpurun_out/pmc_$TAG
+OUT=$(realpath -m "${RM_PROFILE_OUT:-$R/profiles/raw}")/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 i=0

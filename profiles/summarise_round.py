@@ -1,4 +1,4 @@
-"""Turns what profiles/collect_round.sh left under gpurun_out/ into the committed summaries:
+"""Turns what profiles/collect_round.sh left under $RM_PROFILE_OUT (default profiles/raw/) into the committed summaries:
     python profiles/summarise_round.py r03
 -> profiles/<tag>_kernel_stats_<C>.csv   rocprofv3 --kernel-trace --stats, first rows
    profiles/<tag>_pmc_<C>.csv            mean PMC counters per launch: the render kernel and the
@@ -19,7 +19,7 @@ import bench       # noqa: E402
 import workloads   # noqa: E402
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-out = os.path.join(ROOT, "gpurun_out")
+out = os.path.abspath(os.environ.get("RM_PROFILE_OUT") or os.path.join(ROOT, "profiles", "raw"))
 
 for c in ("C2", "C3", "C5", "C4", "default"):
     # (an earlier collection's files may lie beside the last one's: the newest wins)

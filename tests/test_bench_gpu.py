@@ -28,7 +28,7 @@ def _bench(args, env=None):
 
 
 def test_one_gpu_line_has_the_contract_fields():
-    d = _bench(["--steps", "20", "--warmup", "3", "--check", "--no-sizes"])
+    d = _bench(["--full", "--steps", "20", "--warmup", "3", "--check", "--no-sizes"])
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["unit"] == "Mpixels/s" and d["dtype"] == "f64"
     assert d["metric"] == "Mpixels/sec at 1920x1080, max-bounce=5" and d["vs_baseline"] is None
     assert d["max_abs_delta_vs_oracle"] < 1e-9 and d["display_bytes_differing_from_oracle"] == 0
@@ -39,6 +39,32 @@ def test_one_gpu_line_has_the_contract_fields():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["cpu"] and c["value"] > 0 and "frame(s)" in c["sample"]
     assert d["value"] > 100 * c["value"]                      # north star: >= 100x the host-CPU path
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path):
+    """Without --full the line is the metric alone; --dump-outputs writes the f64 frame of the last
+    timed step in full and a seeded sample of its display bytes, and the frame is the oracle's."""
+    import numpy as np
+
+    import __graft_entry__ as G
+    import workloads
+    d = _bench(["--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and abs(d["value"] - 1920 * 1080 / (d["ms_per_step"] * 1e3)) < 1e-6 * d["value"]
+    for leg in ("cpu_baseline", "other_frames", "end_to_end_host", "camera_on_the_move", "four_frames_in_flight"):
+        assert leg not in d
+    assert sorted(os.listdir(tmp_path)) == ["display.npy", "frame.npy"]
+    assert sum(os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path)) <= 64 * 10 ** 6
+    frame, display = np.load(tmp_path / "frame.npy"), np.load(tmp_path / "display.npy")
+    assert frame.dtype == np.float64 and frame.shape == (1080, 1920, 3)
+    assert display.dtype == np.float32 and display.shape == (3_000_000,) and d["outputs_dumped"]["display"]["sample"]
+    O = G.load_oracle()
+    ref = O.render(workloads.oracle_scene(O, "demo"), 1920, 1080, max_depth=5)[:1056]
+    assert float(np.abs(frame[:1056] - ref).max()) < 1e-9
+    idx = np.sort(np.random.default_rng(0x5EED).choice(1080 * 1920 * 3, 3_000_000, replace=False))
+    want = np.zeros(1080 * 1920 * 3, np.uint8)
+    want[:1056 * 1920 * 3] = O.to_vec(ref.copy())
+    keep = idx < 1056 * 1920 * 3                               # (the rows below the last whole patch row are not rendered)
+    assert np.array_equal(display[keep], want[idx[keep]].astype(np.float32))
 
 
 def test_two_ranks_self_spawned_on_this_gpu_over_gloo():
@@ -52,6 +78,38 @@ def test_two_ranks_self_spawned_on_this_gpu_over_gloo():
     d = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--check", "--no-sizes", "--payload", "f64"],
                env={"RM_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["max_abs_delta_vs_oracle"] < 1e-9
+
+
+@pytest.mark.parametrize("payload", ["u8", "f64"])
+@pytest.mark.parametrize("ranks", ["two_over_gloo", "one_over_rccl"])
+def test_sharded_path_dumps_what_the_consumer_received(ranks, payload, tmp_path):
+    """--dump-outputs on the sharded path: rank 0's frame in image order after the last timed step
+    of the path the line reports (torch's exchange over gloo; over RCCL the faster of torch's and
+    the library's) -- the display bytes (a seeded sample) or, with --payload f64, the f64 rows in full."""
+    import numpy as np
+
+    import __graft_entry__ as G
+    import workloads
+    args = ["--steps", "4", "--warmup", "1", "--payload", payload, "--dump-outputs", str(tmp_path)]
+    if ranks == "two_over_gloo":
+        d = _bench(["--gpus", "2"] + args, env={"RM_BENCH_BACKEND": "gloo"})
+    else:
+        d = _bench(["--force-dist"] + args)
+        assert "direct" in d["exchange_paths"], d["config"]["collective"]
+    assert d["steps"] == 4
+    O = G.load_oracle()
+    ref = O.render(workloads.oracle_scene(O, "demo"), 1920, 1080, max_depth=5)[:1056]
+    if payload == "f64":
+        assert os.listdir(tmp_path) == ["frame.npy"]
+        frame = np.load(tmp_path / "frame.npy")
+        assert frame.dtype == np.float64 and frame.shape == (1056, 1920, 3)
+        assert float(np.abs(frame - ref).max()) < 1e-9
+    else:
+        assert os.listdir(tmp_path) == ["display.npy"]
+        display = np.load(tmp_path / "display.npy")
+        assert display.dtype == np.float32 and display.shape == (3_000_000,)
+        idx = np.sort(np.random.default_rng(0x5EED).choice(1056 * 1920 * 3, 3_000_000, replace=False))
+        assert np.array_equal(display, O.to_vec(ref.copy())[idx].astype(np.float32))
 
 
 @pytest.mark.parametrize("payload", ["u8", "f64"])
