@@ -438,6 +438,81 @@ rm_status rm_frame_timing(rm_ctx *ctx, uint32_t slot, rm_frame_times *out);
 rm_status rm_comm_info(rm_ctx *ctx, int *rank, int *world, int *n_communicators);
 
 
+/* ---- ray queries: the resident scene asked about rays of the caller's own ----------------
+ * The render's intersection engine without the shading: find_closest_intersect
+ * (shapes.rs:110-143) and intersect_shape_set (shapes.rs:92-108) for rays the caller names,
+ * the ray under a pixel (click-to-pick), and a per-pixel hit buffer of a frame.  Added under
+ * ABI version 5 (RM_ABI_VERSION did not move); a host detects them by " queries" in
+ * rm_build_info().
+ *
+ * Semantics common to every query:
+ *   - Scene: the one resident from rm_scene_upload (RM_ERR_NO_SCENE without one).  Ray lists
+ *     carry their own origins; rm_pick / rm_primary_hits_device cast from the context's
+ *     current camera (rm_camera_update) with the params' Renderer and frame geometry.
+ *   - Numeric flavour: always the strict default, whatever params->flags says; hit / miss /
+ *     shape decisions are the reference's bit for bit.  A render with RM_FLAG_FAST_FP may
+ *     therefore disagree with a pick at exact-incidence pixels (a ray on a polygon edge).
+ *     params->flags may carry RM_FLAG_FAST_FP (ignored) and nothing else, and the band must
+ *     be the default one (patch_row_begin = patch_row_end = 0, stride 0 or 1): anything
+ *     else is RM_ERR_INVALID_ARG.
+ *   - Directions must be unit length within the reference's own assert,
+ *     |(x*x + y*y) + z*z - 1| < 1e-4 (sphere.rs:31, polygon.rs:62, triangle.rs:53).  The host
+ *     entry points check it, and that every component of origin and direction is finite:
+ *     RM_ERR_INVALID_ARG naming the first bad ray in rm_last_error, nothing computed.  For the
+ *     device entry points it is a precondition: a bad ray gets an unspecified answer for
+ *     that ray, never a fault.
+ *   - Occlusion is intersect_shape_set exactly: a hit ANYWHERE along the ray, t in
+ *     [0, inf) -- the reference has no maximum distance, so a shadow ray aimed at a light
+ *     counts as blocked by a shape BEHIND the light.
+ *   - n_rays == 0 is RM_OK and does nothing.
+ *   - Device variants are asynchronous on hip_stream (a hipStream_t; NULL = HIP's default
+ *     stream), as rm_render_device is; host variants and rm_pick block until the answer is
+ *     there.
+ *   - Queries leave every piece of render state alone (per-stream tags, classification and
+ *     order state, feedback sets, the resident frame): a frame rendered after any sequence
+ *     of queries is byte-identical to the frame rendered without them.  A pixel query at a
+ *     frame geometry other than the last render's rebuilds the backproject tables the two
+ *     share: the next render rebuilds them once more, its output does not change.
+ */
+
+/* One answer of find_closest_intersect (shapes.rs:110-143) for one ray. */
+typedef struct rm_hit {
+    double   t;         /* the hit lies at origin + t * direction */
+    rm_vec3  point;     /* Intersection.point  (shapes.rs:3-8) */
+    rm_vec3  normal;    /* Intersection.normal */
+    uint32_t shape;     /* index into Scene.shapes (shapes.rs:140's shape_hit, NOT wrapped to u8) */
+    uint32_t element;   /* triangle index inside the Obj for a mesh shape; 0 for sphere / polygon */
+    int32_t  hit;       /* 1 hit, 0 miss; every other field is 0 on a miss */
+    uint32_t _pad;
+} rm_hit;               /* 72 bytes */
+
+/* Closest hit of n_rays rays: origins[i] + t directions[i] (host arrays) into hits[i]. */
+rm_status rm_intersect_rays(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions,
+                            uint32_t n_rays, rm_hit *hits);
+/* intersect_shape_set of n_rays rays: occluded[i] = 1 where anything is hit, else 0. */
+rm_status rm_occluded_rays(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions,
+                           uint32_t n_rays, uint8_t *occluded);
+/* The same on device buffers (n_rays rm_vec3 each; n_rays rm_hit / bytes out). */
+rm_status rm_intersect_rays_device(rm_ctx *ctx, const void *device_origins, const void *device_directions,
+                                   uint32_t n_rays, void *device_hits, void *hip_stream);
+rm_status rm_occluded_rays_device(rm_ctx *ctx, const void *device_origins, const void *device_directions,
+                                  uint32_t n_rays, void *device_occluded, void *hip_stream);
+/*
+ * What is under pixel (x, y) -- x the column, y the row -- of the frame render() would draw
+ * with `params`: the ray renderer.rs:80 casts there, backproject(x, y) (renderer.rs:128-135)
+ * from the camera, its direction bit-identical to the strict render kernel's.  Pixels
+ * outside frame_width x frame_height are RM_ERR_INVALID_ARG; the frame_height % 32 rows the
+ * render leaves untouched are answered all the same.  frame_width need not be a multiple of 32.
+ */
+rm_status rm_pick(rm_ctx *ctx, const rm_params *params, uint32_t x, uint32_t y, rm_hit *hit);
+/*
+ * rm_pick for every pixel rm_render_device writes with the same params (the whole patch rows,
+ * rows >= frame_height - frame_height % 32 untouched): device_hits is
+ * [frame_height][frame_width] rm_hit.  frame_width % 32 != 0 is RM_ERR_DIMENSIONS, as for the
+ * render.
+ */
+rm_status rm_primary_hits_device(rm_ctx *ctx, const rm_params *params, void *device_hits, void *hip_stream);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

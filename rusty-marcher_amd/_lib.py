@@ -81,6 +81,12 @@ class rm_frame_times(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("gather_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class rm_hit(C.Structure):
+    """One answer of find_closest_intersect (shapes.rs:110-143): the ray queries' record."""
+    _fields_ = [("t", C.c_double), ("point", rm_vec3), ("normal", rm_vec3), ("shape", C.c_uint32),
+                ("element", C.c_uint32), ("hit", C.c_int32), ("_pad", C.c_uint32)]
+
+
 _P = C.POINTER
 _VP = C.c_void_p
 
@@ -138,6 +144,12 @@ SIGNATURES = {
     "rm_frame_timing_enable": (C.c_int, [_VP, C.c_int]),
     "rm_frame_timing": (C.c_int, [_VP, C.c_uint32, _P(rm_frame_times)]),
     "rm_comm_info": (C.c_int, [_VP, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
+    "rm_intersect_rays": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), C.c_uint32, _P(rm_hit)]),
+    "rm_occluded_rays": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), C.c_uint32, _P(C.c_uint8)]),
+    "rm_intersect_rays_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP]),
+    "rm_occluded_rays_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP]),
+    "rm_pick": (C.c_int, [_VP, _P(rm_params), C.c_uint32, C.c_uint32, _P(rm_hit)]),
+    "rm_primary_hits_device": (C.c_int, [_VP, _P(rm_params), _VP, _VP]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

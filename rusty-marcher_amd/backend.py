@@ -1,8 +1,40 @@
 """rm_ctx ownership for the Python host mirror: one context per GPU, created on first
 use.  Raises (never falls back) when no MI355X is visible."""
+import collections
 import ctypes as C
 
+import numpy as np
+
 from . import _lib
+
+# numpy mirror of rm_hit (72 bytes): what Context.intersect returns, one record per ray
+HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("shape", "<u4"),
+                      ("element", "<u4"), ("hit", "<i4"), ("_pad", "<u4")])
+assert HIT_DTYPE.itemsize == C.sizeof(_lib.rm_hit)
+
+# The device answers as views of one buffer of rm_hit records, nothing copied: t (N,), point and normal (N, 3) float64;
+# shape, element and hit (N,) int32 (torch has no uint32 arithmetic; shape indices stay below 2^31); raw: the records,
+# (N, 9) float64 -- or [H][W] of them for primary_hits_device.
+DeviceHits = collections.namedtuple("DeviceHits", "t point normal shape element hit raw")
+
+
+def _rays(origins, directions):
+    o = np.ascontiguousarray(origins, dtype=np.float64)
+    d = np.ascontiguousarray(directions, dtype=np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+        raise ValueError("origins and directions must be two float64 arrays of shape (N, 3), got %s and %s" % (o.shape, d.shape))
+    return o, d
+
+
+def _device_hits(raw):
+    """DeviceHits over a float64 tensor whose last dimension is one rm_hit (9 words)."""
+    ints = raw.view(_torch().int32)                       # 18 int32 a record: shape, element, hit are 14, 15, 16
+    return DeviceHits(raw[..., 0], raw[..., 1:4], raw[..., 4:7], ints[..., 14], ints[..., 15], ints[..., 16], raw)
+
+
+def _torch():
+    import torch
+    return torch
 
 
 class Context:
@@ -104,6 +136,87 @@ class Context:
         _lib.check(self.L.rm_render_device_u8(self.ptr, C.byref(params), C.c_void_p(device_ptr),
                                               C.c_void_p(device_ptr8), C.c_void_p(stream) if stream else None),
                    self.ptr)
+
+    # ---- ray queries (include/rusty_marcher_amd.h, "ray queries") ----
+    def intersect(self, origins, directions):
+        """find_closest_intersect (shapes.rs:110-143) of N rays of the caller's own: (N, 3) float64 origins and unit
+        directions -> a structured array of N rm_hit records (HIT_DTYPE), written by the library in place."""
+        o, d = _rays(origins, directions)
+        out = np.zeros(o.shape[0], dtype=HIT_DTYPE)
+        V = C.POINTER(_lib.rm_vec3)
+        _lib.check(self.L.rm_intersect_rays(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V), o.shape[0],
+                                            out.ctypes.data_as(C.POINTER(_lib.rm_hit))), self.ptr)
+        return out
+
+    def occluded(self, origins, directions):
+        """intersect_shape_set (shapes.rs:92-108) of N rays: a bool array, True where anything lies along the ray
+        (no maximum distance, as in the reference)."""
+        o, d = _rays(origins, directions)
+        out = np.zeros(o.shape[0], dtype=np.uint8)
+        V = C.POINTER(_lib.rm_vec3)
+        _lib.check(self.L.rm_occluded_rays(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V), o.shape[0],
+                                           out.ctypes.data_as(C.POINTER(C.c_uint8))), self.ptr)
+        return out.view(np.bool_)
+
+    def _device_rays(self, origins, directions):
+        torch = _torch()
+        for name, t in (("origins", origins), ("directions", directions)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("%s must be a float64 torch tensor of shape (N, 3)" % name)
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        if origins.shape != directions.shape:
+            raise ValueError("origins %s and directions %s differ in shape" % (tuple(origins.shape), tuple(directions.shape)))
+        return origins.shape[0]
+
+    def _stream(self, stream):
+        """The HIP stream of a call: `stream` (a torch stream or a raw handle), else torch's current stream."""
+        torch = _torch()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+
+    def intersect_device(self, origins, directions, stream=None):
+        """intersect() on torch tensors of the context's device, asynchronous on `stream` (torch's current one by
+        default): DeviceHits, no copy to the host."""
+        torch = _torch()
+        n = self._device_rays(origins, directions)
+        raw = torch.empty((n, 9), dtype=torch.float64, device=origins.device)
+        _lib.check(self.L.rm_intersect_rays_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                                   n, C.c_void_p(raw.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return _device_hits(raw)
+
+    def occluded_device(self, origins, directions, stream=None):
+        """occluded() on torch tensors of the context's device: a bool tensor there, asynchronous on `stream`."""
+        torch = _torch()
+        n = self._device_rays(origins, directions)
+        out = torch.empty((n,), dtype=torch.uint8, device=origins.device)
+        _lib.check(self.L.rm_occluded_rays_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                                  n, C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return out.view(torch.bool)
+
+    def primary_hits_device(self, params, out=None, stream=None):
+        """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole
+        patch rows), as DeviceHits of [frame_height][frame_width].  `out`: a float64 tensor of shape
+        (frame_height, frame_width, 9) on the context's device (zeros by default); rows the render leaves untouched
+        keep what it holds."""
+        torch = _torch()
+        h, w = params.frame_height, params.frame_width
+        if out is None:
+            out = torch.zeros((h, w, 9), dtype=torch.float64, device="cuda:%d" % self.device)
+        if out.dtype != torch.float64 or tuple(out.shape) != (h, w, 9) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor of shape (%d, %d, 9)" % (h, w))
+        _lib.check(self.L.rm_primary_hits_device(self.ptr, C.byref(params), C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(self._stream(stream))), self.ptr)
+        return _device_hits(out)
+
+    def pick(self, params, x, y):
+        """rm_pick: the rm_hit under pixel (x = column, y = row) of the frame `params` describes."""
+        hit = _lib.rm_hit()
+        _lib.check(self.L.rm_pick(self.ptr, C.byref(params), int(x), int(y), C.byref(hit)), self.ptr)
+        return hit
 
     # ---- multi-GPU frames (include/rusty_marcher_amd.h, rm_comm_* / rm_frame_*) ----
     @staticmethod

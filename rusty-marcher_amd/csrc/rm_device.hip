@@ -18,6 +18,7 @@
 #include "rm_bvh.hpp"
 #include "rm_internal.h"
 #include "rm_kernel_args.hpp"
+#include "rm_query.hpp"
 
 using namespace rmdev;
 
@@ -289,6 +290,15 @@ struct rm_ctx {
     rm_hostio *hostio = nullptr;
     bool comm_stuck = false;          // a timed-out collective could not be aborted: nothing that waits for the device may run
 
+    // ray queries (rm_query_host.inc): pid -> (index into Scene.shapes, triangle index inside the Obj) of the
+    // resident image, 2 words per pid -- a buffer of its own, not part of the scene blob (the blob's size decides
+    // whether the render kernels copy the scene into LDS) -- and the host variants' staging buffer
+    uint32_t *d_pid_map = nullptr;
+    size_t pid_map_words = 0;
+    std::vector<uint32_t> host_pid_map;
+    void *d_query = nullptr;
+    size_t query_bytes = 0;
+
     // post-process scratch
     unsigned long long *d_max = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -366,7 +376,7 @@ const void *rm_pick_kernel(bool fast, bool staged, bool bvh, bool cull, bool edg
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -483,6 +493,8 @@ void rm_destroy(rm_ctx *ctx) {
         if (ctx->d_scene) (void)hipFree(ctx->d_scene);
         if (ctx->d_frame) (void)hipFree(ctx->d_frame);
         if (ctx->d_backproject) (void)hipFree(ctx->d_backproject);
+        if (ctx->d_pid_map) (void)hipFree(ctx->d_pid_map);
+        if (ctx->d_query) (void)hipFree(ctx->d_query);
         if (ctx->d_max) (void)hipFree(ctx->d_max);
         if (ctx->d_rgb8) (void)hipFree(ctx->d_rgb8);
         if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -501,6 +513,22 @@ rm_status rm_device_info(rm_ctx *ctx, char *name_buf, size_t buflen, int *n_cus,
 }
 
 static uint64_t pack_u32x2(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+
+// The queries' pid -> (shape, element) map of a new resident image into its device buffer (the device is idle: the
+// caller has synchronised it).  Swaps `map` into the context.
+static rm_status upload_pid_map(rm_ctx *ctx, std::vector<uint32_t> &map) {
+    const size_t words = std::max<size_t>(map.size(), 2u);
+    if (ctx->pid_map_words < words) {
+        if (ctx->d_pid_map) RM_HIP(ctx, hipFree(ctx->d_pid_map));
+        ctx->d_pid_map = nullptr;
+        ctx->pid_map_words = 0;
+        RM_HIP(ctx, hipMalloc(&ctx->d_pid_map, words * sizeof(uint32_t)));
+        ctx->pid_map_words = words;
+    }
+    if (!map.empty()) RM_HIP(ctx, hipMemcpy(ctx->d_pid_map, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->host_pid_map.swap(map);
+    return RM_OK;
+}
 
 static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL ctx");
@@ -549,6 +577,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     // ---- regroup Scene.shapes by kind, remembering list order for ties ----
     std::vector<uint32_t> sphere_src, polygon_src, tri_src;   // indices into desc arrays
     std::vector<uint32_t> sphere_key, polygon_key, tri_key;   // ordinal in flattened list order
+    std::vector<uint32_t> ordinal_shape;                      // ordinal -> (index into Scene.shapes, triangle index inside the Obj)
     uint32_t ordinal = 0;
     for (uint32_t i = 0; i < d->n_shapes; i++) {
         const rm_shape_ref &r = d->shapes[i];
@@ -556,14 +585,19 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
         case RM_SHAPE_SPHERE:
             if (r.first >= d->n_spheres || r.count != 1) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad sphere ref");
             sphere_src.push_back(r.first); sphere_key.push_back(ordinal++);
+            ordinal_shape.insert(ordinal_shape.end(), {i, 0u});
             break;
         case RM_SHAPE_POLYGON:
             if (r.first >= d->n_polygons || r.count != 1) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad polygon ref");
             polygon_src.push_back(r.first); polygon_key.push_back(ordinal++);
+            ordinal_shape.insert(ordinal_shape.end(), {i, 0u});
             break;
         case RM_SHAPE_MESH:
             if ((uint64_t)r.first + r.count > d->n_triangles) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad mesh ref");
-            for (uint32_t t = 0; t < r.count; t++) { tri_src.push_back(r.first + t); tri_key.push_back(ordinal++); }
+            for (uint32_t t = 0; t < r.count; t++) {
+                tri_src.push_back(r.first + t); tri_key.push_back(ordinal++);
+                ordinal_shape.insert(ordinal_shape.end(), {i, t});
+            }
             break;
         default:
             return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: unknown shape kind");
@@ -610,6 +644,12 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     keys.insert(keys.end(), tri_key.begin(), tri_key.end());
     bool ordered = true;
     for (size_t i = 1; i < keys.size(); i++) ordered = ordered && keys[i - 1] < keys[i];
+    // the queries' way back from a device primitive to the reference's (shape, element): through the same keys
+    std::vector<uint32_t> pid_map(2u * keys.size());
+    for (size_t q = 0; q < keys.size(); q++) {
+        pid_map[2u * q] = ordinal_shape[2u * keys[q]];
+        pid_map[2u * q + 1u] = ordinal_shape[2u * keys[q] + 1u];
+    }
 
     rm_dev_header H{};
     H.n_spheres = (uint32_t)sphere_src.size();
@@ -817,6 +857,13 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
 
     // (a different description that builds the same device image -- an edit undone -- is not copied either)
     if (ctx->have_scene && blob == ctx->host_blob && std::memcmp(&H, &ctx->H, sizeof H) == 0) {
+        // (the same image can come from another shape list -- one Obj of two triangles, or two of one --: the
+        // queries' map is the image's too, and goes across alone where only it differs)
+        if (pid_map != ctx->host_pid_map) {
+            RM_HIP(ctx, hipSetDevice(ctx->device));
+            RM_HIP(ctx, hipDeviceSynchronize());          // a query may still be reading the old map
+            if (rm_status mst = upload_pid_map(ctx, pid_map)) return mst;
+        }
         ctx->camera = d->camera;
         keep_description();
         return RM_OK;
@@ -831,6 +878,10 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
         ctx->d_scene_words = blob.size();
     }
     RM_HIP(ctx, hipMemcpy(ctx->d_scene, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (rm_status mst = upload_pid_map(ctx, pid_map)) {
+        ctx->have_scene = false;                             // (the blob went across, its map did not: no half image)
+        return mst;
+    }
     ctx->H = H;
     ctx->camera = d->camera;
     ctx->have_scene = true;
@@ -1737,3 +1788,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 
 #include "rm_exchange.inc"
 #include "rm_hostio.inc"
+#include "rm_query_host.inc"

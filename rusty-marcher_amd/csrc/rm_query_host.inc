@@ -1,0 +1,191 @@
+// rm_query_host.inc -- host side of the ray queries (include/rusty_marcher_amd.h, "ray queries"); included at the end of
+// rm_device.hip.  The kernels are rm_query.hip's.
+//
+// Nothing here touches render state: the queries read the resident scene blob, the pid map the upload builds next to it
+// (rm_ctx::d_pid_map) and -- the pixel queries -- the backproject tables of the render (rebuilt for another frame geometry
+// exactly as a render would: the next render at its own geometry rebuilds them again, with the same values).  The host
+// variants stage their rays and answers in a buffer of their own on the context's stream.
+
+// What the queries accept of rm_params: the default band, no flag but RM_FLAG_FAST_FP (which they ignore: the queries
+// are the strict flavour).
+static rm_status check_query_params(rm_ctx *ctx, const rm_params *p, const char *who) {
+    if (!p) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL params");
+    if (!ctx->have_scene) return ctx_fail(ctx, RM_ERR_NO_SCENE, std::string(who) + ": no scene uploaded (rm_scene_upload)");
+    if (p->flags & ~RM_FLAG_FAST_FP)
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": params.flags may carry RM_FLAG_FAST_FP only (queries are always strict)");
+    if (p->patch_row_begin != 0u || p->patch_row_end != 0u || p->patch_row_stride > 1u)
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": queries take the default patch-row band only");
+    if (p->patch_size != RM_PATCH_SIZE) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": patch_size must be 32 (renderer.rs:47)");
+    if (p->frame_width == 0 || p->frame_height == 0) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": empty frame");
+    return RM_OK;
+}
+
+// The host variants' check of the reference's assert (sphere.rs:31, polygon.rs:62, triangle.rs:53): |d.d - 1| < 1e-4, with
+// d.d = (x x + y y) + z z as geometry.rs:180-182 forms it; every component of origin and direction finite.
+static rm_status check_rays(rm_ctx *ctx, const char *who, const rm_vec3 *o, const rm_vec3 *d, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        const bool finite = std::isfinite(o[i].x) && std::isfinite(o[i].y) && std::isfinite(o[i].z) && std::isfinite(d[i].x) &&
+                            std::isfinite(d[i].y) && std::isfinite(d[i].z);
+        const double nn = d[i].x * d[i].x + d[i].y * d[i].y + d[i].z * d[i].z;
+        if (!finite || !(std::fabs(nn - 1.) < 1e-4)) {
+            char buf[256];
+            std::snprintf(buf, sizeof buf, "%s: ray %u: origin (%g, %g, %g), direction (%g, %g, %g): %s", who, i, o[i].x, o[i].y, o[i].z,
+                          d[i].x, d[i].y, d[i].z, finite ? "direction is not of unit length (|d.d - 1| >= 1e-4)" : "not finite");
+            return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+        }
+    }
+    return RM_OK;
+}
+
+static rm_status launch_query(rm_ctx *ctx, int kind, QueryArgs &q, uint32_t blocks, hipStream_t stream) {
+    q.H = ctx->H;
+    q.pid_map = ctx->d_pid_map;
+    const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (as launch_render picks its kernels)
+    const void *fn = rm_query_kernel(kind, bvh);
+    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "query: no such kernel");
+    void *args[] = {(void *)&ctx->d_scene, (void *)&q};
+    RM_HIP(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(64), args, 0, stream));
+    return RM_OK;
+}
+
+static uint32_t ray_blocks(uint32_t n_rays) { return (uint32_t)(((uint64_t)n_rays + 63u) / 64u); }
+
+// The ray-list queries on device buffers, on `stream`.
+static rm_status query_rays(rm_ctx *ctx, bool occlusion, const void *origins, const void *directions, uint32_t n_rays, void *out,
+                            hipStream_t stream) {
+    QueryArgs q{};
+    q.origins = static_cast<const rm_vec3 *>(origins);
+    q.directions = static_cast<const rm_vec3 *>(directions);
+    q.n_rays = n_rays;
+    if (occlusion) q.occluded = static_cast<uint8_t *>(out);
+    else q.hits = static_cast<rm_hit *>(out);
+    return launch_query(ctx, occlusion ? RM_QUERY_OCCLUDED : RM_QUERY_CLOSEST, q, ray_blocks(n_rays), stream);
+}
+
+// The host variants' staging buffer: rays in, answers out (grown as needed; only synchronous calls use it).
+static rm_status query_staging(rm_ctx *ctx, size_t bytes, char **out) {
+    if (ctx->query_bytes < bytes) {
+        if (ctx->d_query) RM_HIP(ctx, hipFree(ctx->d_query));
+        ctx->d_query = nullptr;
+        ctx->query_bytes = 0;
+        RM_HIP(ctx, hipMalloc(&ctx->d_query, bytes));
+        ctx->query_bytes = bytes;
+    }
+    *out = static_cast<char *>(ctx->d_query);
+    return RM_OK;
+}
+
+static rm_status rays_host_impl(rm_ctx *ctx, const char *who, bool occlusion, const rm_vec3 *origins, const rm_vec3 *directions,
+                                uint32_t n_rays, void *out) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    if (!ctx->have_scene) return ctx_fail(ctx, RM_ERR_NO_SCENE, std::string(who) + ": no scene uploaded (rm_scene_upload)");
+    if (n_rays == 0) return RM_OK;
+    if (!origins || !directions || !out) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL array");
+    if (rm_status cst = check_rays(ctx, who, origins, directions, n_rays)) return cst;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ray_bytes = (size_t)n_rays * sizeof(rm_vec3);
+    const size_t out_bytes = (size_t)n_rays * (occlusion ? sizeof(uint8_t) : sizeof(rm_hit));
+    char *buf = nullptr;
+    if (rm_status sst = query_staging(ctx, 2u * ray_bytes + out_bytes, &buf)) return sst;
+    RM_HIP(ctx, hipMemcpyAsync(buf, origins, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
+    RM_HIP(ctx, hipMemcpyAsync(buf + ray_bytes, directions, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (rm_status qst = query_rays(ctx, occlusion, buf, buf + ray_bytes, n_rays, buf + 2u * ray_bytes, ctx->stream)) return qst;
+    RM_HIP(ctx, hipMemcpyAsync(out, buf + 2u * ray_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RM_OK;
+}
+
+static rm_status rays_device_impl(rm_ctx *ctx, const char *who, bool occlusion, const void *origins, const void *directions,
+                                  uint32_t n_rays, void *out, void *hip_stream) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    if (!ctx->have_scene) return ctx_fail(ctx, RM_ERR_NO_SCENE, std::string(who) + ": no scene uploaded (rm_scene_upload)");
+    if (n_rays == 0) return RM_OK;
+    if (!origins || !directions || !out) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL device buffer");
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    return query_rays(ctx, occlusion, origins, directions, n_rays, out, (hipStream_t)hip_stream);   // NULL: HIP's default stream, as rm_render_device
+}
+
+// The pixel queries: one pixel (n_tiles == 0) or the tiles of the whole patch rows.
+static rm_status query_pixels(rm_ctx *ctx, const rm_params *p, uint32_t x, uint32_t y, uint32_t n_tiles, rm_hit *out,
+                              hipStream_t stream) {
+    if (rm_status bst = backproject_tables(ctx, p)) return bst;
+    QueryArgs q{};
+    q.frame_width = p->frame_width;
+    q.tiles_per_row = p->frame_width / TILE_W;
+    q.n_tiles = n_tiles;
+    q.pick_x = x;
+    q.pick_y = y;
+    q.bp_x = ctx->d_backproject;
+    q.bp_y = ctx->d_backproject + p->frame_width;
+    q.cam_x = ctx->camera.x; q.cam_y = ctx->camera.y; q.cam_z = ctx->camera.z;
+    q.hits = out;
+    return launch_query(ctx, RM_QUERY_PIXELS, q, n_tiles ? n_tiles : 1u, stream);
+}
+
+static rm_status rm_pick_impl(rm_ctx *ctx, const rm_params *params, uint32_t x, uint32_t y, rm_hit *hit) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_pick: NULL ctx");
+    if (rm_status pst = check_query_params(ctx, params, "rm_pick")) return pst;
+    if (!hit) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_pick: NULL hit");
+    if (x >= params->frame_width || y >= params->frame_height) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "rm_pick: pixel (%u, %u) outside the %u x %u frame", x, y, params->frame_width, params->frame_height);
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+    }
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    char *buf = nullptr;
+    if (rm_status sst = query_staging(ctx, sizeof(rm_hit), &buf)) return sst;
+    if (rm_status qst = query_pixels(ctx, params, x, y, 0u, reinterpret_cast<rm_hit *>(buf), ctx->stream)) return qst;
+    RM_HIP(ctx, hipMemcpyAsync(hit, buf, sizeof(rm_hit), hipMemcpyDeviceToHost, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RM_OK;
+}
+
+static rm_status rm_primary_hits_device_impl(rm_ctx *ctx, const rm_params *params, void *device_hits, void *hip_stream) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_primary_hits_device: NULL ctx");
+    if (rm_status pst = check_query_params(ctx, params, "rm_primary_hits_device")) return pst;
+    if (params->frame_width % RM_PATCH_SIZE != 0)
+        return ctx_fail(ctx, RM_ERR_DIMENSIONS,
+                        "rm_primary_hits_device: frame width is not a multiple of 32; the reference's scatter "
+                        "(renderer.rs:92-108) indexes out of bounds and panics");
+    if (!device_hits) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_primary_hits_device: NULL device buffer");
+    const uint32_t n_rows = params->frame_height / RM_PATCH_SIZE;     // renderer.rs:53: the bottom H % 32 rows are not rendered
+    if (n_rows == 0) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n_tiles = (uint64_t)(params->frame_width / TILE_W) * (n_rows * RM_PATCH_SIZE / TILE_H);
+    if (n_tiles > 0x7FFFFFFFull) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_primary_hits_device: frame too large for one launch");
+    return query_pixels(ctx, params, 0u, 0u, (uint32_t)n_tiles, static_cast<rm_hit *>(device_hits), (hipStream_t)hip_stream);
+}
+
+extern "C" {
+
+rm_status rm_intersect_rays(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions, uint32_t n_rays, rm_hit *hits) {
+    return guarded(ctx, "rm_intersect_rays", [&]() { return rays_host_impl(ctx, "rm_intersect_rays", false, origins, directions, n_rays, hits); });
+}
+
+rm_status rm_occluded_rays(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions, uint32_t n_rays, uint8_t *occluded) {
+    return guarded(ctx, "rm_occluded_rays", [&]() { return rays_host_impl(ctx, "rm_occluded_rays", true, origins, directions, n_rays, occluded); });
+}
+
+rm_status rm_intersect_rays_device(rm_ctx *ctx, const void *device_origins, const void *device_directions, uint32_t n_rays,
+                                   void *device_hits, void *hip_stream) {
+    return guarded(ctx, "rm_intersect_rays_device", [&]() {
+        return rays_device_impl(ctx, "rm_intersect_rays_device", false, device_origins, device_directions, n_rays, device_hits, hip_stream);
+    });
+}
+
+rm_status rm_occluded_rays_device(rm_ctx *ctx, const void *device_origins, const void *device_directions, uint32_t n_rays,
+                                  void *device_occluded, void *hip_stream) {
+    return guarded(ctx, "rm_occluded_rays_device", [&]() {
+        return rays_device_impl(ctx, "rm_occluded_rays_device", true, device_origins, device_directions, n_rays, device_occluded, hip_stream);
+    });
+}
+
+rm_status rm_pick(rm_ctx *ctx, const rm_params *params, uint32_t x, uint32_t y, rm_hit *hit) {
+    return guarded(ctx, "rm_pick", [&]() { return rm_pick_impl(ctx, params, x, y, hit); });
+}
+
+rm_status rm_primary_hits_device(rm_ctx *ctx, const rm_params *params, void *device_hits, void *hip_stream) {
+    return guarded(ctx, "rm_primary_hits_device", [&]() { return rm_primary_hits_device_impl(ctx, params, device_hits, hip_stream); });
+}
+
+}  // extern "C"

@@ -335,14 +335,24 @@ struct Renderer {
         // (refused with RM_ERR_INVALID_ARG when the frame on the device is of another size: a window resized since)
         check(rm_fetch_rows(context(), rows.data(), (uint32_t)frame.width, (uint32_t)frame.height, 0, 0), ctx_);
     }
+    // What render(frame, sc) shows at pixel (x = column, y = row) of a width x height frame: the closest hit of the ray
+    // renderer.rs:80 casts there (rm_pick) -- hit.shape indexes sc.shapes; hit.hit == 0 where the ray leaves the scene.
+    rm_hit pick(size_t width_px, size_t height_px, const scene::Scene &sc, uint32_t x, uint32_t y) {
+        const rm_params p = prepare(width_px, height_px, sc, false);
+        rm_hit hit;
+        check(rm_pick(ctx_, &p, x, y, &hit), ctx_);
+        return hit;
+    }
     rm_ctx *context() { if (!ctx_) check(rm_init(0, &ctx_)); return ctx_; }
 
   private:
     rm_ctx *ctx_ = nullptr;
-    rm_params prepare(size_t width_px, size_t height_px, const scene::Scene &sc) {
+    rm_params prepare(size_t width_px, size_t height_px, const scene::Scene &sc, bool announce = true) {
         if (!ctx_) check(rm_init(0, &ctx_));
-        if (height_px % 32 != 0 || width_px % 32 != 0) std::printf("Dimensions mismatch\n");
-        std::printf("Rendering using patches of size %d, using %zu patches overall\n", 32, (height_px / 32) * (width_px / 32));
+        if (announce) {
+            if (height_px % 32 != 0 || width_px % 32 != 0) std::printf("Dimensions mismatch\n");
+            std::printf("Rendering using patches of size %d, using %zu patches overall\n", 32, (height_px / 32) * (width_px / 32));
+        }
         bool owned = false;
         rm_scene *flat = sc.flatten(&owned);
         rm_scene_desc d;

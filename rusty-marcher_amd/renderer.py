@@ -1,10 +1,16 @@
 """`Renderer` / `create_renderer` of engine/src/renderer.rs:17-126.  render() keeps
 the reference's contract -- synchronous, fills the caller's FrameBuffer, returns the
 status string -- and runs the patch loop on the MI355X through the C ABI."""
+import collections
 import ctypes as C
 import time
 
 from . import _lib, backend
+from .geometry import Vec3f
+
+# What is under a pixel: Intersection (shapes.rs:3-8) without the reflectance, with the ray parameter and where in
+# Scene.shapes it lies (shape: index into scene.shapes; element: the triangle inside an Obj, 0 otherwise).
+PickHit = collections.namedtuple("PickHit", "t point normal shape element")
 
 
 class Renderer:
@@ -39,6 +45,18 @@ class Renderer:
         info = ctx.device_info()
         print("%d compute units used" % info["cus"])                     # renderer.rs:124 prints the thread count
         return message
+
+    def pick(self, frame, scene, x, y):
+        """What render(frame, scene) shows at pixel (x = column, y = row): the closest hit of the ray renderer.rs:80
+        casts there (bit for bit the strict render's direction), or None where that ray leaves the scene."""
+        ctx = backend.default_context(self.device)
+        p = backend.make_params(self.fov, self.height, self.width, self.max_depth)
+        p.frame_width, p.frame_height = frame.width, frame.height
+        ctx.upload(scene.flatten())
+        h = ctx.pick(p, x, y)
+        if not h.hit:
+            return None
+        return PickHit(h.t, Vec3f(h.point.x, h.point.y, h.point.z), Vec3f(h.normal.x, h.normal.y, h.normal.z), h.shape, h.element)
 
 
 def create_renderer(fov, height, width):

@@ -108,6 +108,20 @@ pub struct RmFrameTimes {
     pub total_ms: f64,
 }
 
+/// One answer of find_closest_intersect (shapes.rs:110-143): what `Gpu::pick` returns.
+/// `shape` indexes `Scene.shapes` (not wrapped to u8); `element` is the triangle inside an `Obj`.
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmHit {
+    pub t: f64,
+    pub point: RmVec3,
+    pub normal: RmVec3,
+    pub shape: u32,
+    pub element: u32,
+    pub hit: i32,
+    pub _pad: u32,
+}
+
 pub enum RmScene {}
 pub enum RmCtx {}
 
@@ -170,6 +184,12 @@ extern "C" {
     fn rm_frame_timing_enable(ctx: *mut RmCtx, on: c_int) -> c_int;
     fn rm_frame_timing(ctx: *mut RmCtx, slot: u32, out: *mut RmFrameTimes) -> c_int;
     fn rm_comm_info(ctx: *mut RmCtx, rank: *mut c_int, world: *mut c_int, n_communicators: *mut c_int) -> c_int;
+    fn rm_intersect_rays(ctx: *mut RmCtx, origins: *const RmVec3, directions: *const RmVec3, n_rays: u32, hits: *mut RmHit) -> c_int;
+    fn rm_occluded_rays(ctx: *mut RmCtx, origins: *const RmVec3, directions: *const RmVec3, n_rays: u32, occluded: *mut u8) -> c_int;
+    fn rm_intersect_rays_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, n_rays: u32, device_hits: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_occluded_rays_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, n_rays: u32, device_occluded: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_pick(ctx: *mut RmCtx, params: *const RmParams, x: u32, y: u32, hit: *mut RmHit) -> c_int;
+    fn rm_primary_hits_device(ctx: *mut RmCtx, params: *const RmParams, device_hits: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -339,6 +359,34 @@ impl Gpu {
         let mut timing = RmTiming::default();
         check(unsafe { rm_render_display(self.ctx, &p, display.as_mut_ptr(), &mut timing) }, self.ctx);
         Gpu::status(now, frame_width, frame_height)
+    }
+
+    /// What `render` shows at pixel (x = column, y = row) of a `frame_width` x `frame_height` frame: the closest hit
+    /// of the ray renderer.rs:80 casts there -- the same direction as the frame's, bit for bit -- or None where that ray
+    /// leaves the scene.  `hit.shape` indexes `scene.shapes` (click-to-pick).
+    pub fn pick(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        scene: &::scene::Scene,
+        x: u32,
+        y: u32,
+    ) -> Option<RmHit> {
+        self.upload(scene);
+        let mut p: RmParams = unsafe { ::std::mem::zeroed() };
+        unsafe { rm_create_renderer(fov, height, width, &mut p) };
+        p.frame_width = frame_width as u32;
+        p.frame_height = frame_height as u32;
+        let mut hit: RmHit = unsafe { ::std::mem::zeroed() };
+        check(unsafe { rm_pick(self.ctx, &p, x, y, &mut hit) }, self.ctx);
+        if hit.hit != 0 {
+            Some(hit)
+        } else {
+            None
+        }
     }
 
     /// The f64 rows of the frame the last render left on the device, into `frame.buffer`.
