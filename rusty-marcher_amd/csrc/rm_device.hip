@@ -220,6 +220,10 @@ struct rm_ctx {
     uint32_t cull_min_prims = RM_CULL_MIN_PRIMS;   // RM_CULL_MIN (A/B knob)
     bool cull_edges = true;           // RM_CULL_EDGES=0: the bundle cull without its edge test (A/B knob)
     bool force_unstaged = false;      // RM_FORCE_UNSTAGED=1 (A/B knob)
+    // The shadow rays' occluder masks of the plain-walk kernels (rm_build_shadow_masks): RM_SHADOW_MASKS=0 uploads no
+    // table, and every shadow walk tests every primitive (A/B knob)
+    bool shadow_masks = true;
+    double occ_camera_limit = 0.;     // the resident image's: cameras farther out (L1 norm) render without its masks
     int force_stack = 0;              // RM_FORCE_STACK=4|8|16|32: a deeper ray stack than the depth cap needs (A/B knob)
     bool debug_empty = false;         // RM_DEBUG_EMPTY=1: measure the dispatch floor of a launch geometry
     // frame-to-frame feedback (rm_feedback): RM_FEEDBACK=0 never, 1 always, unset: launches of
@@ -416,6 +420,7 @@ rm_status rm_init(int device_ordinal, rm_ctx **out) {
     if (const char *env = std::getenv("RM_FORCE_GENERIC_POW")) ctx->force_generic_pow = env[0] == '1';
     if (const char *env = std::getenv("RM_FORCE_FAST_FP")) ctx->force_fast_fp = env[0] == '1';
     if (const char *env = std::getenv("RM_FORCE_UNSTAGED")) ctx->force_unstaged = env[0] == '1';
+    if (const char *env = std::getenv("RM_SHADOW_MASKS")) ctx->shadow_masks = env[0] != '0';
     if (const char *env = std::getenv("RM_DISABLE_BVH")) ctx->disable_bvh = env[0] == '1';
     if (const char *env = std::getenv("RM_FORCE_STACK")) ctx->force_stack = std::atoi(env);
     if (const char *env = std::getenv("RM_FEEDBACK")) ctx->feedback_mode = env[0] == '1' ? 1 : 0;
@@ -530,50 +535,15 @@ static rm_status upload_pid_map(rm_ctx *ctx, std::vector<uint32_t> &map) {
     return RM_OK;
 }
 
-static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
-    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL ctx");
-    if (!d) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL desc");
-    if ((d->n_shapes && !d->shapes) || (d->n_spheres && !d->spheres) || (d->n_polygons && !d->polygons) ||
-        (d->n_polygon_vertices && !d->polygon_vertices) || (d->n_triangles && !d->triangles) ||
-        (d->n_lights && !d->lights))
-        return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL array with non-zero count");
-
-    // The reference's hosts hand the whole Scene to every render() call (main.rs:331-333).  A
-    // description byte-identical to the one the resident image was built from (cameras apart:
-    // the camera travels as a kernel argument) needs no work at all.  Identity is decided on
-    // the bytes themselves -- the context keeps a copy of the arrays it last built from and
-    // compares in place, one pass, no hashing: a digest can collide, and a collision would
-    // silently render the old scene.
-    ctx->upload_calls++;
-    const struct { const void *p; size_t bytes; } parts[6] = {
-        {d->shapes, (size_t)d->n_shapes * sizeof(rm_shape_ref)},   {d->spheres, (size_t)d->n_spheres * sizeof(rm_sphere)},
-        {d->polygons, (size_t)d->n_polygons * sizeof(rm_polygon)}, {d->polygon_vertices, (size_t)d->n_polygon_vertices * sizeof(rm_vec3)},
-        {d->triangles, (size_t)d->n_triangles * sizeof(rm_triangle)}, {d->lights, (size_t)d->n_lights * sizeof(rm_light)}};
-    auto same_description = [&]() {
-        size_t off = 0;
-        for (int i = 0; i < 6; i++) {
-            if (ctx->desc_sizes[i] != parts[i].bytes) return false;
-            if (parts[i].bytes && std::memcmp(ctx->desc_bytes.data() + off, parts[i].p, parts[i].bytes) != 0) return false;
-            off += parts[i].bytes;
-        }
-        return true;
-    };
-    auto keep_description = [&]() {
-        size_t total = 0;
-        for (int i = 0; i < 6; i++) total += parts[i].bytes;
-        ctx->desc_bytes.resize(total);
-        size_t off = 0;
-        for (int i = 0; i < 6; i++) {
-            if (parts[i].bytes) std::memcpy(ctx->desc_bytes.data() + off, parts[i].p, parts[i].bytes);
-            ctx->desc_sizes[i] = parts[i].bytes;
-            off += parts[i].bytes;
-        }
-    };
-    if (ctx->have_scene && same_description()) {
-        ctx->camera = d->camera;
-        return RM_OK;
-    }
-
+// The device image of a description: header, blob, the queries' pid -> (shape, element) map.  Host work
+// only (rm_scene_upload copies it; rmi_shadow_masks hands its occluder masks to the tests).
+struct rm_image {
+    rm_dev_header H{};
+    std::vector<double> blob;
+    std::vector<uint32_t> pid_map;
+    double occ_camera_limit = 0.;      // |camera|_1 beyond which the render does not use the occluder masks
+};
+static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, bool shadow_masks, rm_image &img) {
     // ---- regroup Scene.shapes by kind, remembering list order for ties ----
     std::vector<uint32_t> sphere_src, polygon_src, tri_src;   // indices into desc arrays
     std::vector<uint32_t> sphere_key, polygon_key, tri_key;   // ordinal in flattened list order
@@ -606,7 +576,6 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     // ---- hierarchies over the spheres and the mesh triangles (rm_bvh.hpp): primitives of
     // a kind are re-ordered into leaf order; their list-order keys travel with them
     rm_bvh bvh_s, bvh_t;
-    const bool use_bvh = !ctx->disable_bvh;
     if (use_bvh && sphere_src.size() >= RM_BVH_MIN_SPHERES) {
         std::vector<rm_aabb> boxes(sphere_src.size());
         for (size_t i = 0; i < sphere_src.size(); i++) {
@@ -645,13 +614,15 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     bool ordered = true;
     for (size_t i = 1; i < keys.size(); i++) ordered = ordered && keys[i - 1] < keys[i];
     // the queries' way back from a device primitive to the reference's (shape, element): through the same keys
-    std::vector<uint32_t> pid_map(2u * keys.size());
+    std::vector<uint32_t> &pid_map = img.pid_map;
+    pid_map.assign(2u * keys.size(), 0u);
     for (size_t q = 0; q < keys.size(); q++) {
         pid_map[2u * q] = ordinal_shape[2u * keys[q]];
         pid_map[2u * q + 1u] = ordinal_shape[2u * keys[q] + 1u];
     }
 
-    rm_dev_header H{};
+    rm_dev_header &H = img.H;
+    H = rm_dev_header{};
     H.n_spheres = (uint32_t)sphere_src.size();
     H.n_polygons = (uint32_t)polygon_src.size();
     H.n_triangles = (uint32_t)tri_src.size();
@@ -697,7 +668,8 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     take(64u);                                               // batch loads may read past the last record
     H.total_words = off;
 
-    std::vector<double> blob(H.total_words ? H.total_words : 2, 0.);
+    std::vector<double> &blob = img.blob;
+    blob.assign(H.total_words ? H.total_words : 2, 0.);
     auto put_material = [&](uint32_t pid, const rm_reflectance &r) {
         double *m = &blob[H.off_materials + RM_MATERIAL_WORDS * pid];
         m[0] = r.diffusion;
@@ -855,6 +827,82 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     if (H.off_bvh_spheres) std::memcpy(&blob[H.off_bvh_spheres], bvh_s.nodes.data(), bvh_s.nodes.size() * sizeof(double));
     if (H.off_bvh_triangles) std::memcpy(&blob[H.off_bvh_triangles], bvh_t.nodes.data(), bvh_t.nodes.size() * sizeof(double));
 
+    // The shadow rays' occluder masks (rm_build_shadow_masks) for the plain-walk kernels' scenes, behind the
+    // image the staged kernels copy (the walks read them with scalar loads): scenes of up to 64 pids.
+    if (shadow_masks && n_prims > 0u && n_prims <= RM_SHADOW_MASK_MAX_PRIMS && H.n_lights > 0u) {
+        const uint64_t words = (uint64_t)n_prims * H.n_lights;
+        if ((uint64_t)H.total_words + words + 2u <= RM_SCENE_MAX_WORDS) {
+            H.off_occ = H.total_words;
+            blob.resize((size_t)H.total_words + ((words + 1u) & ~1ull), 0.);
+            rm_build_shadow_masks(blob.data(), H, reinterpret_cast<unsigned long long *>(&blob[H.off_occ]));
+            // the camera beyond which the table is not used (the hit points' rounding: 1e-7 of the scene's size
+            // is the builder's margin), from the coordinates it was built from
+            double size = 0.;
+            for (uint32_t q = 0; q < n_prims; q++) {
+                const double *w = &blob[H.off_bounds + 4u * q];
+                if (w[3] >= 0.) size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]) + w[3]);
+            }
+            for (uint32_t l = 0; l < H.n_lights; l++) {
+                const double *w = &blob[H.off_lights + RM_LIGHT_WORDS * l];
+                size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]));
+            }
+            img.occ_camera_limit = std::isfinite(size) ? 1e6 * (1. + size) : 0.;
+        }
+    }
+    return RM_OK;
+}
+
+static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL ctx");
+    if (!d) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL desc");
+    if ((d->n_shapes && !d->shapes) || (d->n_spheres && !d->spheres) || (d->n_polygons && !d->polygons) ||
+        (d->n_polygon_vertices && !d->polygon_vertices) || (d->n_triangles && !d->triangles) ||
+        (d->n_lights && !d->lights))
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL array with non-zero count");
+
+    // The reference's hosts hand the whole Scene to every render() call (main.rs:331-333).  A
+    // description byte-identical to the one the resident image was built from (cameras apart:
+    // the camera travels as a kernel argument) needs no work at all.  Identity is decided on
+    // the bytes themselves -- the context keeps a copy of the arrays it last built from and
+    // compares in place, one pass, no hashing: a digest can collide, and a collision would
+    // silently render the old scene.
+    ctx->upload_calls++;
+    const struct { const void *p; size_t bytes; } parts[6] = {
+        {d->shapes, (size_t)d->n_shapes * sizeof(rm_shape_ref)},   {d->spheres, (size_t)d->n_spheres * sizeof(rm_sphere)},
+        {d->polygons, (size_t)d->n_polygons * sizeof(rm_polygon)}, {d->polygon_vertices, (size_t)d->n_polygon_vertices * sizeof(rm_vec3)},
+        {d->triangles, (size_t)d->n_triangles * sizeof(rm_triangle)}, {d->lights, (size_t)d->n_lights * sizeof(rm_light)}};
+    auto same_description = [&]() {
+        size_t off = 0;
+        for (int i = 0; i < 6; i++) {
+            if (ctx->desc_sizes[i] != parts[i].bytes) return false;
+            if (parts[i].bytes && std::memcmp(ctx->desc_bytes.data() + off, parts[i].p, parts[i].bytes) != 0) return false;
+            off += parts[i].bytes;
+        }
+        return true;
+    };
+    auto keep_description = [&]() {
+        size_t total = 0;
+        for (int i = 0; i < 6; i++) total += parts[i].bytes;
+        ctx->desc_bytes.resize(total);
+        size_t off = 0;
+        for (int i = 0; i < 6; i++) {
+            if (parts[i].bytes) std::memcpy(ctx->desc_bytes.data() + off, parts[i].p, parts[i].bytes);
+            ctx->desc_sizes[i] = parts[i].bytes;
+            off += parts[i].bytes;
+        }
+    };
+    if (ctx->have_scene && same_description()) {
+        ctx->camera = d->camera;
+        return RM_OK;
+    }
+
+    rm_image img;
+    if (rm_status bst = build_image(ctx, d, !ctx->disable_bvh, ctx->shadow_masks, img)) return bst;
+    const rm_dev_header &H = img.H;
+    std::vector<double> &blob = img.blob;
+    std::vector<uint32_t> &pid_map = img.pid_map;
+    const uint32_t n_prims = H.n_spheres + H.n_polygons + H.n_triangles;
+
     // (a different description that builds the same device image -- an edit undone -- is not copied either)
     if (ctx->have_scene && blob == ctx->host_blob && std::memcmp(&H, &ctx->H, sizeof H) == 0) {
         // (the same image can come from another shape list -- one Obj of two triangles, or two of one --: the
@@ -883,6 +931,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
         return mst;
     }
     ctx->H = H;
+    ctx->occ_camera_limit = img.occ_camera_limit;
     ctx->camera = d->camera;
     ctx->have_scene = true;
     ctx->scene_epoch++;                                      // (the feedback of another scene's frames is void)
@@ -900,6 +949,24 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
 
 rm_status rm_scene_upload(rm_ctx *ctx, const rm_scene_desc *d) {
     return guarded(ctx, "rm_scene_upload", [&]() { return rm_scene_upload_impl(ctx, d); });
+}
+
+// Test hook, not part of the ABI (tests/test_shadow_masks.py): the occluder masks the upload of `d` builds, with
+// the knob's default.  dims[0] = pids, dims[1] = lights, dims[2] = 1 where there is a table; then, when there is
+// and cap >= pids x lights, occ[pid * lights + light] and shape_of[pid] = the pid's index into Scene.shapes.
+// Host work only: no device is needed.
+extern "C" rm_status rmi_shadow_masks(const rm_scene_desc *d, uint64_t *occ, uint32_t *shape_of, uint32_t cap, uint32_t *dims) {
+    if (!d || !dims) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rmi_shadow_masks: NULL argument");
+    rm_image img;
+    if (rm_status st = build_image(nullptr, d, true, true, img)) return st;
+    const rm_dev_header &H = img.H;
+    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
+    dims[0] = n; dims[1] = H.n_lights; dims[2] = H.off_occ ? 1u : 0u;
+    if (H.off_occ && occ && shape_of && (uint64_t)n * H.n_lights <= cap) {
+        std::memcpy(occ, &img.blob[H.off_occ], (size_t)n * H.n_lights * sizeof(uint64_t));
+        for (uint32_t q = 0; q < n; q++) shape_of[q] = img.pid_map[2u * q];
+    }
+    return RM_OK;
 }
 
 rm_status rm_scene_uploads(rm_ctx *ctx, uint64_t *calls, uint64_t *copies) {
@@ -1153,6 +1220,9 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
     a.bp_y = ctx->d_backproject + p->frame_width;
     a.half_fov = p->half_fov; a.height = p->height; a.width = p->width; a.ratio = p->ratio;
     a.cam_x = ctx->camera.x; a.cam_y = ctx->camera.y; a.cam_z = ctx->camera.z;
+    // (the occluder masks hold for hit points within 1e-7 of the scene's size of their primitives: a camera
+    // far enough out to round its hit points coarser than that renders without them)
+    if (!(std::fabs(ctx->camera.x) + std::fabs(ctx->camera.y) + std::fabs(ctx->camera.z) <= ctx->occ_camera_limit)) a.H.off_occ = 0u;
     a.bg_x = p->background.x; a.bg_y = p->background.y; a.bg_z = p->background.z;
     a.frame_width = p->frame_width;
     a.patch_row_begin = row_begin;

@@ -39,6 +39,10 @@ const char *rm_get_host_error();
 //   bvh       16 words per node (rm_bvh.hpp), one hierarchy over the spheres and one
 //                               over the triangles when there are enough of them; the
 //                               primitives of a kind are then stored in leaf order
+//   occ       1 u64 per pid and light, [pid][light], BEHIND the total_words of the image the
+//                               staged kernels copy into LDS (read with scalar loads only): the
+//                               primitives (bit = pid) a shadow ray cast from a hit on pid
+//                               towards that light can hit at all (rm_build_shadow_masks)
 struct rm_dev_header {
     uint32_t n_spheres, n_polygons, n_triangles, n_lights;
     uint32_t off_spheres, off_polygons, off_pverts, off_triangles;
@@ -49,8 +53,13 @@ struct rm_dev_header {
     uint32_t off_bounds;          // bounding sphere per pid (centre, radius: 4 words), inflated -- the bundle cull reads these
     uint32_t off_planar;          // per polygon / triangle (pid - n_spheres): lifted vertices + count, 16 words (cull_step)
     uint32_t off_groups;          // 0, or (scenes of 3 to 64 cull steps) a bounding sphere per 64 consecutive pids, 4 words each
+    uint32_t off_occ;             // 0, or (scenes of up to 64 pids) the shadow rays' occluder masks: n_prims x n_lights words
     double shadow_rho;            // every shadow ray passes within this of its light: 1e-3 x the longest normal (renderer.rs:168-172)
 };
+
+// occ[pid][light] from the image's bounds, lifted vertices, lights and shadow_rho (rm_scene.cpp)
+void rm_build_shadow_masks(const double *blob, const rm_dev_header &H, unsigned long long *occ);
+#define RM_SHADOW_MASK_MAX_PRIMS 64u
 
 #define RM_SPHERE_WORDS 4u
 #define RM_POLYGON_WORDS 16u   /* normal, plane point, (first vertex | count), pad, x/y of the first four vertices */

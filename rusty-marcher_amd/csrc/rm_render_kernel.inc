@@ -118,7 +118,7 @@ __device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArg
             if (where<DIV>(got)) {
                 const Surface s = surface_at<DIV>(sc, orig, dir, h, got);
                 const unsigned long long t_sd = RM_PHASE_T();
-                L = pick(got, bg + shade_direct<POW, BVH, CULL, EDGES>(sc, neg(dir), s, got), bg);
+                L = pick(got, bg + shade_direct<POW, BVH, CULL, EDGES>(sc, neg(dir), s, got, h.pid), bg);
                 RM_PHASE_ADD(sc, 3, t_sd);
                 if (DIV) acc = acc + scaled(L, weight);
                 const bool glass = got & (s.mat[8] != 0.);     // is_glass_like, renderer.rs:277
@@ -832,6 +832,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(POW 
     sc.H.list_ordered = own_sgpr(a.H.list_ordered);   sc.H.off_bvh_spheres = own_sgpr(a.H.off_bvh_spheres);
     sc.H.off_bvh_triangles = own_sgpr(a.H.off_bvh_triangles); sc.H.off_bounds = own_sgpr(a.H.off_bounds);
     sc.H.off_planar = own_sgpr(a.H.off_planar);       sc.H.off_groups = own_sgpr(a.H.off_groups);
+    sc.H.off_occ = own_sgpr(a.H.off_occ);
     sc.H.shadow_rho = own_sgpr(a.H.shadow_rho);
 
     const unsigned long long fb_t0 = feedback ? __builtin_amdgcn_s_memrealtime() : 0ull;

@@ -922,6 +922,61 @@ __device__ __forceinline__ void any_hit2(const SceneView &sc, V3 o, V3 d0, V3 d1
     out0 = occ0; out1 = occ1;
 }
 
+// The same walk over the primitives of `m0 | m1` only (wave-uniform, bit = pid, scenes of up to 64 pids): those
+// that ray 0 / ray 1 of SOME lane can hit at all (shadow_masks2).  A primitive outside a ray's mask is not
+// tested for it: no lane's answer can change, since the lane's own mask is part of the union.
+__device__ __forceinline__ void any_hit2_masked(const SceneView &sc, V3 o, V3 d0, V3 d1, bool decided0, bool decided1, bool &out0,
+                                                bool &out1, unsigned long long m0, unsigned long long m1) {
+    const double *__restrict__ S = sc.G;
+    const rm_dev_header &H = sc.H;
+    const uint32_t ns = H.n_spheres, np = H.n_polygons;
+    bool occ0 = decided0, occ1 = decided1;
+    unsigned long long m = m0 | m1;
+    while (m && !__all(occ0 & occ1)) {
+        const uint32_t pid = (uint32_t)__builtin_ctzll(m);
+        m &= m - 1ull;
+        const bool t0 = (m0 >> pid) & 1ull, t1 = (m1 >> pid) & 1ull;
+        if (pid < ns) {
+            const SphereRec s = load_sphere(S, H, pid);
+            const SphereFrom f = sphere_from(s, o);
+            if (t0) occ0 = occ0 | shadow_sphere_from(s, f, d0, occ0);
+            if (t1) occ1 = occ1 | shadow_sphere_from(s, f, d1, occ1);
+        } else if (pid < ns + np) {
+            const PolyRec pg = load_polygon(S, H, pid - ns);
+            const double num = plane_num(pg.px, pg.py, pg.pz, pg.nx, pg.ny, pg.nz, o);
+            double dist;
+            V3 p;
+            if (t0) occ0 = occ0 | polygon_hit_num(S, H, pg, pg.q, num, o, d0, !occ0, dist, p);
+            if (t1) occ1 = occ1 | polygon_hit_num(S, H, pg, pg.q, num, o, d1, !occ1, dist, p);
+        } else {
+            const TriRec t = load_triangle(S, H, pid - ns - np);
+            const double num = plane_num(t.cx, t.cy, t.cz, t.nx, t.ny, t.nz, o);
+            double dist;
+            V3 p;
+            if (t0) occ0 = occ0 | triangle_hit_num(t, num, o, d0, !occ0, dist, p);
+            if (t1) occ1 = occ1 | triangle_hit_num(t, num, o, d1, !occ1, dist, p);
+        }
+    }
+    out0 = occ0; out1 = occ1;
+}
+
+// Occluder masks (rm_build_shadow_masks, at upload; H.off_occ != 0): occ[q][l] holds every primitive a shadow ray
+// cast from a hit on q towards light l can hit.  The union of the rows of the primitives the wave's lanes shade
+// (`got`, `pid`), for lights l and l + 1, is all their walk needs.  (A scalar loop, one step per distinct
+// primitive: a vote, a lane read, two scalar loads.)
+__device__ __forceinline__ void shadow_masks2(const SceneView &sc, bool got, uint32_t pid, uint32_t l, unsigned long long &m0,
+                                              unsigned long long &m1) {
+    const unsigned long long *occ = reinterpret_cast<const unsigned long long *>(sc.G + sc.H.off_occ) + l;
+    unsigned long long left = __ballot(got);
+    m0 = 0ull; m1 = 0ull;
+    while (left) {
+        const uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)pid, (int)__builtin_ctzll(left));
+        m0 |= occ[q * sc.H.n_lights];
+        m1 |= occ[q * sc.H.n_lights + 1u];
+        left &= ~__ballot(got & (pid == q));
+    }
+}
+
 // `decided`: lanes whose answer is not needed (no hit to shade, or a light that adds
 // exactly zero); they come back as occluded.  `through` / `rho`: every shadow ray passes
 // within rho of that point -- the light (renderer.rs:166-172: the direction is taken from
@@ -1136,8 +1191,9 @@ __device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, con
     return a;
 }
 
+// `pid`: the primitive each lane's hit lies on.
 template <int POW, bool BVH, bool CULL, bool EDGES>
-__device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got) {
+__device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got, uint32_t pid) {
     const double *m = s.mat;
     const double exponent = m[5];
     // (colour and specular weight are fetched where a light is found unshadowed: held in
@@ -1163,6 +1219,8 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
                     __builtin_fma(lcol.z, spec, __builtin_fma(lcol.z * diffuse_color.z, di, li.z)));
         }
     };
+    // plain-walk kernels: the occluder masks of the walks, where the scene has them
+    const bool masks = !BVH && !CULL && sc.H.off_occ != 0u;
     for (uint32_t l = 0; l < sc.H.n_lights;) {
         const LightAt a = light_at(sc, l, s, dir_to_viewer, exponent);
         const bool dec_a = !got | a.dark;
@@ -1175,7 +1233,16 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
             if (__all(dec_a | dec_b | ((a.ldn < 0.) == (b.ldn < 0.)))) {
                 bool occ_a, occ_b;
                 const unsigned long long t_sh = RM_PHASE_T();
-                any_hit2(sc, pick(dec_a, b.from, a.from), a.dir, b.dir, dec_a, dec_b, occ_a, occ_b);
+                const V3 from = pick(dec_a, b.from, a.from);
+                unsigned long long m_a = 0ull, m_b = 0ull;
+                if (masks) shadow_masks2(sc, got, pid, l, m_a, m_b);
+                // (where both masks hold every primitive -- hits on the floor: its shadow rays can meet anything --
+                // the plain walk, which fetches its records in batches)
+                const uint32_t n = sc.H.n_spheres + sc.H.n_polygons + sc.H.n_triangles;
+                if (masks && (m_a & m_b) != ((n >= 64u) ? ~0ull : (1ull << n) - 1ull))
+                    any_hit2_masked(sc, from, a.dir, b.dir, dec_a, dec_b, occ_a, occ_b, m_a, m_b);
+                else
+                    any_hit2(sc, from, a.dir, b.dir, dec_a, dec_b, occ_a, occ_b);
                 RM_PHASE_ADD(sc, 1, t_sh);
                 add_light(l, a, !occ_a);                              // :174
                 add_light(l + 1u, b, !occ_b);
