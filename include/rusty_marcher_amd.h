@@ -513,6 +513,62 @@ rm_status rm_pick(rm_ctx *ctx, const rm_params *params, uint32_t x, uint32_t y, 
  */
 rm_status rm_primary_hits_device(rm_ctx *ctx, const rm_params *params, void *device_hits, void *hip_stream);
 
+/* ---- the oriented camera: look-at and turn for renders and pixel queries ------------------
+ *
+ * The reference's camera is a point (scene.rs:12) that always looks down -z with +y up
+ * (backproject, renderer.rs:128-135).  A context can be given a view direction as well: three
+ * world-space unit vectors, right, up and forward.  The fixed view is right (1,0,0), up (0,1,0),
+ * forward (0,0,-1).  Additive to ABI version 5; a host detects it by " camera" in
+ * rm_build_info().
+ *
+ * With bx = 2 (x / width - 0.5) half_fov ratio and by = -2 (y / height - 0.5) half_fov, the two
+ * numbers backproject forms for pixel (x, y), the primary ray of the pixel leaves the camera
+ * position along, per component c,
+ *     d.c = (bx * right.c + by * up.c) + forward.c
+ * (strict flavour: two products and two sums, each rounded once, in this order, no fused
+ * multiply-add; the fast flavour may contract), normalised as every direction is.  Nothing else
+ * changes: same patches and rows, same shading, same frame formats.
+ *
+ * The oriented state belongs to the context, like rm_camera_update's position: it is off after
+ * rm_init, survives rm_scene_upload (which still sets the position from desc.camera), and holds
+ * for every render entry point, every stream and frame slot, rm_pick and rm_primary_hits_device.
+ * The ray-list queries take the caller's rays and are not concerned.  While it is off every
+ * launch runs the fixed view's kernels and gives the fixed view's frames bit for bit.  A basis
+ * whose nine components compare equal (==) to the fixed view's turns it off again rather than
+ * on: "identity" never differs from "unset".
+ *
+ * A basis is accepted when all nine numbers are finite, every vector's squared length is
+ * within 1e-12 of 1 and every pairwise dot product within 1e-12 of 0; otherwise
+ * RM_ERR_INVALID_ARG, and the context keeps what it had.  Left-handed bases are accepted (the
+ * picture is mirrored).
+ */
+typedef struct rm_camera_basis {
+    rm_vec3 right, up, forward;
+} rm_camera_basis;
+
+/* Sets the context's view direction; basis == NULL resets it to the fixed view. */
+rm_status rm_camera_orient(rm_ctx *ctx, const rm_camera_basis *basis);
+/* rm_camera_update(eye) and rm_camera_orient(rm_camera_basis_look_at(eye, target, up_hint)) in
+ * one call; on failure neither is changed.  Needs an uploaded scene, as rm_camera_update. */
+rm_status rm_camera_look_at(rm_ctx *ctx, rm_vec3 eye, rm_vec3 target, rm_vec3 up_hint);
+/* What the context renders with: position, basis (the fixed view's while the state is off),
+ * and whether the oriented state is on.  Every out-pointer is optional. */
+rm_status rm_camera_get(rm_ctx *ctx, rm_vec3 *position, rm_camera_basis *basis, int *oriented);
+/* Host arithmetic only -- no GPU, no context:
+ * forward = unit(target - eye), right = unit(forward x up_hint), up = right x forward.
+ * RM_ERR_INVALID_ARG for eye == target, an up_hint parallel to the line of sight (or zero),
+ * non-finite input.  eye (0,0,0), target (0,0,-1), up_hint (0,1,0) gives a basis that compares
+ * equal to the fixed view. */
+rm_status rm_camera_basis_look_at(rm_vec3 eye, rm_vec3 target, rm_vec3 up_hint, rm_camera_basis *out);
+/* Turns a basis about its own axes, in this order: yaw about up, pitch about right, roll about
+ * forward (radians), then makes it orthonormal again (a thousand small turns still pass the
+ * check; handedness is kept).  Positive yaw turns left (counter-clockwise seen from the tip of
+ * up: the fixed view yawed by pi/2 looks down -x), positive pitch looks up (forward towards
+ * up), positive roll tips the camera's up towards its right.  in == out is allowed. */
+rm_status rm_camera_basis_turn(const rm_camera_basis *in, double yaw, double pitch, double roll, rm_camera_basis *out);
+/* RM_OK where rm_camera_orient would accept the basis. */
+rm_status rm_camera_basis_check(const rm_camera_basis *basis);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

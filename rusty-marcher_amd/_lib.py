@@ -87,6 +87,11 @@ class rm_hit(C.Structure):
                 ("element", C.c_uint32), ("hit", C.c_int32), ("_pad", C.c_uint32)]
 
 
+class rm_camera_basis(C.Structure):
+    """The oriented camera's view direction: three world-space unit vectors (72 bytes)."""
+    _fields_ = [("right", rm_vec3), ("up", rm_vec3), ("forward", rm_vec3)]
+
+
 _P = C.POINTER
 _VP = C.c_void_p
 
@@ -114,6 +119,12 @@ SIGNATURES = {
     "rm_scene_upload": (C.c_int, [_VP, _P(rm_scene_desc)]),
     "rm_scene_uploads": (C.c_int, [_VP, _P(C.c_uint64), _P(C.c_uint64)]),
     "rm_camera_update": (C.c_int, [_VP, rm_vec3]),
+    "rm_camera_orient": (C.c_int, [_VP, _P(rm_camera_basis)]),
+    "rm_camera_look_at": (C.c_int, [_VP, rm_vec3, rm_vec3, rm_vec3]),
+    "rm_camera_get": (C.c_int, [_VP, _P(rm_vec3), _P(rm_camera_basis), _P(C.c_int)]),
+    "rm_camera_basis_look_at": (C.c_int, [rm_vec3, rm_vec3, rm_vec3, _P(rm_camera_basis)]),
+    "rm_camera_basis_turn": (C.c_int, [_P(rm_camera_basis), C.c_double, C.c_double, C.c_double, _P(rm_camera_basis)]),
+    "rm_camera_basis_check": (C.c_int, [_P(rm_camera_basis)]),
     "rm_render": (C.c_int, [_VP, _P(rm_params), _P(C.c_double), _P(rm_timing)]),
     "rm_render_rows": (C.c_int, [_VP, _P(rm_params), _P(_P(C.c_double)), _P(rm_timing)]),
     "rm_render_display": (C.c_int, [_VP, _P(rm_params), _P(C.c_uint8), _P(rm_timing)]),
@@ -194,6 +205,14 @@ def check(status, ctx=None):
     if status != RM_OK:
         msg = lib().rm_last_error(ctx)
         raise BackendError(status, msg.decode() if msg else "")
+
+
+def camera_basis(b):
+    """rm_camera_basis from one, or from three vectors (right, up, forward)."""
+    if isinstance(b, rm_camera_basis):
+        return b
+    right, up, forward = b
+    return rm_camera_basis(vec3(right), vec3(up), vec3(forward))
 
 
 def vec3(v):

@@ -71,6 +71,23 @@ class Context:
     def set_camera(self, cam):
         _lib.check(self.L.rm_camera_update(self.ptr, _lib.vec3(cam)), self.ptr)
 
+    # ---- the oriented camera (include/rusty_marcher_amd.h, "the oriented camera") ----
+    def orient(self, basis=None):
+        """View direction of every later render and pixel query: an rm_camera_basis or (right, up, forward); None resets to
+        the reference's fixed view (down -z, +y up)."""
+        b = None if basis is None else C.byref(_lib.camera_basis(basis))
+        _lib.check(self.L.rm_camera_orient(self.ptr, b), self.ptr)
+
+    def look_at(self, eye, target, up=(0., 1., 0.)):
+        """Camera at `eye`, looking at `target`."""
+        _lib.check(self.L.rm_camera_look_at(self.ptr, _lib.vec3(eye), _lib.vec3(target), _lib.vec3(up)), self.ptr)
+
+    def camera(self):
+        """(position, basis, oriented) the context renders with."""
+        pos, b, on = _lib.rm_vec3(), _lib.rm_camera_basis(), C.c_int(0)
+        _lib.check(self.L.rm_camera_get(self.ptr, C.byref(pos), C.byref(b), C.byref(on)), self.ptr)
+        return pos, b, bool(on.value)
+
     def render(self, params, host_array=None):
         t = _lib.rm_timing()
         ptr = host_array.ctypes.data_as(C.POINTER(C.c_double)) if host_array is not None else None
@@ -321,3 +338,21 @@ def make_params(fov, height, width, max_depth=3, band=None):
         if len(band) > 2:
             p.patch_row_stride = int(band[2])
     return p
+
+
+# ---- the oriented camera's host arithmetic (no GPU, no context) ----
+FIXED_VIEW = ((1., 0., 0.), (0., 1., 0.), (0., 0., -1.))
+
+
+def basis_look_at(eye, target, up=(0., 1., 0.)):
+    """rm_camera_basis_look_at: forward = unit(target - eye), right = unit(forward x up), up = right x forward."""
+    out = _lib.rm_camera_basis()
+    _lib.check(_lib.lib().rm_camera_basis_look_at(_lib.vec3(eye), _lib.vec3(target), _lib.vec3(up), C.byref(out)))
+    return out
+
+
+def basis_turn(basis, yaw=0., pitch=0., roll=0.):
+    """rm_camera_basis_turn: about the basis' own up, right, forward (radians; positive yaw turns left)."""
+    out = _lib.rm_camera_basis()
+    _lib.check(_lib.lib().rm_camera_basis_turn(C.byref(_lib.camera_basis(basis)), float(yaw), float(pitch), float(roll), C.byref(out)))
+    return out

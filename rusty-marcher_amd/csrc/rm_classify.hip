@@ -20,20 +20,30 @@
 // Conservative by construction -- a primitive some ray of the tile hits is never dropped -- so the
 // frame is bit-identical with the classification off (RM_TILE_CLASSIFY=0;
 // tests/test_gpu_parity.py::test_tile_classification_is_bitwise_invisible).
+// (compiled twice: for the fixed view and, -DRM_KERNEL_ORIENTED=1, for the oriented camera -- cone_of then sends the rectangle
+// through the view's basis)
 #define RM_KERNEL_FAST 0
 #include "rm_render_kernel.hpp"
 
 using namespace rmdev;
+#if RM_KERNEL_ORIENTED
+using namespace rmdev_strict_o;
+#define RM_CLASSIFY_KERNEL rm_classify_tiles_oriented_kernel
+#define RM_CLASSIFY_PICK rm_classify_kernel_oriented
+#else
 using namespace rmdev_strict;
+#define RM_CLASSIFY_KERNEL rm_classify_tiles_kernel
+#define RM_CLASSIFY_PICK rm_classify_kernel
+#endif
 
 template <bool EDGES>
-__global__ __launch_bounds__(64) void rm_classify_tiles_kernel(const double *__restrict__ scene_blob, KernelArgs a, ClassifyArgs o) {
+__global__ __launch_bounds__(64) void RM_CLASSIFY_KERNEL(const double *__restrict__ scene_blob, KernelArgs a, ClassifyArgs o) {
     const uint32_t patch = blockIdx.x * 4u + ((threadIdx.x & 63u) >> 4);
     unsigned long long sig, own;
     const bool valid = patch < (a.n_tiles >> 4);
     (void)classify_patches<EDGES>(cls_view_of_blob(scene_blob, a.H), a, patch, valid, classify_ask(a, patch, valid), o.tile_mask, o.n_prims, 0u, sig, own);
 }
 
-const void *rmdev::rm_classify_kernel(bool edges) {
-    return edges ? (const void *)rm_classify_tiles_kernel<true> : (const void *)rm_classify_tiles_kernel<false>;
+const void *rmdev::RM_CLASSIFY_PICK(bool edges) {
+    return edges ? (const void *)RM_CLASSIFY_KERNEL<true> : (const void *)RM_CLASSIFY_KERNEL<false>;
 }

@@ -25,17 +25,26 @@ __device__ __forceinline__ V3 unit(V3 a) {
 // holds its corners.  The margins are far beyond the rounding of the kernel's own normalisation of the same
 // table values.  False: the cone tests do not hold for it (half-angle towards 90 degrees -- a frame of a few
 // tiles -- or a camera / table value that is not a number): everything is kept.
+#if RM_KERNEL_ORIENTED
+// (oriented camera: the rectangle's points go through the view's linear map, (bx right + by up) + forward, as the render's rays
+// do: the rectangle becomes a parallelogram in world space, still convex, its corners still its extreme points)
+__device__ __forceinline__ V3 cls_dir(const KernelArgs &a, double bx, double by) {
+    return mk((bx * a.cam_rx + by * a.cam_ux) + a.cam_fx, (bx * a.cam_ry + by * a.cam_uy) + a.cam_fy, (bx * a.cam_rz + by * a.cam_uz) + a.cam_fz);
+}
+#else
+__device__ __forceinline__ V3 cls_dir(const KernelArgs &, double bx, double by) { return mk(bx, by, -1.); }
+#endif
 template <bool SHARED>
 __device__ __forceinline__ bool cone_of(Bundle &b, const KernelArgs &a, double bx0, double bx1, double by0, double by1, uint32_t sub) {
-    const V3 u = unit(mk(0.5 * (bx0 + bx1), 0.5 * (by0 + by1), -1.));
+    const V3 u = unit(cls_dir(a, 0.5 * (bx0 + bx1), 0.5 * (by0 + by1)));
     double cm;
     if (SHARED) {                                                  // the lanes of a group share the rectangle: a corner each
-        cm = dot(unit(mk((sub & 1u) ? bx1 : bx0, (sub & 2u) ? by1 : by0, -1.)), u);
+        cm = dot(unit(cls_dir(a, (sub & 1u) ? bx1 : bx0, (sub & 2u) ? by1 : by0)), u);
         cm = __builtin_fmin(cm, __shfl_xor(cm, 1, 64));
         cm = __builtin_fmin(cm, __shfl_xor(cm, 2, 64));
     } else {
-        cm = __builtin_fmin(__builtin_fmin(dot(unit(mk(bx0, by0, -1.)), u), dot(unit(mk(bx1, by0, -1.)), u)),
-                            __builtin_fmin(dot(unit(mk(bx0, by1, -1.)), u), dot(unit(mk(bx1, by1, -1.)), u)));
+        cm = __builtin_fmin(__builtin_fmin(dot(unit(cls_dir(a, bx0, by0)), u), dot(unit(cls_dir(a, bx1, by0)), u)),
+                            __builtin_fmin(dot(unit(cls_dir(a, bx0, by1)), u), dot(unit(cls_dir(a, bx1, by1)), u)));
     }
     cm -= 1e-9;
     b.ax = a.cam_x; b.ay = a.cam_y; b.az = a.cam_z;

@@ -178,7 +178,7 @@ struct rm_tile_lists {
     // first launch of the view being rendered, the first of this geometry and scene, and that view
     unsigned long long *hint = nullptr;
     uint32_t seq = 0, view_seq0 = 0, key_seq0 = 0, ord_tag = 0;
-    double view[7] = {0., 0., 0., 0., 0., 0., 0.};
+    double view[16] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};   // camera, Renderer, the camera's basis
     // classification at the head of the render launch: the words carry the launch's tag (1..255)
     uint32_t tag = 0, tagged_tiles = 0;
     uint64_t tagged_scene = 0;
@@ -200,6 +200,11 @@ struct rm_ctx {
     double *d_scene = nullptr;
     size_t d_scene_words = 0;
     rm_vec3 camera{0., 0., 0.};
+    // The oriented camera (rm_camera_orient / rm_camera_look_at).  Off: the reference's fixed view -- down -z, +y up -- and the
+    // kernels that have it built in.  On: `basis` is a real turn (never the fixed view's own nine numbers: setting those turns
+    // the state off) and every launch takes the oriented kernels.  The context's, like `camera`: an upload leaves it alone.
+    bool oriented = false;
+    rm_camera_basis basis{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
     std::vector<double> host_blob;    // the device image of the resident scene (rm_scene_upload skips identical ones)
     uint64_t upload_calls = 0, upload_copies = 0;
     std::vector<unsigned char> desc_bytes;   // the description arrays the resident image was built from, back to back
@@ -361,6 +366,10 @@ static constexpr size_t RM_BVH_MIN_SPHERES = 16, RM_BVH_MIN_TRIANGLES = 12;
 #define RM_DECLARE_GROUP(g) \
     const void *rm_pick_kernel_strict_g##g(bool edges, int order, int stack, int pow_mode); \
     const void *rm_pick_kernel_fast_g##g(bool edges, int order, int stack, int pow_mode);
+#define RM_DECL_PICK_O(g) \
+    const void *rm_pick_kernel_strict_o_g##g(bool edges, int order, int stack, int pow_mode); \
+    const void *rm_pick_kernel_fast_o_g##g(bool edges, int order, int stack, int pow_mode);
+RM_DECL_PICK_O(0) RM_DECL_PICK_O(1) RM_DECL_PICK_O(2) RM_DECL_PICK_O(3)
 RM_DECLARE_GROUP(0) RM_DECLARE_GROUP(1) RM_DECLARE_GROUP(2) RM_DECLARE_GROUP(3) RM_DECLARE_GROUP(4)
 #undef RM_DECLARE_GROUP
 
@@ -377,10 +386,22 @@ const void *rm_pick_kernel(bool fast, bool staged, bool bvh, bool cull, bool edg
     }
 }
 
+const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull, bool edges, int stack, int pow_mode) {
+    const int group = staged ? (cull ? 1 : 0) : !bvh ? 2 : 3;
+    if (staged && bvh) return nullptr;
+    if (!staged && !cull) return nullptr;
+    switch (group) {
+    case 0: return fast ? rm_pick_kernel_fast_o_g0(edges, 1, stack, pow_mode) : rm_pick_kernel_strict_o_g0(edges, 1, stack, pow_mode);
+    case 1: return fast ? rm_pick_kernel_fast_o_g1(edges, 1, stack, pow_mode) : rm_pick_kernel_strict_o_g1(edges, 1, stack, pow_mode);
+    case 2: return fast ? rm_pick_kernel_fast_o_g2(edges, 1, stack, pow_mode) : rm_pick_kernel_strict_o_g2(edges, 1, stack, pow_mode);
+    default: return fast ? rm_pick_kernel_fast_o_g3(edges, 1, stack, pow_mode) : rm_pick_kernel_strict_o_g3(edges, 1, stack, pow_mode);
+    }
+}
+
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -983,6 +1004,43 @@ rm_status rm_camera_update(rm_ctx *ctx, rm_vec3 camera) {
     return RM_OK;
 }
 
+// The fixed view: the reference's backproject looks down -z with +y up.
+static const rm_camera_basis k_fixed_view{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
+
+static void set_basis(rm_ctx *ctx, const rm_camera_basis &b) {
+    // (== component by component: a -0 that a cross product leaves counts as 0, and the state then holds the fixed view's own words)
+    const bool fixed = b.right.x == 1. && b.right.y == 0. && b.right.z == 0. && b.up.x == 0. && b.up.y == 1. && b.up.z == 0. &&
+                       b.forward.x == 0. && b.forward.y == 0. && b.forward.z == -1.;
+    ctx->oriented = !fixed;
+    ctx->basis = fixed ? k_fixed_view : b;
+}
+
+rm_status rm_camera_orient(rm_ctx *ctx, const rm_camera_basis *basis) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_camera_orient: NULL ctx");
+    if (!basis) { set_basis(ctx, k_fixed_view); return RM_OK; }
+    if (rm_status st = rm_camera_basis_check(basis)) return ctx_fail(ctx, st, std::string("rm_camera_orient: ") + rm_get_host_error());
+    set_basis(ctx, *basis);   // the basis travels as kernel arguments
+    return RM_OK;
+}
+
+rm_status rm_camera_look_at(rm_ctx *ctx, rm_vec3 eye, rm_vec3 target, rm_vec3 up_hint) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_camera_look_at: NULL ctx");
+    if (!ctx->have_scene) return ctx_fail(ctx, RM_ERR_NO_SCENE, "rm_camera_look_at: no scene uploaded");
+    rm_camera_basis b;
+    if (rm_status st = rm_camera_basis_look_at(eye, target, up_hint, &b)) return ctx_fail(ctx, st, std::string("rm_camera_look_at: ") + rm_get_host_error());
+    ctx->camera = eye;
+    set_basis(ctx, b);
+    return RM_OK;
+}
+
+rm_status rm_camera_get(rm_ctx *ctx, rm_vec3 *position, rm_camera_basis *basis, int *oriented) {
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_camera_get: NULL ctx");
+    if (position) *position = ctx->camera;
+    if (basis) *basis = ctx->basis;
+    if (oriented) *oriented = ctx->oriented ? 1 : 0;
+    return RM_OK;
+}
+
 // The patch rows a call owns: begin, begin + stride, ... < end.
 struct rm_band {
     uint32_t begin = 0, end = 0, stride = 1;
@@ -1180,7 +1238,8 @@ static rm_status choose_kernel(rm_ctx *ctx, const rm_params *p, uint32_t tiles, 
     k->order_in_big_scene = k->bvh && ctx->patch_order_mode != 0 && ctx->feedback_mode != 1 && !ctx->debug_empty && ctx->classify_mode != 0 &&
                             ctx->classify_in_launch && ctx->tile_order == TILE_ORDER_REVERSE && (22u * n_prims + 110u * n_planar) / 16u <= RM_CLASSIFY_IN_LAUNCH_MAX_COST &&
                             tiles / 16u <= ctx->patch_order_max_deep && (ctx->patch_order_mode == 1 || tiles >= ctx->classify_min_tiles);
-    k->feedback = k->bvh && !k->order_in_big_scene && ctx->feedback_mode != 0 && !ctx->debug_empty &&
+    // (an oriented launch never carries it: the oriented kernels come without -- it takes the hierarchy kernels as they are)
+    k->feedback = k->bvh && !k->order_in_big_scene && ctx->feedback_mode != 0 && !ctx->debug_empty && !ctx->oriented &&
                   (ctx->feedback_mode == 1 || (p->max_depth >= 6u && tiles >= RM_FEEDBACK_MIN_TILES));
     // the dispatch order: launches of up to 4,096 patches that do not carry the tile-level feedback (launches of more patches
     // than that may take the same kernels for the sky tail alone -- RM_SKY_TAIL_BIG=1: by place, below; r4: measured to buy
@@ -1189,7 +1248,9 @@ static rm_status choose_kernel(rm_ctx *ctx, const rm_params *p, uint32_t tiles, 
                (ctx->patch_order_mode != 0 && !k->feedback && !ctx->debug_empty && ctx->tile_order == TILE_ORDER_REVERSE &&
                 (tiles / 16u <= ctx->patch_order_max || (ctx->sky_tail && ctx->sky_tail_big && n_prims <= 56u && tiles / 16u >= ctx->sky_tail_big_min)) &&
                 (ctx->patch_order_mode == 1 || tiles >= ctx->classify_min_tiles));
-    k->fn = rm_pick_kernel(f, k->staged, k->bvh, k->cull, k->edges, k->order ? 1 : 0, k->feedback, st, pw);
+    // (the oriented kernels are the ones with the dispatch order: a launch without one runs them with ord_cnt == NULL)
+    k->fn = ctx->oriented ? rm_pick_kernel_oriented(f, k->staged, k->bvh, k->cull, k->edges, st, pw)
+                          : rm_pick_kernel(f, k->staged, k->bvh, k->cull, k->edges, k->order ? 1 : 0, k->feedback, st, pw);
     if (!k->fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "render: no kernel for this scene / depth combination");
     return RM_OK;
 }
@@ -1220,6 +1281,10 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
     a.bp_y = ctx->d_backproject + p->frame_width;
     a.half_fov = p->half_fov; a.height = p->height; a.width = p->width; a.ratio = p->ratio;
     a.cam_x = ctx->camera.x; a.cam_y = ctx->camera.y; a.cam_z = ctx->camera.z;
+    const rm_camera_basis &cb = ctx->basis;                  // (the fixed view's own while the oriented state is off; its kernels do not read it)
+    a.cam_rx = cb.right.x; a.cam_ry = cb.right.y; a.cam_rz = cb.right.z;
+    a.cam_ux = cb.up.x; a.cam_uy = cb.up.y; a.cam_uz = cb.up.z;
+    a.cam_fx = cb.forward.x; a.cam_fy = cb.forward.y; a.cam_fz = cb.forward.z;
     // (the occluder masks hold for hit points within 1e-7 of the scene's size of their primitives: a camera
     // far enough out to round its hit points coarser than that renders without them)
     if (!(std::fabs(ctx->camera.x) + std::fabs(ctx->camera.y) + std::fabs(ctx->camera.z) <= ctx->occ_camera_limit)) a.H.off_occ = 0u;
@@ -1347,7 +1412,7 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
                 o.n_prims = n_prims_all;
                 // sixteen lanes to a 32x32 patch, four patches to a wave
                 void *cargs[] = {(void *)&ctx->d_scene, (void *)&a, (void *)&o};
-                RM_HIP(ctx, hipLaunchKernel(rm_classify_kernel(n_planar > 0u), dim3((a.n_tiles / 16u + 3u) / 4u), dim3(64), cargs, 0, stream));
+                RM_HIP(ctx, hipLaunchKernel(ctx->oriented ? rm_classify_kernel_oriented(n_planar > 0u) : rm_classify_kernel(n_planar > 0u), dim3((a.n_tiles / 16u + 3u) / 4u), dim3(64), cargs, 0, stream));
             }
             a.tile_mask = tl->mask();
             a.mask_exact = n_prims_all <= (in_launch ? 56u : 64u) ? 1u : 0u;      // (a tagged word names 56 primitives, rm_classify.inc)
@@ -1411,7 +1476,9 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
             const uint32_t f = tl->order_frames++;
             const uint32_t seq = ++tl->seq;
             if (f == 0u) tl->key_seq0 = seq;
-            const double view[7] = {ctx->camera.x, ctx->camera.y, ctx->camera.z, p->half_fov, p->height, p->width, p->ratio};
+            // (the basis with it: a turn is a view that has moved -- no predecessor's order, first round or classification words)
+            const double view[16] = {ctx->camera.x, ctx->camera.y, ctx->camera.z, p->half_fov, p->height, p->width, p->ratio,
+                                     cb.right.x, cb.right.y, cb.right.z, cb.up.x, cb.up.y, cb.up.z, cb.forward.x, cb.forward.y, cb.forward.z};
             if (f == 0u || std::memcmp(tl->view, view, sizeof view) != 0) {
                 std::memcpy(tl->view, view, sizeof view);
                 tl->view_seq0 = seq;
@@ -1746,9 +1813,10 @@ rm_status rm_kernel_name(rm_ctx *ctx, const rm_params *params, char *buf, size_t
     st = choose_kernel(ctx, params, band.count() * (params->frame_width / RM_PATCH_SIZE) * 16u, &k);
     if (st != RM_OK) return st;
     // the name rocprofv3's kernel trace shows (template arguments in declaration order)
-    std::snprintf(buf, buflen, "%s::rm_render_static<%d, %d, %d, %d, %s, %s, %s, %s, %s, %s>", k.fast ? "rmdev_fast" : "rmdev_strict", k.stack,
+    // (the oriented camera's kernels: namespaces of their own, always the instantiation with the dispatch order)
+    std::snprintf(buf, buflen, "%s%s::rm_render_static<%d, %d, %d, %d, %s, %s, %s, %s, %s, %s>", k.fast ? "rmdev_fast" : "rmdev_strict", ctx->oriented ? "_o" : "", k.stack,
                   k.pow_mode, k.mode.waves, k.mode.per_wave, k.staged ? "true" : "false", k.bvh ? "true" : "false",
-                  k.cull ? "true" : "false", k.edges ? "true" : "false", k.order ? "true" : "false", k.feedback ? "true" : "false");
+                  k.cull ? "true" : "false", k.edges ? "true" : "false", (k.order || ctx->oriented) ? "true" : "false", k.feedback ? "true" : "false");
     return RM_OK;
 }
 

@@ -179,6 +179,11 @@ struct KernelArgs {
     unsigned long long *err_word;            // page-locked: non-zero once a wave of a launch on this stream gave up a wait that cannot fail (the frame is void)
     uint32_t launch_seq;
     uint32_t test_stall;                     // test hook: the order is never laid out (the waves behind the first round give up)
+    // Oriented camera (rm_camera_orient): the view's basis in world space, read by the ORIENTED kernels only
+    // (-DRM_KERNEL_ORIENTED=1, namespaces rmdev_strict_o / rmdev_fast_o) -- pixel (x, y) casts
+    // normalized((bp_x[x] * right + bp_y[y] * up) + forward) from the camera.  The fixed view's kernels, whose
+    // direction is (bp_x[x], bp_y[y], -1), never look at it.  (Last in the block: nothing in front of it moves.)
+    double cam_rx, cam_ry, cam_rz, cam_ux, cam_uy, cam_uz, cam_fx, cam_fy, cam_fz;
 };
 
 // What the classification launch gets besides the render launch's own arguments.
@@ -190,6 +195,7 @@ struct ClassifyArgs {
 
 // rm_classify.hip
 const void *rm_classify_kernel(bool edges);
+const void *rm_classify_kernel_oriented(bool edges);
 
 // Feedback histogram: tile times in 100 MHz ticks, four buckets per octave (bucket b holds
 // [edge(b), edge(b+1)), edge(b) = (4 + b % 4) << (b / 4) >> 2: 1, 1, 1, 1, 2, 2, 3, 3, 4, 5, 6, 7, 8, 10, ...);
@@ -222,5 +228,9 @@ struct StackEntry {
 // The kernel of a launch (rm_kernels.hip, compiled once per numeric flavour and kernel group):
 // stack 4 / 8 / 16 / 32, pow_mode POW_GENERIC / POW_INTEGER.  NULL: no such instantiation.
 const void *rm_pick_kernel(bool fast, bool staged, bool bvh, bool cull, bool edges, int order, bool feedback, int stack, int pow_mode);   // order: 0 off, 1 the dispatch order from the launch's own classification
+// ... of an oriented launch: the same kernels compiled with the basis in their ray generation and classification.  A reduced set:
+// the instantiations with the dispatch order only (they take launches without one as they are: ord_cnt == NULL), none with the
+// tile-level feedback (such launches take the hierarchy kernels without it).
+const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull, bool edges, int stack, int pow_mode);
 
 #endif

@@ -9,8 +9,12 @@
 //   group 4  hierarchy walk + bundle cull + frame-to-frame feedback             -- 256 spheres: C5
 #include "rm_render_kernel.hpp"
 
-#if RM_KERNEL_FAST
+#if RM_KERNEL_FAST && RM_KERNEL_ORIENTED
+namespace flavour = rmdev_fast_o;
+#elif RM_KERNEL_FAST
 namespace flavour = rmdev_fast;
+#elif RM_KERNEL_ORIENTED
+namespace flavour = rmdev_strict_o;
 #else
 namespace flavour = rmdev_strict;
 #endif
@@ -34,8 +38,12 @@ const void *pick(int stack, int pow_mode) {
 
 #define RM_PICK_CAT2(a, b, c) rm_pick_kernel_##a##_g##b
 #define RM_PICK_CAT(a, b) RM_PICK_CAT2(a, b, )
-#if RM_KERNEL_FAST
+#if RM_KERNEL_FAST && RM_KERNEL_ORIENTED
+#define RM_PICK_NAME RM_PICK_CAT(fast_o, RM_KERNEL_GROUP)
+#elif RM_KERNEL_FAST
 #define RM_PICK_NAME RM_PICK_CAT(fast, RM_KERNEL_GROUP)
+#elif RM_KERNEL_ORIENTED
+#define RM_PICK_NAME RM_PICK_CAT(strict_o, RM_KERNEL_GROUP)
 #else
 #define RM_PICK_NAME RM_PICK_CAT(strict, RM_KERNEL_GROUP)
 #endif
@@ -43,6 +51,15 @@ const void *pick(int stack, int pow_mode) {
 // (ORDER -- the dispatch order from the launch's own classification -- in every group but the one with the tile-level feedback)
 template <bool STAGED, bool BVH, bool CULL, bool FB>
 static const void *pick_eo(bool edges, int order, int stack, int pow_mode) {     // order: 0 off, 1 on
+#if RM_KERNEL_ORIENTED
+    // (the oriented camera's reduced set: the kernels with the dispatch order only -- rm_kernel_args.hpp)
+    static_assert(!FB, "no oriented kernels with the tile-level feedback");
+    (void)order;
+    if constexpr (CULL) {
+        if (edges) return pick<STAGED, BVH, CULL, true, true, false>(stack, pow_mode);
+    }
+    return pick<STAGED, BVH, CULL, false, true, false>(stack, pow_mode);
+#else
     if constexpr (FB) {
         return edges ? pick<STAGED, BVH, CULL, true, false, true>(stack, pow_mode) : pick<STAGED, BVH, CULL, false, false, true>(stack, pow_mode);
     } else {
@@ -51,6 +68,7 @@ static const void *pick_eo(bool edges, int order, int stack, int pow_mode) {    
         }
         return order ? pick<STAGED, BVH, CULL, false, true, false>(stack, pow_mode) : pick<STAGED, BVH, CULL, false, false, false>(stack, pow_mode);
     }
+#endif
 }
 
 const void *RM_PICK_NAME(bool edges, int order, int stack, int pow_mode) {
@@ -62,7 +80,7 @@ const void *RM_PICK_NAME(bool edges, int order, int stack, int pow_mode) {
     return pick_eo<false, false, true, false>(edges, order, stack, pow_mode);
 #elif RM_KERNEL_GROUP == 3
     return pick_eo<false, true, true, false>(edges, order, stack, pow_mode);
-#elif RM_KERNEL_GROUP == 4
+#elif RM_KERNEL_GROUP == 4 && !RM_KERNEL_ORIENTED
     return pick_eo<false, true, true, true>(edges, 0, stack, pow_mode);
 #else
 #error "RM_KERNEL_GROUP must be 0..4"

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64) void rm_query_rays_kernel(const double *__restr
     }
 }
 
-template <bool BVH>
+template <bool BVH, bool ORIENTED>
 __global__ __launch_bounds__(64) void rm_query_pixels_kernel(const double *__restrict__ scene_blob, QueryArgs q) {
     __shared__ uint32_t bstack[64];
     const SceneView sc = query_view(scene_blob, q.H, bstack);
@@ -94,7 +94,10 @@ __global__ __launch_bounds__(64) void rm_query_pixels_kernel(const double *__res
         on = true;
     }
     // renderer.rs:80 / :128-135, exactly as the strict render kernel forms it
-    const V3 d = normalized(mk(q.bp_x[x], q.bp_y[y], -1.));
+    // (ORIENTED: ... and as the oriented one does, (bx right + by up) + forward, every operation rounded once)
+    const double bx = q.bp_x[x], by = q.bp_y[y];
+    const V3 d = normalized(ORIENTED ? mk((bx * q.cam_rx + by * q.cam_ux) + q.cam_fx, (bx * q.cam_ry + by * q.cam_uy) + q.cam_fy, (bx * q.cam_rz + by * q.cam_uz) + q.cam_fz)
+                                     : mk(bx, by, -1.));
     const V3 o = mk(q.cam_x, q.cam_y, q.cam_z);
     Hit h{0., 0u};
     const bool got = closest_hit<BVH, false, false>(sc, o, d, on, h, false, 0ull);
@@ -105,11 +108,13 @@ __global__ __launch_bounds__(64) void rm_query_pixels_kernel(const double *__res
 
 using namespace rmquery;
 
-const void *rm_query_kernel(int kind, bool bvh) {
+const void *rm_query_kernel(int kind, bool bvh, bool oriented) {
     switch (kind) {
     case RM_QUERY_CLOSEST: return bvh ? (const void *)rm_query_rays_kernel<true, false> : (const void *)rm_query_rays_kernel<false, false>;
     case RM_QUERY_OCCLUDED: return bvh ? (const void *)rm_query_rays_kernel<true, true> : (const void *)rm_query_rays_kernel<false, true>;
-    case RM_QUERY_PIXELS: return bvh ? (const void *)rm_query_pixels_kernel<true> : (const void *)rm_query_pixels_kernel<false>;
+    case RM_QUERY_PIXELS:
+        if (oriented) return bvh ? (const void *)rm_query_pixels_kernel<true, true> : (const void *)rm_query_pixels_kernel<false, true>;
+        return bvh ? (const void *)rm_query_pixels_kernel<true, false> : (const void *)rm_query_pixels_kernel<false, false>;
     default: return nullptr;
     }
 }

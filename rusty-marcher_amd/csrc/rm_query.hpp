@@ -25,12 +25,15 @@ struct QueryArgs {
     double cam_x, cam_y, cam_z;
     rm_hit *hits;                            // RM_QUERY_CLOSEST / RM_QUERY_PIXELS
     uint8_t *occluded;                       // RM_QUERY_OCCLUDED
+    // RM_QUERY_PIXELS under an oriented camera (rm_camera_orient): right, up, forward, as the oriented render kernels get them
+    double cam_rx, cam_ry, cam_rz, cam_ux, cam_uy, cam_uz, cam_fx, cam_fy, cam_fz;
 };
 
 }  // namespace rmdev
 
 // The kernel of a query launch (64 lanes a workgroup, arguments: scene blob, QueryArgs).
 // bvh: the scene carries a hierarchy (rm_dev_header::off_bvh_spheres / off_bvh_triangles).
-const void *rm_query_kernel(int kind, bool bvh);
+// oriented (RM_QUERY_PIXELS only): the pixels' rays are formed from the camera's basis.
+const void *rm_query_kernel(int kind, bool bvh, bool oriented);
 
 #endif

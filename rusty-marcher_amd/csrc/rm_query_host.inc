@@ -41,7 +41,7 @@ static rm_status launch_query(rm_ctx *ctx, int kind, QueryArgs &q, uint32_t bloc
     q.H = ctx->H;
     q.pid_map = ctx->d_pid_map;
     const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (as launch_render picks its kernels)
-    const void *fn = rm_query_kernel(kind, bvh);
+    const void *fn = rm_query_kernel(kind, bvh, kind == RM_QUERY_PIXELS && ctx->oriented);
     if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "query: no such kernel");
     void *args[] = {(void *)&ctx->d_scene, (void *)&q};
     RM_HIP(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(64), args, 0, stream));
@@ -118,6 +118,10 @@ static rm_status query_pixels(rm_ctx *ctx, const rm_params *p, uint32_t x, uint3
     q.bp_x = ctx->d_backproject;
     q.bp_y = ctx->d_backproject + p->frame_width;
     q.cam_x = ctx->camera.x; q.cam_y = ctx->camera.y; q.cam_z = ctx->camera.z;
+    const rm_camera_basis &cb = ctx->basis;                          // (read by the oriented kernel only)
+    q.cam_rx = cb.right.x; q.cam_ry = cb.right.y; q.cam_rz = cb.right.z;
+    q.cam_ux = cb.up.x; q.cam_uy = cb.up.y; q.cam_uz = cb.up.z;
+    q.cam_fx = cb.forward.x; q.cam_fy = cb.forward.y; q.cam_fz = cb.forward.z;
     q.hits = out;
     return launch_query(ctx, RM_QUERY_PIXELS, q, n_tiles ? n_tiles : 1u, stream);
 }

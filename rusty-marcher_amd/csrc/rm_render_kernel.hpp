@@ -122,8 +122,17 @@ __device__ __forceinline__ void tile_origin(const KernelArgs &a, uint32_t tile, 
 }  // namespace rmdev
 
 // ---- the two numeric flavours of the same source --------------------------------------
+// (RM_KERNEL_ORIENTED=1: the same source again with the camera's basis in the ray generation and the tile classification,
+// in namespaces -- and so under kernel names -- of its own; the fixed view's kernels are compiled as if it did not exist)
+#ifndef RM_KERNEL_ORIENTED
+#define RM_KERNEL_ORIENTED 0
+#endif
 #if !defined(RM_KERNEL_FAST) || !RM_KERNEL_FAST
+#if RM_KERNEL_ORIENTED
+#define RM_FLAVOR_NS rmdev_strict_o
+#else
 #define RM_FLAVOR_NS rmdev_strict
+#endif
 #define RM_FAST 0
 #pragma clang fp contract(off)
 #include "rm_trace.inc"
@@ -134,7 +143,11 @@ __device__ __forceinline__ void tile_origin(const KernelArgs &a, uint32_t tile, 
 #endif
 
 #if !defined(RM_KERNEL_FAST) || RM_KERNEL_FAST
+#if RM_KERNEL_ORIENTED
+#define RM_FLAVOR_NS rmdev_fast_o
+#else
 #define RM_FLAVOR_NS rmdev_fast
+#endif
 #define RM_FAST 1
 #pragma clang fp contract(fast)
 #include "rm_trace.inc"

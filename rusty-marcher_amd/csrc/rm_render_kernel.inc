@@ -51,7 +51,15 @@ __device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArg
     // tabulates them once per frame geometry with these very operations, rm_device.hip
     // backproject_tables -- two loads instead of two divisions and six multiplies per pixel.)
     // (PREFETCHED: fetched by the caller -- in the kernels with the feedback they travel while the tile's flag does)
+#if RM_KERNEL_ORIENTED
+    // The oriented camera: the same two table values along the view's own right and up, plus its forward -- per component two
+    // products and two sums in this order (the strict flavour rounds each once; the fast one may contract).  The nine words are
+    // kernel arguments: scalar registers, one scalar operand to a vector instruction.
+    const double bx = PREFETCHED ? bp_x : a.bp_x[tx0 + (lane % TILE_W)], by = PREFETCHED ? bp_y : a.bp_y[ty0 + (lane / TILE_W)];
+    V3 dir = normalized(mk((bx * a.cam_rx + by * a.cam_ux) + a.cam_fx, (bx * a.cam_ry + by * a.cam_uy) + a.cam_fy, (bx * a.cam_rz + by * a.cam_uz) + a.cam_fz));
+#else
     V3 dir = normalized(PREFETCHED ? mk(bp_x, bp_y, -1.) : mk(a.bp_x[tx0 + (lane % TILE_W)], a.bp_y[ty0 + (lane / TILE_W)], -1.));
+#endif
     V3 orig = mk(a.cam_x, a.cam_y, a.cam_z);
     double weight = 1.;
     uint32_t depth = 1;                                       // renderer.rs:83

@@ -616,3 +616,97 @@ void rm_build_shadow_masks(const double *blob, const rm_dev_header &H, unsigned 
         }
     }
 }
+
+// ---- the oriented camera's host arithmetic (include/rusty_marcher_amd.h, "the oriented camera") ----------------
+// No device, no context: the CPU tests and every binding reach these.
+namespace {
+
+struct Cv { double x, y, z; };
+inline Cv cv(const rm_vec3 &v) { return Cv{v.x, v.y, v.z}; }
+inline rm_vec3 vec(const Cv &v) { return rm_vec3{v.x, v.y, v.z}; }
+inline double cdot(const Cv &a, const Cv &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+inline Cv ccross(const Cv &a, const Cv &b) { return Cv{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+inline Cv cscale(const Cv &a, double s) { return Cv{a.x * s, a.y * s, a.z * s}; }
+inline Cv cadd(const Cv &a, const Cv &b) { return Cv{a.x + b.x, a.y + b.y, a.z + b.z}; }
+inline bool cfinite(const Cv &a) { return std::isfinite(a.x) && std::isfinite(a.y) && std::isfinite(a.z); }
+// a / |a|; false where the length is zero or not a number
+inline bool cunit(const Cv &a, Cv *out) {
+    const double n2 = cdot(a, a);
+    if (!(n2 > 0.) || !std::isfinite(n2)) return false;
+    const double n = std::sqrt(n2);
+    *out = Cv{a.x / n, a.y / n, a.z / n};
+    return true;
+}
+
+rm_status basis_fail(const char *msg) {
+    rm_set_host_error(msg);
+    return RM_ERR_INVALID_ARG;
+}
+
+}  // namespace
+
+extern "C" {
+
+rm_status rm_camera_basis_check(const rm_camera_basis *b) {
+    if (!b) return basis_fail("rm_camera_basis_check: NULL basis");
+    const Cv r = cv(b->right), u = cv(b->up), f = cv(b->forward);
+    if (!cfinite(r) || !cfinite(u) || !cfinite(f)) return basis_fail("camera basis: a component is not finite");
+    const double tol = 1e-12;
+    if (!(std::fabs(cdot(r, r) - 1.) <= tol) || !(std::fabs(cdot(u, u) - 1.) <= tol) || !(std::fabs(cdot(f, f) - 1.) <= tol))
+        return basis_fail("camera basis: right, up and forward must be of unit length (squared length within 1e-12 of 1)");
+    if (!(std::fabs(cdot(r, u)) <= tol) || !(std::fabs(cdot(r, f)) <= tol) || !(std::fabs(cdot(u, f)) <= tol))
+        return basis_fail("camera basis: right, up and forward must be orthogonal (dot products within 1e-12 of 0)");
+    return RM_OK;
+}
+
+rm_status rm_camera_basis_look_at(rm_vec3 eye, rm_vec3 target, rm_vec3 up_hint, rm_camera_basis *out) {
+    if (!out) return basis_fail("rm_camera_basis_look_at: NULL out");
+    const Cv e = cv(eye), t = cv(target), h = cv(up_hint);
+    if (!cfinite(e) || !cfinite(t) || !cfinite(h)) return basis_fail("rm_camera_basis_look_at: eye, target or up_hint is not finite");
+    Cv f, r, hn;
+    if (!cunit(Cv{t.x - e.x, t.y - e.y, t.z - e.z}, &f)) return basis_fail("rm_camera_basis_look_at: eye and target coincide");
+    if (!cunit(h, &hn)) return basis_fail("rm_camera_basis_look_at: up_hint is zero");
+    // (the sine of the angle between the line of sight and the hint: below 1e-8 the cross product is mostly rounding)
+    const Cv side = ccross(f, hn);
+    if (!(cdot(side, side) > 1e-16) || !cunit(ccross(f, h), &r)) return basis_fail("rm_camera_basis_look_at: up_hint is parallel to the line of sight");
+    const Cv u = ccross(r, f);
+    rm_camera_basis b{vec(r), vec(u), vec(f)};
+    if (rm_camera_basis_check(&b) != RM_OK) return RM_ERR_INVALID_ARG;
+    *out = b;
+    return RM_OK;
+}
+
+rm_status rm_camera_basis_turn(const rm_camera_basis *in, double yaw, double pitch, double roll, rm_camera_basis *out) {
+    if (!in || !out) return basis_fail("rm_camera_basis_turn: NULL basis");
+    if (!std::isfinite(yaw) || !std::isfinite(pitch) || !std::isfinite(roll)) return basis_fail("rm_camera_basis_turn: an angle is not finite");
+    if (rm_status st = rm_camera_basis_check(in)) return st;
+    Cv r = cv(in->right), u = cv(in->up), f = cv(in->forward);
+    const double hand = cdot(u, ccross(r, f));                     // +1: right-handed (up = right x forward), -1: mirrored
+    {   // yaw about up: positive turns left -- forward towards -right
+        const double c = std::cos(yaw), s = std::sin(yaw);
+        const Cv f2 = cadd(cscale(f, c), cscale(r, -s)), r2 = cadd(cscale(r, c), cscale(f, s));
+        f = f2; r = r2;
+    }
+    {   // pitch about right: positive looks up -- forward towards up
+        const double c = std::cos(pitch), s = std::sin(pitch);
+        const Cv f2 = cadd(cscale(f, c), cscale(u, s)), u2 = cadd(cscale(u, c), cscale(f, -s));
+        f = f2; u = u2;
+    }
+    {   // roll about forward: positive tips up towards right
+        const double c = std::cos(roll), s = std::sin(roll);
+        const Cv u2 = cadd(cscale(u, c), cscale(r, s)), r2 = cadd(cscale(r, c), cscale(u, -s));
+        u = u2; r = r2;
+    }
+    // orthonormal again (Gram-Schmidt from forward; up from the other two, with the input's handedness)
+    Cv fn, rn;
+    if (!cunit(f, &fn)) return basis_fail("rm_camera_basis_turn: degenerate basis");
+    if (!cunit(cadd(r, cscale(fn, -cdot(r, fn))), &rn)) return basis_fail("rm_camera_basis_turn: degenerate basis");
+    Cv un = ccross(rn, fn);
+    if (hand < 0.) un = cscale(un, -1.);
+    rm_camera_basis b{vec(rn), vec(un), vec(fn)};
+    if (rm_status st = rm_camera_basis_check(&b)) return st;
+    *out = b;
+    return RM_OK;
+}
+
+}  // extern "C"

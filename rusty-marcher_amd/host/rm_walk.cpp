@@ -4,7 +4,7 @@
 // main.rs:337-346 to_vec into the pixbuf) becomes with rm_camera_update + rm_frame_submit.
 //
 //   rm_walk --rank R --world N --id-file PATH [--run-id TEXT] [--device D] [--frames K]
-//           [--step dx,dy,dz] [--width W] [--height H] [--depth D] [--fov F] [--fast-fp] [--out PREFIX]
+//           [--step dx,dy,dz] [--turn DEGREES] [--width W] [--height H] [--depth D] [--fov F] [--fast-fp] [--out PREFIX]
 //
 // Rank 0 creates the RCCL unique id and publishes it through PATH (written to PATH.tmp,
 // then renamed); the other ranks wait for the file.  The file starts with the launcher's
@@ -38,6 +38,7 @@ int main(int argc, char **argv) {
     rm_vec3 step{0., 0., -0.5};
     bool fast = false, use_rccl = true;
     std::string id_file, out, run_id = "rm_walk";
+    double turn_deg = 0.;                                       // --turn: yaw added per frame (degrees; the walk looks around)
     for (int i = 1; i < argc; i++) {
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "--rank")) rank = std::atoi(next());
@@ -51,10 +52,11 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--depth")) depth = (unsigned)std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--fov")) fov = std::atof(next());
         else if (!std::strcmp(argv[i], "--step")) { if (std::sscanf(next(), "%lf,%lf,%lf", &step.x, &step.y, &step.z) != 3) return 2; }
+        else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::atof(next());
         else if (!std::strcmp(argv[i], "--fast-fp")) fast = true;
         else if (!std::strcmp(argv[i], "--no-rccl")) use_rccl = false;
         else if (!std::strcmp(argv[i], "--out")) out = next();
-        else { std::fprintf(stderr, "usage: rm_walk --rank R --world N --id-file PATH [--run-id TEXT] [--device D] [--frames K] [--step dx,dy,dz] [--width W] [--height H] [--depth D] [--fov F] [--fast-fp] [--no-rccl] [--out PREFIX]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rm_walk --rank R --world N --id-file PATH [--run-id TEXT] [--device D] [--frames K] [--step dx,dy,dz] [--turn DEGREES] [--width W] [--height H] [--depth D] [--fov F] [--fast-fp] [--no-rccl] [--out PREFIX]\n"); return 2; }
     }
     if (world < 1 || rank < 0 || rank >= world) { std::fprintf(stderr, "need 0 <= rank < world\n"); return 2; }
     if (world > 1 && id_file.empty()) { std::fprintf(stderr, "--world > 1 needs --id-file\n"); return 2; }
@@ -142,6 +144,9 @@ int main(int argc, char **argv) {
 
     const auto t0 = std::chrono::steady_clock::now();
     rm_vec3 cam = desc.camera;
+    rm_camera_basis basis;                                       // (the fixed view; touched only under --turn)
+    CHECK(ctx, rm_camera_get(ctx, nullptr, &basis, nullptr));
+    const double turn_rad = turn_deg * 3.14159265358979323846 / 180.;
     for (unsigned k = 0; k < frames; k++) {
         const uint32_t s = k % n_slots;
         if (frame_in_slot[s] >= 0) consume(s);                  // frame k - n_slots: display it before its buffers are reused
@@ -149,6 +154,10 @@ int main(int argc, char **argv) {
         CHECK(ctx, rm_frame_submit_to_host(ctx, &p, d_rgb[s], d_gather[s], d_display[s], host[s], s));
         frame_in_slot[s] = (int)k;
         cam.x += step.x; cam.y += step.y; cam.z += step.z;
+        if (turn_rad != 0.) {                                   // the next frame looks a little further left (right: negative)
+            CHECK(ctx, rm_camera_basis_turn(&basis, turn_rad, 0., 0., &basis));
+            CHECK(ctx, rm_camera_orient(ctx, &basis));
+        }
     }
     for (unsigned k = frames; k < frames + n_slots; k++) {      // drain in frame order
         const uint32_t s = k % n_slots;

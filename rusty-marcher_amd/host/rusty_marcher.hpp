@@ -343,6 +343,24 @@ struct Renderer {
         check(rm_pick(ctx_, &p, x, y, &hit), ctx_);
         return hit;
     }
+    // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
+    // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
+    void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }
+    // ... towards `target` from `eye` (the caller's sc.camera); returns the basis
+    rm_camera_basis look_at(Vec3f eye, Vec3f target, Vec3f up = Vec3f{0., 1., 0.}) {
+        rm_camera_basis b;
+        check(rm_camera_basis_look_at(eye.c(), target.c(), up.c(), &b));
+        orient(&b);
+        return b;
+    }
+    // ... turned by yaw / pitch / roll (radians; positive yaw turns left, positive pitch looks up) from what the context holds
+    rm_camera_basis turn(double yaw, double pitch = 0., double roll = 0.) {
+        rm_camera_basis b, out;
+        check(rm_camera_get(context(), nullptr, &b, nullptr), ctx_);
+        check(rm_camera_basis_turn(&b, yaw, pitch, roll, &out));
+        orient(&out);
+        return out;
+    }
     rm_ctx *context() { if (!ctx_) check(rm_init(0, &ctx_)); return ctx_; }
 
   private:

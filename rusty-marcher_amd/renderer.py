@@ -35,6 +35,7 @@ class Renderer:
         p.frame_width, p.frame_height = frame.width, frame.height         # renderer.rs:53-54
         handle = scene.flatten()
         ctx.upload(handle)
+        ctx.orient(getattr(scene, "basis", None))                        # (the default context is shared: None resets)
         self.last_timing = ctx.render(p, frame.buffer)
 
         ms = int((time.perf_counter() - t0) * 1000.)                      # renderer.rs:111-112
@@ -53,6 +54,7 @@ class Renderer:
         p = backend.make_params(self.fov, self.height, self.width, self.max_depth)
         p.frame_width, p.frame_height = frame.width, frame.height
         ctx.upload(scene.flatten())
+        ctx.orient(getattr(scene, "basis", None))
         h = ctx.pick(p, x, y)
         if not h.hit:
             return None

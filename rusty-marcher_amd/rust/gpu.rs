@@ -122,6 +122,16 @@ pub struct RmHit {
     pub _pad: u32,
 }
 
+/// `rm_camera_basis`: the oriented camera's view direction, three world-space unit vectors (72 bytes).
+/// The reference's fixed view is right (1,0,0), up (0,1,0), forward (0,0,-1).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmCameraBasis {
+    pub right: RmVec3,
+    pub up: RmVec3,
+    pub forward: RmVec3,
+}
+
 pub enum RmScene {}
 pub enum RmCtx {}
 
@@ -152,6 +162,12 @@ extern "C" {
     fn rm_scene_upload(ctx: *mut RmCtx, desc: *const RmSceneDesc) -> c_int;
     fn rm_scene_uploads(ctx: *mut RmCtx, calls: *mut u64, copies: *mut u64) -> c_int;
     fn rm_camera_update(ctx: *mut RmCtx, camera: RmVec3) -> c_int;
+    fn rm_camera_orient(ctx: *mut RmCtx, basis: *const RmCameraBasis) -> c_int;
+    fn rm_camera_look_at(ctx: *mut RmCtx, eye: RmVec3, target: RmVec3, up_hint: RmVec3) -> c_int;
+    fn rm_camera_get(ctx: *mut RmCtx, position: *mut RmVec3, basis: *mut RmCameraBasis, oriented: *mut c_int) -> c_int;
+    fn rm_camera_basis_look_at(eye: RmVec3, target: RmVec3, up_hint: RmVec3, out: *mut RmCameraBasis) -> c_int;
+    fn rm_camera_basis_turn(input: *const RmCameraBasis, yaw: f64, pitch: f64, roll: f64, out: *mut RmCameraBasis) -> c_int;
+    fn rm_camera_basis_check(basis: *const RmCameraBasis) -> c_int;
     fn rm_render(ctx: *mut RmCtx, params: *const RmParams, host_rgb: *mut f64, timing: *mut RmTiming) -> c_int;
     fn rm_render_rows(ctx: *mut RmCtx, params: *const RmParams, rows: *const *mut f64, timing: *mut RmTiming) -> c_int;
     fn rm_render_display(ctx: *mut RmCtx, params: *const RmParams, host_rgb8: *mut u8, timing: *mut RmTiming) -> c_int;
@@ -387,6 +403,36 @@ impl Gpu {
         } else {
             None
         }
+    }
+
+    /// The view direction of every later `render`, `render_display` and `pick`; None: the reference's fixed view
+    /// (down -z, +y up).  It stays with the context: uploads -- every render makes one -- leave it alone.
+    pub fn orient(&mut self, basis: Option<&RmCameraBasis>) {
+        let p = match basis {
+            Some(b) => b as *const RmCameraBasis,
+            None => ::std::ptr::null(),
+        };
+        check(unsafe { rm_camera_orient(self.ctx, p) }, self.ctx);
+    }
+
+    /// Turns the camera that stands at `eye` (the caller's `scene.camera`: the position travels with the scene)
+    /// towards `target`; returns the basis, for `turn` to go on from.
+    pub fn look_at(&mut self, eye: Vec3f, target: Vec3f, up: Vec3f) -> RmCameraBasis {
+        let mut b: RmCameraBasis = unsafe { ::std::mem::zeroed() };
+        check(unsafe { rm_camera_basis_look_at(eye.into(), target.into(), up.into(), &mut b) }, ::std::ptr::null());
+        self.orient(Some(&b));
+        b
+    }
+
+    /// Turns the view by yaw / pitch / roll (radians; positive yaw turns left, positive pitch looks up) from what the
+    /// context holds: the two turn buttons of INTEGRATION.md.
+    pub fn turn(&mut self, yaw: f64, pitch: f64, roll: f64) -> RmCameraBasis {
+        let mut b: RmCameraBasis = unsafe { ::std::mem::zeroed() };
+        check(unsafe { rm_camera_get(self.ctx, ::std::ptr::null_mut(), &mut b, ::std::ptr::null_mut()) }, self.ctx);
+        let mut out = b;
+        check(unsafe { rm_camera_basis_turn(&b, yaw, pitch, roll, &mut out) }, ::std::ptr::null());
+        self.orient(Some(&out));
+        out
     }
 
     /// The f64 rows of the frame the last render left on the device, into `frame.buffer`.

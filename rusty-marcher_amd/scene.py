@@ -65,6 +65,19 @@ class Scene:
         self.shapes = []
         self.camera = Vec3f.zero()
         self._prebuilt = None   # SceneHandle built by the library (create_default / open_obj)
+        # The oriented camera: None is the reference's fixed view (down -z, +y up); else an rm_camera_basis that
+        # Renderer.render / Renderer.pick hand to the context on every call (not part of the uploaded scene).
+        self.basis = None
+
+    def look_at(self, target, up=(0., 1., 0.)):
+        """Turns the camera, where it stands, towards `target`."""
+        from . import backend
+        self.basis = backend.basis_look_at(self.camera, target, up)
+
+    def turn(self, yaw=0., pitch=0., roll=0.):
+        """Turns the camera about its own up, right, forward (radians; positive yaw turns left, positive pitch looks up)."""
+        from . import backend
+        self.basis = backend.basis_turn(self.basis if self.basis is not None else backend.FIXED_VIEW, yaw, pitch, roll)
 
     @staticmethod
     def new():
