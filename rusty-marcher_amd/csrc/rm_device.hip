@@ -157,6 +157,10 @@ struct rm_ctx {
     bool integer_exponents = false;   // every material's specular_exponent is a small non-negative integer
     const rm_knobs knobs = rm_knobs_from_env();   // A/B knobs and test hooks: the environment as rm_init found it
     double occ_camera_limit = 0.;     // the resident image's: cameras farther out (L1 norm) render without its masks
+    // checked numerics (rm_trace.inc RM_CHECKED): the resident image's verdict, the last render launch's, and the tiles the
+    // context's launches rendered again because a lane's guard fired (device word, counted up by the kernels)
+    bool scene_exact_only = false, last_launch_exact_only = false;
+    uint32_t *d_redo = nullptr;
     std::vector<rm_feedback> feedback;
     uint64_t feedback_clock = 0, scene_epoch = 0;
     std::vector<rm_tile_lists> tile_lists;
@@ -331,6 +335,8 @@ rm_status rm_init(int device_ordinal, rm_ctx **out) {
     if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreate(&ctx->ev1)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipMalloc(&ctx->d_max, sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = hipMalloc(&ctx->d_redo, sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = hipMemset(ctx->d_redo, 0, sizeof(uint32_t))) != hipSuccess) return bail("hipMemset", e);
     *out = ctx;
     return RM_OK;
 }
@@ -368,6 +374,7 @@ void rm_destroy(rm_ctx *ctx) {
         if (ctx->d_pid_map) (void)hipFree(ctx->d_pid_map);
         if (ctx->d_query) (void)hipFree(ctx->d_query);
         if (ctx->d_max) (void)hipFree(ctx->d_max);
+        if (ctx->d_redo) (void)hipFree(ctx->d_redo);
         if (ctx->d_rgb8) (void)hipFree(ctx->d_rgb8);
         if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
         if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -409,7 +416,35 @@ struct rm_image {
     std::vector<double> blob;
     std::vector<uint32_t> pid_map;
     double occ_camera_limit = 0.;      // |camera|_1 beyond which the render does not use the occluder masks
+    bool exact_only = false;           // outside what the checked numerics are proven for (scene_exact_only)
 };
+
+// Checked numerics (rm_trace.inc RM_CHECKED; the bounds: rm_plan.hpp): a scene is rendered by the exact code alone when any
+// coordinate, radius or light word of its description is not finite or beyond RM_CHECKED_COORD_MAX in magnitude --
+// within it no intermediate of a sphere test overflows into a NaN whose payload the two square-root sequences might carry
+// differently -- or a sphere's radius_square lies outside the range in which the discriminant's root needs no scaling.
+// (The camera is the launch's: rm_camera_update can set it to anything, and the plan looks at the one a launch carries.)
+static bool scene_exact_only(const rm_scene_desc *d) {
+    bool ok = true;
+    auto v3 = [&](const rm_vec3 &v) { ok = ok && rm_checked_coord_ok(v.x) && rm_checked_coord_ok(v.y) && rm_checked_coord_ok(v.z); };
+    for (uint32_t i = 0; i < d->n_spheres; i++) {
+        v3(d->spheres[i].center);
+        const double r2 = d->spheres[i].radius_square;
+        ok = ok && r2 >= RM_CHECKED_R2_MIN && r2 <= RM_CHECKED_R2_MAX && rm_checked_coord_ok(r2);
+    }
+    for (uint32_t i = 0; i < d->n_polygons; i++) { v3(d->polygons[i].plane_normal); v3(d->polygons[i].plane_point); }
+    for (uint32_t i = 0; i < d->n_polygon_vertices; i++) v3(d->polygon_vertices[i]);
+    for (uint32_t i = 0; i < d->n_triangles; i++) {
+        const rm_triangle &t = d->triangles[i];
+        v3(t.normal); v3(t.center);
+        for (const rm_vec3 &v : t.vertices) v3(v);
+    }
+    for (uint32_t i = 0; i < d->n_lights; i++) {
+        v3(d->lights[i].position); v3(d->lights[i].color);
+        ok = ok && rm_checked_coord_ok(d->lights[i].intensity);
+    }
+    return !ok;
+}
 static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, bool shadow_masks, rm_image &img) {
     // ---- regroup Scene.shapes by kind, remembering list order for ties ----
     std::vector<uint32_t> sphere_src, polygon_src, tri_src;   // indices into desc arrays
@@ -544,7 +579,7 @@ static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, 
         m[4] = r.specular; m[5] = r.specular_exponent;
         m[6] = r.reflection; m[7] = r.refractive_index;
         m[8] = r.is_glass_like ? 1. : 0.;
-        m[9] = 0.;
+        m[9] = 1. / r.refractive_index;   // reflect_child / refract_child read it: one IEEE division here, the bits of the device's per ray
     };
     // Bounding sphere of everything of primitive `pid` a ray can hit, for the bundle cull
     // (rm_trace.inc): inflated by 1e-7 relative + 1e-9 of the coordinates' magnitude -- far
@@ -716,6 +751,7 @@ static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, 
             img.occ_camera_limit = std::isfinite(size) ? 1e6 * (1. + size) : 0.;
         }
     }
+    img.exact_only = scene_exact_only(d);
     return RM_OK;
 }
 
@@ -799,6 +835,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     }
     ctx->H = H;
     ctx->occ_camera_limit = img.occ_camera_limit;
+    ctx->scene_exact_only = img.exact_only;
     ctx->camera = d->camera;
     ctx->have_scene = true;
     ctx->scene_epoch++;                                      // (the feedback of another scene's frames is void)
@@ -833,6 +870,32 @@ extern "C" rm_status rmi_shadow_masks(const rm_scene_desc *d, uint64_t *occ, uin
         std::memcpy(occ, &img.blob[H.off_occ], (size_t)n * H.n_lights * sizeof(uint64_t));
         for (uint32_t q = 0; q < n; q++) shape_of[q] = img.pid_map[2u * q];
     }
+    return RM_OK;
+}
+
+// Test hooks, not part of the ABI (tests/test_checked_numerics.py, tests/test_gpu_checked_numerics.py).
+// What the upload of `d` decides and builds for the checked numerics: dims[0] = pids, dims[1] = 1 where the scene is exact
+// only; then, when cap >= 10 x pids, the material words of every pid.  Host work only: no device is needed.
+extern "C" rm_status rmi_upload_numerics(const rm_scene_desc *d, double *materials, uint32_t cap, uint32_t *dims) {
+    if (!d || !dims) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rmi_upload_numerics: NULL argument");
+    rm_image img;
+    if (rm_status st = build_image(nullptr, d, true, true, img)) return st;
+    const uint32_t n = img.H.n_spheres + img.H.n_polygons + img.H.n_triangles;
+    dims[0] = n; dims[1] = img.exact_only ? 1u : 0u;
+    if (materials && (uint64_t)n * RM_MATERIAL_WORDS <= cap)
+        std::memcpy(materials, &img.blob[img.H.off_materials], (size_t)n * RM_MATERIAL_WORDS * sizeof(double));
+    return RM_OK;
+}
+// The tiles the context's render launches have rendered again so far because a lane's guard fired (waits for the device),
+// and whether the last render launch was exact only.
+extern "C" rm_status rmi_redone_tiles(rm_ctx *ctx, uint64_t *redone, uint32_t *last_exact_only) {
+    if (!ctx || !redone) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rmi_redone_tiles: NULL argument");
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, hipDeviceSynchronize());
+    uint32_t n = 0;
+    RM_HIP(ctx, hipMemcpy(&n, ctx->d_redo, sizeof n, hipMemcpyDeviceToHost));
+    *redone = n;
+    if (last_exact_only) *last_exact_only = ctx->last_launch_exact_only ? 1u : 0u;
     return RM_OK;
 }
 
@@ -1002,7 +1065,7 @@ static rm_status void_frame_check(rm_ctx *ctx, const char *who) {
 
 static rm_plan_scene plan_scene_of(const rm_ctx *ctx) {
     return rm_plan_scene{&ctx->H, ctx->scene_epoch, ctx->occ_camera_limit, ctx->integer_exponents, ctx->oriented,
-                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount};
+                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, ctx->scene_exact_only};
 }
 
 static rm_status no_kernel(rm_ctx *ctx) { return ctx_fail(ctx, RM_ERR_INVALID_ARG, "render: no kernel for this scene / depth combination"); }
@@ -1142,6 +1205,7 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
     a.bp_x = ctx->d_backproject;
     a.bp_y = ctx->d_backproject + p->frame_width;
     a.frame8 = d_frame8;
+    a.redo_count = ctx->d_redo;
 
     if (P.cls_fn) {
         P.cls_args.tile_mask = tl->mask();
@@ -1162,6 +1226,7 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
     ctx->last_launch_stream = stream;
     ctx->last_launch_grid = P.grid;
     ctx->last_launch_tail = a.tail_patches;
+    ctx->last_launch_exact_only = P.exact_only;
     if (ctx->knobs.debug_tail && P.ordered)
         if (rm_status dst = dump_order(ctx, P, stream)) return dst;
 #if defined(RM_EXP_STAMPS) || defined(RM_EXP_PHASES)

@@ -24,7 +24,7 @@ const char *rm_get_host_error();
 //                                       product, i.e. only x and y of the vertices)
 //   triangles 12 words each: nx ny nz  cx cy cz  v0x v0y v1x v1y v2x v2y
 //   materials 10 words per pid: diffusion dcx dcy dcz specular exponent
-//                               reflection refractive_index is_glass 0
+//                               reflection refractive_index is_glass 1/refractive_index
 //   lights    8 words each : px py pz  cx cy cz  intensity 0
 //   keys      1 u32 per pid (2 per word): position in Scene.shapes order, used
 //                               only to break exact distance ties (shapes.rs:130)

@@ -184,6 +184,12 @@ struct KernelArgs {
     // normalized((bp_x[x] * right + bp_y[y] * up) + forward) from the camera.  The fixed view's kernels, whose
     // direction is (bp_x[x], bp_y[y], -1), never look at it.  (Last in the block: nothing in front of it moves.)
     double cam_rx, cam_ry, cam_rz, cam_ux, cam_uy, cam_uz, cam_fx, cam_fy, cam_fz;
+    // Checked numerics (the strict plain-walk kernels, rm_trace.inc RM_CHECKED): exact_only != 0 -- every tile of the launch
+    // is rendered by the exact twin (a scene or a camera outside what the range-free sequences are proven for, or
+    // RM_CHECKED_NUMERICS=0); redo_count -- the context's count of tiles rendered again because a lane's guard fired.
+    uint32_t exact_only;
+    uint32_t _pad_checked;
+    uint32_t *redo_count;
 };
 
 // What the classification launch gets besides the render launch's own arguments.

@@ -89,6 +89,7 @@ const knob k_knobs[] = {
     {"RM_CULL_COS", &rm_knobs::cull_cos, CULL_COS},
     {"RM_CULL_MIN", &rm_knobs::cull_min_prims, STRTOUL},
     {"RM_CULL_EDGES", &rm_knobs::cull_edges, NOT_0},
+    {"RM_CHECKED_NUMERICS", &rm_knobs::checked_numerics, NOT_0},
     {"RM_DEBUG_TAIL", &rm_knobs::debug_tail, IS_SET},
 };
 
@@ -212,6 +213,15 @@ static void point(rm_launch_plan &P, T *KernelArgs::*field, rm_buf buf, size_t b
     P.refs[P.n_refs++] = rm_arg_ref{(uint16_t)(at - reinterpret_cast<const char *>(&P.args)), buf, (uint32_t)bytes};
 }
 
+bool rm_camera_exact_only(const rm_plan_scene &sc) {
+    bool ok = rm_checked_coord_ok(sc.camera.x) && rm_checked_coord_ok(sc.camera.y) && rm_checked_coord_ok(sc.camera.z);
+    if (sc.oriented && sc.basis) {
+        const rm_camera_basis &b = *sc.basis;
+        for (const rm_vec3 &v : {b.right, b.up, b.forward}) ok = ok && rm_checked_coord_ok(v.x) && rm_checked_coord_ok(v.y) && rm_checked_coord_ok(v.z);
+    }
+    return !ok;
+}
+
 bool plan_launch(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p, const rm_band &band, const rm_stream_state &before,
                  uint32_t order_cap, const rm_feedback_state &fb, unsigned long long hint, rm_launch_plan *out) {
     rm_launch_plan &P = *out;
@@ -228,6 +238,9 @@ bool plan_launch(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p
     // far enough out to round its hit points coarser than that renders without them)
     if (!(std::fabs(sc.camera.x) + std::fabs(sc.camera.y) + std::fabs(sc.camera.z) <= sc.occ_camera_limit)) a.H.off_occ = 0u;
     a.bg_x = p.background.x; a.bg_y = p.background.y; a.bg_z = p.background.z;
+    // checked numerics: the scene's verdict from its upload, the camera's here, the knob's on top (kernels without them do not look)
+    P.exact_only = !kn.checked_numerics || sc.exact_only || rm_camera_exact_only(sc);
+    a.exact_only = P.exact_only ? 1u : 0u;
     a.frame_width = p.frame_width;
     a.patch_row_begin = band.begin;
     a.patch_row_stride = band.stride;
@@ -606,5 +619,27 @@ extern "C" rm_status rmi_plan_launches(const rmi_plan_case *cases, uint32_t n, r
         if (P.ordered) order_cap = P.order_cap;
         if (P.feedback) fb = P.feedback_after;
     }
+    return RM_OK;
+}
+
+// Test hook, not part of the ABI (tests/test_checked_numerics.py): whether a launch with this camera (and this basis, where
+// `oriented`) of a scene whose upload said `scene_exact_only` would be exact only, with the knobs as the environment has them
+// now -- the decision plan_launch puts into its plan.  No device is needed.
+extern "C" rm_status rmi_plan_exact_only(const rm_vec3 *camera, const rm_camera_basis *basis, uint32_t oriented, uint32_t scene_exact_only, uint32_t *out) {
+    if (!camera || !basis || !out) { rm_set_host_error("rmi_plan_exact_only: NULL argument"); return RM_ERR_INVALID_ARG; }
+    const rm_knobs kn = rm_knobs_from_env();
+    rm_dev_header H{};
+    H.n_spheres = 1; H.total_words = 128;
+    const rm_plan_scene sc{&H, 1u, 0., true, oriented != 0, *camera, basis, 256u, scene_exact_only != 0};
+    rm_params p{};
+    p.half_fov = 0.75; p.height = 64.; p.width = 64.; p.ratio = 1.;
+    p.frame_width = 64; p.frame_height = 64; p.max_depth = 3;
+    rm_band band;
+    rm_launch_plan P;
+    if (!rm_band_of(p, &band) || !plan_launch(kn, sc, p, band, rm_stream_state{}, 0u, rm_feedback_state{}, 0ull, &P)) {
+        rm_set_host_error("rmi_plan_exact_only: no plan");
+        return RM_ERR_INVALID_ARG;
+    }
+    *out = (P.exact_only ? 1u : 0u) | (P.args.exact_only ? 2u : 0u);
     return RM_OK;
 }

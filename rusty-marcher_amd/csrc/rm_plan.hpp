@@ -82,6 +82,9 @@ struct rm_knobs {
     int test_stall_order = 0;            // RM_TEST_STALL_ORDER (test hook) = 1: the launch's order is never laid out (the frame is void); = 2: its classifying workgroups never say they have arrived (the order of last resort)
     int sky_tail_force = -1;             // RM_SKY_TAIL_FORCE=n (test hook): the last n patches of the order are taken for sky, whatever the hint says
     int patch_order_mode = -1;           // RM_PATCH_ORDER=0 never, 1 whenever possible; unset: launches of RM_CLASSIFY_MIN_TILES tiles and more
+    // RM_CHECKED_NUMERICS=0: every launch of the strict plain-walk kernels is exact only -- the compiler's own square roots and
+    // divisions throughout (the A/B switch, and what the bit-equality tests compare with)
+    bool checked_numerics = true;
     bool debug_tail = false;             // RM_DEBUG_TAIL (set at all): every ordered launch is waited for and its order dumped to stderr; no launch is frozen
 };
 rm_knobs rm_knobs_from_env();
@@ -105,7 +108,17 @@ struct rm_plan_scene {
     rm_vec3 camera;
     const rm_camera_basis *basis;     // (the fixed view's own while the oriented state is off)
     uint32_t n_cus;
+    bool exact_only = false;          // the resident scene is outside what the checked numerics are proven for (rm_device.hip scene_exact_only)
 };
+
+// Checked numerics (rm_trace.inc RM_CHECKED): a coordinate, radius, camera or light word is inside the proven range when it is
+// finite and at most this in magnitude -- no intermediate of a sphere test can then overflow -- ...
+static constexpr double RM_CHECKED_COORD_MAX = 0x1p+200;
+// ... and a sphere's radius_square when the discriminant's root needs no scaling: a non-zero r^2 - d^2 is at least r^2 2^-54
+static constexpr double RM_CHECKED_R2_MIN = 0x1p-600, RM_CHECKED_R2_MAX = 0x1p+600;
+inline bool rm_checked_coord_ok(double v) { return v >= -RM_CHECKED_COORD_MAX && v <= RM_CHECKED_COORD_MAX; }   // (NaN: no)
+// The camera a launch carries (rm_camera_update can set it to anything), and the basis where the launch is oriented.
+bool rm_camera_exact_only(const rm_plan_scene &sc);
 
 // How the 64-pixel tiles of a band are handed to waves (see rm_render_kernel.hpp): `waves`
 // waves per workgroup, `per_wave` tiles per wave.  Measured at 1080p on the demo scene
@@ -223,6 +236,7 @@ struct rm_launch_plan {
     const void *cls_fn = nullptr;     // ... by a launch of its own in front (NULL: at the head of the render launch, or not at all)
     uint32_t cls_grid = 0;
     rmdev::ClassifyArgs cls_args{};   // (tile_mask: the launcher's)
+    bool exact_only = false;          // checked numerics: the launch renders every tile with the exact twin (args.exact_only says so to the kernel)
     bool ordered = false;             // the launch has a dispatch order (the order block and the hint must exist)
     bool frozen = false;              // ... and takes everything from its predecessor (order_freeze)
     // device work in front of the launch, in this order

@@ -135,6 +135,28 @@ __device__ __forceinline__ void tile_origin(const KernelArgs &a, uint32_t tile, 
 #endif
 #define RM_FAST 0
 #pragma clang fp contract(off)
+// The plain-walk kernels (group 0 of rm_kernels.hip) render their tiles with checked range-free numerics: the device functions
+// and the tile body once more, RM_CHECKED=1, in a namespace of their own (the kernels, and so their names, stay the strict
+// namespace's, whose own tile body is the exact twin).  RM_CHECKED_NUMERICS_OFF: a build without.
+#if defined(RM_KERNEL_GROUP) && RM_KERNEL_GROUP == 0 && !defined(RM_CHECKED_NUMERICS_OFF)
+#if RM_KERNEL_ORIENTED
+#define RM_CHECKED_NS rmdev_strict_o_checked
+#else
+#define RM_CHECKED_NS rmdev_strict_checked
+#endif
+#undef RM_FLAVOR_NS
+#define RM_FLAVOR_NS RM_CHECKED_NS
+#define RM_CHECKED 1
+#include "rm_trace.inc"
+#include "rm_render_kernel.inc"
+#undef RM_CHECKED
+#undef RM_FLAVOR_NS
+#if RM_KERNEL_ORIENTED
+#define RM_FLAVOR_NS rmdev_strict_o
+#else
+#define RM_FLAVOR_NS rmdev_strict
+#endif
+#endif
 #include "rm_trace.inc"
 #include "rm_classify.inc"
 #include "rm_render_kernel.inc"

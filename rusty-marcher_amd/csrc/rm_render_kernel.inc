@@ -25,14 +25,19 @@ using namespace rmdev;
 // stack is empty, so it always holds the shallowest parked ray of the lane's current tree),
 // deeper levels in scratch.  A lane works depth-first on ONE tree at a time, so its parked
 // rays have distinct depths: at most max_depth - 1 of them (STACK = 4 / 8 / 16 / 32).
+// Returns whether the tile has to be rendered again by the exact code -- nothing of it has been stored then (RM_CHECKED, the
+// range-free numerics of rm_trace.inc: some lane met an operand outside their range); never, otherwise.
 template <int STACK, int POW, bool BVH, bool CULL, bool EDGES, bool PREFETCHED>
-__device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArgs &a, uint32_t tx0, uint32_t ty0,
+__device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArgs &a, uint32_t tx0, uint32_t ty0,
                                             uint32_t tyf, uint32_t ty8, double bp_x, double bp_y, double *wl,
                                             double *__restrict__ frame_in, unsigned long long *stats, bool have_mask,
                                             unsigned long long first_mask, const char *kargs_of_kernel) {
     const uint32_t lane = threadIdx.x & 63u;
     const V3 bg = mk(own_sgpr(a.bg_x), own_sgpr(a.bg_y), own_sgpr(a.bg_z));
     const uint32_t max_depth = own_sgpr(a.max_depth);
+#if RM_CHECKED
+    bool sus = false;                                         // per lane: an operand outside the checked sequences' range
+#endif
 
     // the wave's LDS block (rm_render_kernel.hpp): level 0 of the ray stacks, the pixel sums
     // (which the store phase reads as they lie: [pixel][channel] is the tile's row-major
@@ -56,9 +61,9 @@ __device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArg
     // products and two sums in this order (the strict flavour rounds each once; the fast one may contract).  The nine words are
     // kernel arguments: scalar registers, one scalar operand to a vector instruction.
     const double bx = PREFETCHED ? bp_x : a.bp_x[tx0 + (lane % TILE_W)], by = PREFETCHED ? bp_y : a.bp_y[ty0 + (lane / TILE_W)];
-    V3 dir = normalized(mk((bx * a.cam_rx + by * a.cam_ux) + a.cam_fx, (bx * a.cam_ry + by * a.cam_uy) + a.cam_fy, (bx * a.cam_rz + by * a.cam_uz) + a.cam_fz));
+    V3 dir = RM_NORMALIZED(mk((bx * a.cam_rx + by * a.cam_ux) + a.cam_fx, (bx * a.cam_ry + by * a.cam_uy) + a.cam_fy, (bx * a.cam_rz + by * a.cam_uz) + a.cam_fz), true);
 #else
-    V3 dir = normalized(PREFETCHED ? mk(bp_x, bp_y, -1.) : mk(a.bp_x[tx0 + (lane % TILE_W)], a.bp_y[ty0 + (lane / TILE_W)], -1.));
+    V3 dir = RM_NORMALIZED(PREFETCHED ? mk(bp_x, bp_y, -1.) : mk(a.bp_x[tx0 + (lane % TILE_W)], a.bp_y[ty0 + (lane / TILE_W)], -1.), true);
 #endif
     V3 orig = mk(a.cam_x, a.cam_y, a.cam_z);
     double weight = 1.;
@@ -124,17 +129,17 @@ __device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArg
             double w_cap = 0.;
             if (DIV && !got && depth > 1u) acc = acc + scaled(bg, weight);
             if (where<DIV>(got)) {
-                const Surface s = surface_at<DIV>(sc, orig, dir, h, got);
+                const Surface s = surface_at<DIV>(sc, orig, dir, h, got RM_SUS_ARG);
                 const unsigned long long t_sd = RM_PHASE_T();
-                L = pick(got, bg + shade_direct<POW, BVH, CULL, EDGES>(sc, neg(dir), s, got, h.pid), bg);
+                L = pick(got, bg + shade_direct<POW, BVH, CULL, EDGES>(sc, neg(dir), s, got, h.pid RM_SUS_ARG), bg);
                 RM_PHASE_ADD(sc, 3, t_sd);
                 if (DIV) acc = acc + scaled(L, weight);
                 const bool glass = got & (s.mat[8] != 0.);     // is_glass_like, renderer.rs:277
                 if (where<DIV>(glass)) {
-                    const double reflection = s.mat[6], ri = s.mat[7];
+                    const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];   // (1 / ri: the upload's division, rm_device.hip put_material)
                     V3 ro, rd, to, td;
-                    const bool has_r = glass & reflect_child<DIV>(dir, s, ri, ro, rd);   // renderer.rs:195-222
-                    const bool has_t = glass & refract_child(dir, s, ri, to, td);   // renderer.rs:225-252
+                    const bool has_r = glass & reflect_child<DIV>(dir, s, ri, inv_ri, ro, rd);   // renderer.rs:195-222
+                    const bool has_t = glass & refract_child(dir, s, ri, inv_ri, glass, to, td RM_SUS_ARG);   // renderer.rs:225-252
                     const double wr = weight * reflection, wt = weight * (1. - reflection);
                     // a child beyond the cap returns the background (renderer.rs:262-264)
                     const bool capped = depth + 1u > max_depth;
@@ -235,6 +240,9 @@ __device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArg
         }
     }
     __builtin_amdgcn_wave_barrier();
+#if RM_CHECKED
+    if (__any(sus)) return true;                               // (wave-uniform; nothing of the tile has left the wave)
+#endif
     if (handed) acc = acc + mk(sum[lane * 3 + 0], sum[lane * 3 + 1], sum[lane * 3 + 2]);
     sum[lane * 3 + 0] = acc.x;
     sum[lane * 3 + 1] = acc.y;
@@ -292,7 +300,18 @@ __device__ __forceinline__ void render_tile(const SceneView &sc, const KernelArg
 #else
     (void)stats;
 #endif
+    return false;
 }
+#undef RM_SUS_PARAM
+#undef RM_SUS_ARG
+#undef RM_NORMALIZED
+#undef RM_SQRT_DISCRIMINANT
+#if RM_CHECKED
+#undef RM_CHECKED_X_MIN
+#undef RM_CHECKED_X_MAX
+#endif
+
+#if !RM_CHECKED   // (the checked copy is the tile body alone: the kernels are the strict namespace's)
 
 // What a patch is sorted by: its LONGEST tile.  A launch ends with the tiles that were started late and run long; sorted by
 // the sum of its tiles' times a patch of a few 30-us tiles among cheap ones went out in the middle of the launch, and the
@@ -362,8 +381,10 @@ __device__ __forceinline__ uint32_t order_entry(const KernelArgs &a, uint32_t k,
 // after the other -- correct, and slow.  A function of its own, not inlined, that takes nothing but the patch: code that no
 // wave of a settled render loop runs must not shape the registers of the others (the kernel's arguments it reads where
 // they lie, in the kernel's argument segment: scene pointer, KernelArgs, frame pointer).
+// (... and the exact twin of the kernels whose tile body has the checked numerics: `n` = 1, the tile a wave has to render again,
+// or renders in the first place where the launch is exact only; `staged`: the wave's LDS block holds the scene already)
 template <int STACK, int POW, bool STAGED, bool BVH, bool CULL, bool EDGES>
-__device__ __attribute__((noinline)) void render_patch_alone(const char *kargs_of_kernel, uint32_t tile0) {
+__device__ __attribute__((noinline)) void render_patch_alone(const char *kargs_of_kernel, uint32_t tile0, uint32_t n = 16u, bool staged = false) {
     // (the pointer arrives in vector registers; it is the same for every lane and points into the constant address
     // space: said so, the argument block is read with scalar loads as in the kernel)
     const unsigned long long kv = (unsigned long long)kargs_of_kernel;
@@ -373,7 +394,7 @@ __device__ __attribute__((noinline)) void render_patch_alone(const char *kargs_o
     const double *__restrict__ scene_blob = *reinterpret_cast<const double *const *>(kargs);
     const KernelArgs &a = *reinterpret_cast<const KernelArgs *>(kargs + sizeof(const double *));
     double *__restrict__ frame = *reinterpret_cast<double *const *>(kargs + sizeof(const double *) + sizeof(KernelArgs));
-    for (uint32_t t = 0; t < 16u; t++) {
+    for (uint32_t t = 0; t < n; t++) {
         const uint32_t tile = tile0 + t;
         uint32_t tx0, ty0, tyf, ty8;
         tile_origin(a, tile, tx0, ty0, tyf, ty8);
@@ -383,7 +404,7 @@ __device__ __attribute__((noinline)) void render_patch_alone(const char *kargs_o
             const unsigned long long w = uniform_u64(__hip_atomic_load(const_cast<unsigned long long *>(a.tile_mask) + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             if ((uint32_t)(w >> 56) == a.mask_tag) { first_mask = w & 0x00FFFFFFFFFFFFFFull; have_mask = true; }
         }
-        if (STAGED) stage_scene(scene_blob, a.H);
+        if (STAGED && !staged) stage_scene(scene_blob, a.H);
         double *wl = rm_lds + (STAGED ? a.H.total_words : 0u);
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         SceneView sc;
@@ -398,7 +419,7 @@ __device__ __attribute__((noinline)) void render_patch_alone(const char *kargs_o
         uint32_t cull_counts[4] = {0u, 0u, 0u, 0u};
         sc.cnt = cull_counts;
 #endif
-        render_tile<STACK, POW, BVH, CULL, EDGES, false>(sc, a, tx0, ty0, tyf, ty8, 0., 0., wl, frame, nullptr, have_mask & (a.mask_exact != 0u), first_mask, kargs_of_kernel);
+        (void)render_tile<STACK, POW, BVH, CULL, EDGES, false>(sc, a, tx0, ty0, tyf, ty8, 0., 0., wl, frame, nullptr, have_mask & (a.mask_exact != 0u), first_mask, kargs_of_kernel);
         if (a.patch_cost && (threadIdx.x & 63u) == 0u) {
             const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - t0;
             RM_PATCH_COST_OP(a.patch_cost + (tile >> 4), dt < 0x00FFFFFFull ? (uint32_t)dt : 0x00FFFFFFu);
@@ -818,40 +839,59 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(POW 
     double *wl = rm_lds + (STAGED ? a.H.total_words : cull_words);
     // (patch order: the wave's start time waits in its LDS block, not in a register that would be live through the tile)
     if (ORDER && (threadIdx.x & 63u) == 0u) reinterpret_cast<uint32_t *>(wl + RM_WAVE_T0_WORDS)[0] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    SceneView sc;
-    if (STAGED) sc.S = rm_lds; else sc.S = scene_blob;
-    sc.G = scene_blob;
-    sc.cull_bounds = cull_words ? rm_lds : scene_blob + a.H.off_bounds;
-    sc.cull_planar = cull_words ? rm_lds + 4u * (a.H.n_spheres + a.H.n_polygons + a.H.n_triangles) : scene_blob + a.H.off_planar;
-    sc.bstack = reinterpret_cast<uint32_t *>(wl + RM_WAVE_BVH_STACK_WORDS);
-    sc.cull_cos = own_sgpr(a.cull_cos);
-#ifdef RM_EXP_STAMPS
-    sc.cnt = cull_counts;
-#endif
-    // every header field in a scalar register of its own: the kernel arguments arrive as
-    // 16-dword tuples, and a tuple is spilled and reloaded whole (16 lane reads to get at
-    // the background colour, four times per ray)
-    sc.H.n_spheres = own_sgpr(a.H.n_spheres);         sc.H.n_polygons = own_sgpr(a.H.n_polygons);
-    sc.H.n_triangles = own_sgpr(a.H.n_triangles);     sc.H.n_lights = own_sgpr(a.H.n_lights);
-    sc.H.off_spheres = own_sgpr(a.H.off_spheres);     sc.H.off_polygons = own_sgpr(a.H.off_polygons);
-    sc.H.off_pverts = own_sgpr(a.H.off_pverts);       sc.H.off_triangles = own_sgpr(a.H.off_triangles);
-    sc.H.off_materials = own_sgpr(a.H.off_materials); sc.H.off_lights = own_sgpr(a.H.off_lights);
-    sc.H.off_keys = own_sgpr(a.H.off_keys);           sc.H.total_words = a.H.total_words;
-    sc.H.list_ordered = own_sgpr(a.H.list_ordered);   sc.H.off_bvh_spheres = own_sgpr(a.H.off_bvh_spheres);
-    sc.H.off_bvh_triangles = own_sgpr(a.H.off_bvh_triangles); sc.H.off_bounds = own_sgpr(a.H.off_bounds);
-    sc.H.off_planar = own_sgpr(a.H.off_planar);       sc.H.off_groups = own_sgpr(a.H.off_groups);
-    sc.H.off_occ = own_sgpr(a.H.off_occ);
-    sc.H.shadow_rho = own_sgpr(a.H.shadow_rho);
-
-    const unsigned long long fb_t0 = feedback ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#if defined(RM_EXP_STAMPS) && defined(RM_EXP_PHASES)
-    cull_counts[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_start);
-#endif
-#ifdef RM_EXP_STAMPS
-    render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, &tile_stats, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+    // The strict plain-walk kernels render the tile with the checked numerics (RM_CHECKED_NS: this source's device functions
+    // compiled once more, rm_render_kernel.hpp) and keep this namespace's tile body, behind render_patch_alone, as the exact
+    // twin: a launch that is exact only (KernelArgs::exact_only) enters it at once, a tile some lane of which met an operand
+    // outside the checked range is rendered again by it -- and only then stored.
+#ifdef RM_CHECKED_NS
+    constexpr bool CHECKED = STAGED && !BVH && !CULL;
+    namespace tile_ns = RM_CHECKED_NS;
 #else
-    render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, nullptr, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+    constexpr bool CHECKED = false;
+    namespace tile_ns = RM_FLAVOR_NS;
 #endif
+    const unsigned long long fb_t0 = feedback ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    bool exact = CHECKED && a.exact_only != 0u;                     // wave-uniform
+    if (!exact) {
+        tile_ns::SceneView sc;
+        if (STAGED) sc.S = rm_lds; else sc.S = scene_blob;
+        sc.G = scene_blob;
+        sc.cull_bounds = cull_words ? rm_lds : scene_blob + a.H.off_bounds;
+        sc.cull_planar = cull_words ? rm_lds + 4u * (a.H.n_spheres + a.H.n_polygons + a.H.n_triangles) : scene_blob + a.H.off_planar;
+        sc.bstack = reinterpret_cast<uint32_t *>(wl + RM_WAVE_BVH_STACK_WORDS);
+        sc.cull_cos = own_sgpr(a.cull_cos);
+#ifdef RM_EXP_STAMPS
+        sc.cnt = cull_counts;
+#endif
+        // every header field in a scalar register of its own: the kernel arguments arrive as
+        // 16-dword tuples, and a tuple is spilled and reloaded whole (16 lane reads to get at
+        // the background colour, four times per ray)
+        sc.H.n_spheres = own_sgpr(a.H.n_spheres);         sc.H.n_polygons = own_sgpr(a.H.n_polygons);
+        sc.H.n_triangles = own_sgpr(a.H.n_triangles);     sc.H.n_lights = own_sgpr(a.H.n_lights);
+        sc.H.off_spheres = own_sgpr(a.H.off_spheres);     sc.H.off_polygons = own_sgpr(a.H.off_polygons);
+        sc.H.off_pverts = own_sgpr(a.H.off_pverts);       sc.H.off_triangles = own_sgpr(a.H.off_triangles);
+        sc.H.off_materials = own_sgpr(a.H.off_materials); sc.H.off_lights = own_sgpr(a.H.off_lights);
+        sc.H.off_keys = own_sgpr(a.H.off_keys);           sc.H.total_words = a.H.total_words;
+        sc.H.list_ordered = own_sgpr(a.H.list_ordered);   sc.H.off_bvh_spheres = own_sgpr(a.H.off_bvh_spheres);
+        sc.H.off_bvh_triangles = own_sgpr(a.H.off_bvh_triangles); sc.H.off_bounds = own_sgpr(a.H.off_bounds);
+        sc.H.off_planar = own_sgpr(a.H.off_planar);       sc.H.off_groups = own_sgpr(a.H.off_groups);
+        sc.H.off_occ = own_sgpr(a.H.off_occ);
+        sc.H.shadow_rho = own_sgpr(a.H.shadow_rho);
+
+#if defined(RM_EXP_STAMPS) && defined(RM_EXP_PHASES)
+        cull_counts[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_start);
+#endif
+#ifdef RM_EXP_STAMPS
+        exact = tile_ns::render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, &tile_stats, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+#else
+        exact = tile_ns::render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, nullptr, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+#endif
+        if (CHECKED && exact) {                                          // (counted: tests and profiles ask how many, rm_device.hip rmi_redone_tiles)
+            const KernelArgs &b = *reinterpret_cast<const KernelArgs *>(reread_kernargs((const char *)__builtin_amdgcn_kernarg_segment_ptr()) + sizeof(const double *));
+            if (b.redo_count && (threadIdx.x & 63u) == 0u) atomicAdd(b.redo_count, 1u);
+        }
+    }
+    if constexpr (CHECKED) if (exact) render_patch_alone<STACK, POW, STAGED, BVH, CULL, EDGES>((const char *)__builtin_amdgcn_kernarg_segment_ptr(), tile, 1u, true);
     if (ORDER) {
         // (the kernel's arguments read afresh from its argument segment: asked of `a` they would be kept in scalar registers
         // -- spilt ones -- through the whole tile for these few lines)
@@ -897,5 +937,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(POW 
     }
     stamp();
 }
+
+#endif   // !RM_CHECKED
 
 }  // namespace RM_FLAVOR_NS

@@ -48,7 +48,81 @@ __device__ __forceinline__ V3 scaled(V3 a, double s) { return mk(a.x * s, a.y * 
 __device__ __forceinline__ V3 pick(bool c, V3 a, V3 b) { return mk(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z); }
 // geometry.rs:180-182: (x*x' + y*y') + z*z'
 __device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+#ifndef RM_CHECKED
+#define RM_CHECKED 0
+#endif
+// RM_CHECKED (rm_render_kernel.hpp: the strict plain-walk kernels' tile body): a lane's "an operand lay outside the range the
+// range-free sequences below are proven for" travels with the calls; the tile is rendered again by the exact code if any is set.
+#if RM_CHECKED
+#define RM_SUS_PARAM , bool &sus
+#define RM_SUS_ARG , sus
+#else
+#define RM_SUS_PARAM
+#define RM_SUS_ARG
+#endif
+#if RM_CHECKED
+// The compiler's own expansion of a binary64 square root (v_rsq_f64, g = x y, h = y / 2, one coupled refinement of both, two
+// residual corrections of g) without what it puts around it for x < 2^-767 -- a compare, two selects, two v_ldexp_f64 that
+// scale by 2^256 and back.  The same operations on the same values: for x >= 2^-767 bit for bit the compiler's root.
+// `h`: ~ 0.5 / sqrt(x) as the iteration leaves it.
+__device__ __forceinline__ double sqrt_unscaled(double x, double &h) {
+    const double y = __builtin_amdgcn_rsq(x);
+    const double g0 = x * y, h0 = y * 0.5;
+    const double r0 = __builtin_fma(-h0, g0, 0.5);
+    const double g1 = __builtin_fma(g0, r0, g0), h1 = __builtin_fma(h0, r0, h0);
+    const double d0 = __builtin_fma(-g1, g1, x);
+    const double g2 = __builtin_fma(d0, h1, g1);
+    const double d1 = __builtin_fma(-g2, g2, x);
+    h = h1;
+    return __builtin_fma(d1, h1, g2);
+}
+// ... with the compiler's select for 0, -0 and +inf (the root of a tangent ray's discriminant is exactly 0).  The argument is
+// r^2 - d^2 of a sphere test: not below r^2 2^-54 unless it is zero, and the upload keeps r^2 within [2^-600, 2^600]
+// (rm_device.hip scene_exact_only) -- no lane needs a guard.
+__device__ __forceinline__ double sqrt_discriminant(double x) {
+    double h;
+    const double r = sqrt_unscaled(x, h);
+    return (x == 0. || x == __builtin_inf()) ? x : r;
+}
+#define RM_SQRT_DISCRIMINANT(x) sqrt_discriminant(x)
+// The range the checked normalisation is proven for, with margin: the root needs x >= 2^-767; the division's scaling sets in
+// for divisors beyond about 2^+-768, far outside the norms 2^-300 .. 2^300 of this range.
+#define RM_CHECKED_X_MIN 0x1p-600
+#define RM_CHECKED_X_MAX 0x1p+600
+struct CheckedNorm { double norm, inv; bool outside; };
+// sqrt, then 1 / norm of the ROUNDED norm (geometry.rs:104-109): the compiler's own expansion of the division (v_rcp_f64, two
+// Newton steps, the quotient's residual correction) without what it puts around it for operands near the ends of the
+// exponent range -- two v_div_scale_f64, which leave a divisor within [2^-300, 2^300] and the dividend 1 as they are,
+// v_div_fmas_f64, which is then a plain fma, and v_div_fixup_f64, which passes such a quotient through.  The same operations
+// on the same values: bit for bit the compiler's quotient.  Everything outside the range (NaN, the zero vector) is `outside`.
+// (Seeding the reciprocal with h + h from the root's iteration instead of v_rcp_f64 -- one Newton step less, no second
+// transcendental -- was built first and is NOT bit-identical: it rounds 1 / norm the other way for every norm whose
+// significand is all ones, and that is the norm of every nearly unit vector whose squared length falls an ulp or two short
+// of 1 -- the refracted directions: DESIGN.md section 4.)
+__device__ __forceinline__ CheckedNorm checked_norm(double x) {
+    CheckedNorm c;
+    double h;
+    c.norm = sqrt_unscaled(x, h);
+    const double y0 = __builtin_amdgcn_rcp(c.norm);
+    const double y1 = __builtin_fma(y0, __builtin_fma(-c.norm, y0, 1.), y0);
+    const double y2 = __builtin_fma(y1, __builtin_fma(-c.norm, y1, 1.), y1);
+    c.inv = __builtin_fma(__builtin_fma(-c.norm, y2, 1.), y2, y2);
+    c.outside = !((x >= RM_CHECKED_X_MIN) & (x <= RM_CHECKED_X_MAX));              // (NaN and the zero vector: outside)
+    return c;
+}
+#else
+#define RM_SQRT_DISCRIMINANT(x) __builtin_sqrt(x)
+#endif
 // geometry.rs:104-109: multiply by the reciprocal of the norm
+// (RM_CHECKED: `on` -- the lanes whose vector is a ray's; the others' flags do not count)
+#if RM_CHECKED
+__device__ __forceinline__ V3 normalized(V3 a, bool on, bool &sus) {
+    const CheckedNorm c = checked_norm(dot(a, a));
+    sus = sus | (on & c.outside);
+    return scaled(a, (c.norm > 0.) ? c.inv : 1.);
+}
+#define RM_NORMALIZED(a, on) normalized(a, on, sus)
+#else
 __device__ __forceinline__ V3 normalized(V3 a) {
 #if RM_FAST
     // 1/sqrt(x) from the hardware estimate (v_rsq_f64, ~26 bits) and two Newton steps,
@@ -67,6 +141,8 @@ __device__ __forceinline__ V3 normalized(V3 a) {
     return scaled(a, (norm > 0.) ? inv : 1.);     // `if norm > 0` of the reference: else the vector itself (x * 1 is exact)
 #endif
 }
+#define RM_NORMALIZED(a, on) normalized(a)
+#endif
 
 // Scene view: S points at the blob (LDS copy), H carries counts and offsets in SGPRs.
 struct SceneView {
@@ -689,7 +765,7 @@ __device__ __forceinline__ void closest_sphere(const SceneView &sc, ClosestState
     sphere_setup(s, o, d, tca, d2);
     const bool in = on & !(d2 > s.r2);                               // sphere.rs:37
     if (!__any(in)) return;                                          // the whole wave misses: no sqrt
-    const double thc = __builtin_sqrt(s.r2 - d2);
+    const double thc = RM_SQRT_DISCRIMINANT(s.r2 - d2);
     const double t0 = tca - thc;
     const double t1 = tca + thc;
     const double t = (t0 < 0.) ? t1 : t0;                            // :46-48
@@ -863,7 +939,7 @@ __device__ __forceinline__ bool shadow_sphere_from(const SphereRec &s, const Sph
     bool hit = in & front;
     const bool need = in & !front & !occ;          // origin inside the sphere, or the sphere behind it
     if (__any(need)) {
-        const double thc = __builtin_sqrt(s.r2 - d2);
+        const double thc = RM_SQRT_DISCRIMINANT(s.r2 - d2);
         const double t0 = tca - thc;
         const double t1 = tca + thc;
         const double t = (t0 < 0.) ? t1 : t0;
@@ -1092,7 +1168,7 @@ struct Surface {
 // `got`: lanes with a hit.  The other lanes read record 0 of everything (in bounds: the
 // blob ends in 64 words of padding) and their surface is never used.
 template <bool DIV>
-__device__ __forceinline__ Surface surface_at(const SceneView &sc, V3 o, V3 d, const Hit &h, bool got) {
+__device__ __forceinline__ Surface surface_at(const SceneView &sc, V3 o, V3 d, const Hit &h, bool got RM_SUS_PARAM) {
     Surface s;
     s.point = o + scaled(d, h.t);
     const uint32_t ns = sc.H.n_spheres, np = sc.H.n_polygons;
@@ -1103,7 +1179,7 @@ __device__ __forceinline__ Surface surface_at(const SceneView &sc, V3 o, V3 d, c
     s.normal = mk(0., 0., 0.);
     if (where<DIV>(is_s)) {
         const double *sp = sc.S + sc.H.off_spheres + RM_SPHERE_WORDS * (is_s ? pid : 0u);
-        s.normal = normalized(mk(s.point.x - sp[0], s.point.y - sp[1], s.point.z - sp[2]));   // sphere.rs:58
+        s.normal = RM_NORMALIZED(mk(s.point.x - sp[0], s.point.y - sp[1], s.point.z - sp[2]), is_s);   // sphere.rs:58
     }
     if (where<DIV>(is_p | is_t)) {
         const uint32_t word = is_p ? sc.H.off_polygons + RM_POLYGON_WORDS * (pid - ns)          // polygon.rs:95
@@ -1171,11 +1247,12 @@ struct LightAt {
     bool dark;          // adds exactly zero whether or not it is shadowed
 };
 
-__device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, const Surface &s, V3 dir_to_viewer, double exponent) {
+__device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, const Surface &s, V3 dir_to_viewer, double exponent, bool got RM_SUS_PARAM) {
+    (void)got;
     LightAt a;
     const double *lt = sc.G + sc.H.off_lights + RM_LIGHT_WORDS * l;
     a.pos = mk(lt[0], lt[1], lt[2]);
-    a.dir = normalized(a.pos - s.point);                              // :166 (a ray direction: exact)
+    a.dir = RM_NORMALIZED(a.pos - s.point, got);                      // :166 (a ray direction: exact)
     a.ldn = dot(a.dir, s.normal);
     // :168-172 point -/+ normal * 1e-3: one expression, p - n k == p + n (-k) bit for bit
     a.from = s.point + scaled(s.normal, (a.ldn < 0.) ? -1e-3 : 1e-3);
@@ -1193,7 +1270,7 @@ __device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, con
 
 // `pid`: the primitive each lane's hit lies on.
 template <int POW, bool BVH, bool CULL, bool EDGES>
-__device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got, uint32_t pid) {
+__device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got, uint32_t pid RM_SUS_PARAM) {
     const double *m = s.mat;
     const double exponent = m[5];
     // (colour and specular weight are fetched where a light is found unshadowed: held in
@@ -1222,13 +1299,13 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
     // plain-walk kernels: the occluder masks of the walks, where the scene has them
     const bool masks = !BVH && !CULL && sc.H.off_occ != 0u;
     for (uint32_t l = 0; l < sc.H.n_lights;) {
-        const LightAt a = light_at(sc, l, s, dir_to_viewer, exponent);
+        const LightAt a = light_at(sc, l, s, dir_to_viewer, exponent, got RM_SUS_ARG);
         const bool dec_a = !got | a.dark;
         if (!BVH && !CULL && l + 1u < sc.H.n_lights) {
             // plain-walk kernels: lights two at a time -- where both lie on the same side of the
             // surface their shadow rays leave one point and share one walk (any_hit2); where some
             // lane has them on opposite sides (rare) the second light is taken up again alone
-            const LightAt b = light_at(sc, l + 1u, s, dir_to_viewer, exponent);
+            const LightAt b = light_at(sc, l + 1u, s, dir_to_viewer, exponent, got RM_SUS_ARG);
             const bool dec_b = !got | b.dark;
             if (__all(dec_a | dec_b | ((a.ldn < 0.) == (b.ldn < 0.)))) {
                 bool occ_a, occ_b;
@@ -1267,9 +1344,9 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
 // LAZY (per-lane kernels): the reflected ray exists under total reflection only -- no lane of
 // most waves has one -- and is computed under that branch.
 template <bool LAZY>
-__device__ __forceinline__ bool reflect_child(V3 incident, const Surface &s, double ri, V3 &o, V3 &d) {
+__device__ __forceinline__ bool reflect_child(V3 incident, const Surface &s, double ri, double inv_ri, V3 &o, V3 &d) {
     const double c = dot(s.normal, incident);                         // optics.rs:16 (no sign flip)
-    const double r = (c < 0.) ? ri : 1. / ri;
+    const double r = (c < 0.) ? ri : inv_ri;
     const double cos_theta_2 = 1. - r * r * (1. - c * c);
     const bool has = !(cos_theta_2 > 0.);                             // :33-35
     if (!LAZY || has) {
@@ -1279,14 +1356,16 @@ __device__ __forceinline__ bool reflect_child(V3 incident, const Surface &s, dou
     return has;
 }
 
-__device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, double ri, V3 &o, V3 &d) {
+__device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, double ri, double inv_ri, bool glass, V3 &o, V3 &d RM_SUS_PARAM) {
+    (void)glass;
     const double c0 = -dot(s.normal, incident);                       // optics.rs:57
     const bool flip = c0 < 0.;                                        // :60-68: then c = -c, normal = -normal
-    const double r = flip ? ri : 1. / ri;
+    const double r = flip ? ri : inv_ri;
     const double c = flip ? -c0 : c0;
     const double cos_theta_2 = 1. - r * r * (1. - c * c);
     const double k = r * c - __builtin_sqrt(cos_theta_2);
-    d = normalized(scaled(incident, r) + scaled(s.normal, flip ? -k : k));   // :78-79 (flipped normal * k)
+    // (under total reflection k is NaN and there is no such ray: its lanes' flags do not count)
+    d = RM_NORMALIZED(scaled(incident, r) + scaled(s.normal, flip ? -k : k), glass & !(cos_theta_2 < 0.));   // :78-79 (flipped normal * k)
     const double dn = dot(d, s.normal);                               // d . flipped normal = -(d . normal) when flipped
     const bool along = flip ? (dn < 0.) : (dn > 0.);                  // :82 `dir.dot(normal) > 0` with the flipped normal
     o = s.point + scaled(s.normal, (along != flip) ? 1e-4 : -1e-4);   // :82-86: point +- flipped normal * 1e-4
