@@ -597,7 +597,10 @@ static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, 
     // that point pass the 2-D edge tests (polygon.rs:54-56, triangle.rs:69-77), i.e. lie in
     // the convex hull of the vertices' x, y: the hit points are the hull of the vertices
     // LIFTED onto that plane along z -- the vertices themselves when they are coplanar with
-    // it, as they are for everything the reference's constructors build.
+    // it, as they are for everything the reference's constructors build.  That holds for ANY vertex
+    // list, convex or not: a point that is to the left of every edge is wound round by the closed
+    // line at least once, so it lies inside the line's hull (bow ties, darts, clockwise lists:
+    // tests/test_gpu_grazing.py test_odd_vertex_lists).
     auto planar_bounds = [&](uint32_t pid, const rm_vec3 &n, const rm_vec3 &pp, const rm_vec3 *v, uint32_t nv) {
         max_normal = std::max(max_normal, std::sqrt(n.x * n.x + n.y * n.y + n.z * n.z));
         double *pl = &blob[H.off_planar + 16u * (pid - H.n_spheres)];   // zero-filled: count 0 = no edge test
@@ -638,9 +641,25 @@ static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, 
         put_bounds(pid, cx, cy, cz, std::sqrt(r2));
         // the lifted vertices for the cull's edge test (triangles and quads; a triangle
         // repeats its first vertex so that edge 2-3 closes it)
-        bool finite = true;
-        for (const rm_vec3 &q : lifted) finite = finite && std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z);
-        if (finite && (nv == 3u || nv == 4u)) {
+        bool with_edges = nv == 3u || nv == 4u;
+        for (const rm_vec3 &q : lifted) with_edges = with_edges && std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z);
+        // The edge test takes the side of an edge's plane that holds the vertices' mean for the inner one (rm_trace.inc
+        // cull_edge): true of a convex list of either winding, not of any list -- a dart's mean lies on the OUTER side
+        // of the edges at its reflex vertex, and the bundles that hit it between them would be dropped
+        // (tests/test_gpu_grazing.py).  Only lists whose x, y turn one way at every vertex, strictly, get the record;
+        // the others keep their bounding sphere alone.
+        int turn = 0;
+        for (uint32_t i = 0; i < nv && with_edges; i++) {
+            const rm_vec3 &p = lifted[i], &q = lifted[(i + 1u) % nv];
+            for (uint32_t k = 0; k < nv && with_edges; k++) {
+                if (k == i || k == (i + 1u) % nv) continue;
+                const double c = (q.x - p.x) * (lifted[k].y - p.y) - (q.y - p.y) * (lifted[k].x - p.x);
+                const int sgn = c > 0. ? 1 : c < 0. ? -1 : 0;
+                with_edges = sgn != 0 && (turn == 0 || sgn == turn);
+                turn = sgn;
+            }
+        }
+        if (with_edges) {
             for (uint32_t i = 0; i < 4u; i++) {
                 const rm_vec3 &q = lifted[i < nv ? i : 0u];
                 pl[3 * i] = q.x; pl[3 * i + 1] = q.y; pl[3 * i + 2] = q.z;
