@@ -463,7 +463,8 @@ rm_status rm_comm_info(rm_ctx *ctx, int *rank, int *world, int *n_communicators)
  *     that ray, never a fault.
  *   - Occlusion is intersect_shape_set exactly: a hit ANYWHERE along the ray, t in
  *     [0, inf) -- the reference has no maximum distance, so a shadow ray aimed at a light
- *     counts as blocked by a shape BEHIND the light.
+ *     counts as blocked by a shape BEHIND the light.  (The ranged queries below bound the ray:
+ *     rm_occluded_rays_ranged, rm_visible_segments, rm_lights_visible with RM_LIGHTS_CLIPPED.)
  *   - n_rays == 0 is RM_OK and does nothing.
  *   - Device variants are asynchronous on hip_stream (a hipStream_t; NULL = HIP's default
  *     stream), as rm_render_device is; host variants and rm_pick block until the answer is
@@ -512,6 +513,77 @@ rm_status rm_pick(rm_ctx *ctx, const rm_params *params, uint32_t x, uint32_t y, 
  * render.
  */
 rm_status rm_primary_hits_device(rm_ctx *ctx, const rm_params *params, void *device_hits, void *hip_stream);
+
+/* ---- ranged ray queries: segments, point visibility, light visibility ----------------------
+ * The ray queries above answer for rays that run to infinity, as the reference's do.  These take a
+ * closed range [t_min, t_max] of the ray parameter, 0 <= t_min <= t_max, t_max = +inf allowed.
+ * Additive to ABI version 5; a host detects them by " ranges" in rm_build_info().  The numeric
+ * flavour is the strict one, and everything "Semantics common to every query" says holds: the
+ * resident scene, unit directions, device variants asynchronous on hip_stream, no render state
+ * touched (they read the scene image, the pid map and the lights).
+ *
+ * Each primitive offers the candidates the reference forms, with the reference's arithmetic:
+ *   - sphere: the two roots t0 = tca - thc, t1 = tca + thc (sphere.rs:43-45).  The candidate is t0
+ *     if it lies in the range, else t1 if it lies in the range, else none.  For [0, +inf] that is
+ *     the reference's `if t0 < 0 { t1 }` followed by `if t < 0 { None }`.
+ *   - polygon and triangle: the one `dist` of polygon.rs:71-76 / triangle.rs:62-67, accepted when
+ *     it lies in the range and passes the unchanged inside test.
+ * Closest hit: accepted candidates are ordered as before, by |p - o|^2 with p = o + d t
+ * (shapes.rs:128), exact ties to list order; rm_hit.t is the accepted parameter -- a sphere whose
+ * near root lies before t_min is hit at its far root -- point and normal those of that point.
+ * Occlusion: a ray is occluded when any primitive has an accepted candidate.
+ * With {0, +inf} on every ray both give byte for byte what rm_intersect_rays / rm_occluded_rays give.
+ *
+ * Host variants check, before anything is launched, what the unranged ones check and: no NaN in a
+ * range, t_min >= 0, t_max >= t_min; finite segment endpoints, from != to; finite points and
+ * normals, a non-zero normal; skin finite and >= 0; mode 0 or 1.  RM_ERR_INVALID_ARG names the
+ * first offender in rm_last_error and nothing is computed.  For the device variants the
+ * per-element conditions are preconditions: a bad element gets an unspecified answer for that
+ * element, never a fault.  n == 0 is RM_OK and does nothing.
+ */
+typedef struct rm_range { double t_min, t_max; } rm_range;   /* 16 bytes */
+
+/* rm_intersect_rays / rm_occluded_rays with ranges[i] on ray i. */
+rm_status rm_intersect_rays_ranged(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions,
+                                   const rm_range *ranges, uint32_t n_rays, rm_hit *hits);
+rm_status rm_occluded_rays_ranged(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions,
+                                  const rm_range *ranges, uint32_t n_rays, uint8_t *occluded);
+rm_status rm_intersect_rays_ranged_device(rm_ctx *ctx, const void *device_origins, const void *device_directions,
+                                          const void *device_ranges, uint32_t n_rays, void *device_hits,
+                                          void *hip_stream);
+rm_status rm_occluded_rays_ranged_device(rm_ctx *ctx, const void *device_origins, const void *device_directions,
+                                         const void *device_ranges, uint32_t n_rays, void *device_occluded,
+                                         void *hip_stream);
+/*
+ * Can from[i] see to[i]?  With v = to[i] - from[i] the ray is from[i] along normalized(v), its
+ * length L = sqrt(v.v) -- the sqrt and reciprocal the strict normalized() forms -- and the range
+ * [skin, L - skin]: visible[i] = 1 when nothing is accepted in it, else 0.  skin (>= 0, finite) is
+ * the caller's guard against the surfaces the endpoints lie on; the render's own is 1e-3.  A range
+ * that comes out empty, L - skin < skin, is visible.
+ */
+rm_status rm_visible_segments(rm_ctx *ctx, const rm_vec3 *from, const rm_vec3 *to, uint32_t n, double skin,
+                              uint8_t *visible);
+rm_status rm_visible_segments_device(rm_ctx *ctx, const void *device_from, const void *device_to, uint32_t n,
+                                     double skin, void *device_visible, void *hip_stream);
+/*
+ * Which lights reach a surface point: lit is [n_points][n_lights] bytes.  For point P, normal N and
+ * light j, renderer.rs:166-174 exactly, each operation rounded once:
+ * light_dir = normalized(light.position - P); the origin is P - N.scaled(1e-3) if light_dir . N < 0,
+ * else P + N.scaled(1e-3).
+ *   RM_LIGHTS_AS_RENDERED: lit = !intersect_shape_set(origin, light_dir), unbounded: bit for bit
+ *     the decision direct_lighting takes, a shape BEHIND the light shadows.
+ *   RM_LIGHTS_CLIPPED: the same ray in the range [0, |light.position - P|] (the norm normalized
+ *     computed): a shape behind the light no longer shadows.
+ * n_lights must be the resident scene's (it sizes lit), else RM_ERR_INVALID_ARG; a scene without
+ * lights is RM_OK and writes nothing.
+ */
+#define RM_LIGHTS_AS_RENDERED 0u
+#define RM_LIGHTS_CLIPPED 1u
+rm_status rm_lights_visible(rm_ctx *ctx, const rm_vec3 *points, const rm_vec3 *normals, uint32_t n_points,
+                            uint32_t n_lights, uint32_t mode, uint8_t *lit);
+rm_status rm_lights_visible_device(rm_ctx *ctx, const void *device_points, const void *device_normals,
+                                   uint32_t n_points, uint32_t n_lights, uint32_t mode, void *device_lit,
+                                   void *hip_stream);
 
 /* ---- the oriented camera: look-at and turn for renders and pixel queries ------------------
  *

@@ -15,6 +15,7 @@ RM_MAX_DEPTH = 32
 RM_COMM_ID_BYTES, RM_MAX_FRAME_SLOTS = 128, 4
 RM_PATCH_SIZE = 32
 RM_SHAPE_SPHERE, RM_SHAPE_POLYGON, RM_SHAPE_MESH = 0, 1, 2
+RM_LIGHTS_AS_RENDERED, RM_LIGHTS_CLIPPED = 0, 1
 
 STATUS_NAMES = {0: "RM_OK", 1: "RM_ERR_INVALID_ARG", 2: "RM_ERR_DIMENSIONS", 3: "RM_ERR_NO_DEVICE",
                 4: "RM_ERR_HIP", 5: "RM_ERR_NO_SCENE", 6: "RM_ERR_SCENE_LIMIT", 7: "RM_ERR_IO",
@@ -85,6 +86,11 @@ class rm_hit(C.Structure):
     """One answer of find_closest_intersect (shapes.rs:110-143): the ray queries' record."""
     _fields_ = [("t", C.c_double), ("point", rm_vec3), ("normal", rm_vec3), ("shape", C.c_uint32),
                 ("element", C.c_uint32), ("hit", C.c_int32), ("_pad", C.c_uint32)]
+
+
+class rm_range(C.Structure):
+    """The closed range [t_min, t_max] of the ray parameter a ranged query accepts hits in (16 bytes)."""
+    _fields_ = [("t_min", C.c_double), ("t_max", C.c_double)]
 
 
 class rm_camera_basis(C.Structure):
@@ -161,6 +167,14 @@ SIGNATURES = {
     "rm_occluded_rays_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP]),
     "rm_pick": (C.c_int, [_VP, _P(rm_params), C.c_uint32, C.c_uint32, _P(rm_hit)]),
     "rm_primary_hits_device": (C.c_int, [_VP, _P(rm_params), _VP, _VP]),
+    "rm_intersect_rays_ranged": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), _P(rm_range), C.c_uint32, _P(rm_hit)]),
+    "rm_occluded_rays_ranged": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), _P(rm_range), C.c_uint32, _P(C.c_uint8)]),
+    "rm_intersect_rays_ranged_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP]),
+    "rm_occluded_rays_ranged_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP]),
+    "rm_visible_segments": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), C.c_uint32, C.c_double, _P(C.c_uint8)]),
+    "rm_visible_segments_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_double, _VP, _VP]),
+    "rm_lights_visible": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint8)]),
+    "rm_lights_visible_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, _VP, _VP]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -26,6 +26,25 @@ def _rays(origins, directions):
     return o, d
 
 
+def _ranges(ranges, n):
+    """(n, 2) float64 [t_min, t_max] rows from an (n, 2) array or one (t_min, t_max) pair for every ray."""
+    r = np.asarray(ranges, dtype=np.float64)
+    if r.shape == (2,):
+        r = np.broadcast_to(r, (n, 2))
+    if r.shape != (n, 2):
+        raise ValueError("ranges must be one (t_min, t_max) pair or a float64 array of shape (%d, 2), got %s" % (n, r.shape))
+    return np.ascontiguousarray(r)
+
+
+def _pairs(a, b, names):
+    """Two (N, 3) float64 arrays of one shape: segment endpoints, or points and normals."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape:
+        raise ValueError("%s and %s must be two float64 arrays of shape (N, 3), got %s and %s" % (names[0], names[1], a.shape, b.shape))
+    return a, b
+
+
 def _device_hits(raw):
     """DeviceHits over a float64 tensor whose last dimension is one rm_hit (9 words)."""
     ints = raw.view(_torch().int32)                       # 18 int32 a record: shape, element, hit are 14, 15, 16
@@ -155,29 +174,43 @@ class Context:
                    self.ptr)
 
     # ---- ray queries (include/rusty_marcher_amd.h, "ray queries") ----
-    def intersect(self, origins, directions):
+    def intersect(self, origins, directions, ranges=None):
         """find_closest_intersect (shapes.rs:110-143) of N rays of the caller's own: (N, 3) float64 origins and unit
-        directions -> a structured array of N rm_hit records (HIT_DTYPE), written by the library in place."""
+        directions -> a structured array of N rm_hit records (HIT_DTYPE), written by the library in place.
+        ranges: an (N, 2) array of [t_min, t_max], or one pair for every ray: only hits in the range count
+        (rm_intersect_rays_ranged)."""
         o, d = _rays(origins, directions)
         out = np.zeros(o.shape[0], dtype=HIT_DTYPE)
         V = C.POINTER(_lib.rm_vec3)
+        if ranges is not None:
+            r = _ranges(ranges, o.shape[0])
+            _lib.check(self.L.rm_intersect_rays_ranged(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V),
+                                                       r.ctypes.data_as(C.POINTER(_lib.rm_range)), o.shape[0],
+                                                       out.ctypes.data_as(C.POINTER(_lib.rm_hit))), self.ptr)
+            return out
         _lib.check(self.L.rm_intersect_rays(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V), o.shape[0],
                                             out.ctypes.data_as(C.POINTER(_lib.rm_hit))), self.ptr)
         return out
 
-    def occluded(self, origins, directions):
+    def occluded(self, origins, directions, ranges=None):
         """intersect_shape_set (shapes.rs:92-108) of N rays: a bool array, True where anything lies along the ray
-        (no maximum distance, as in the reference)."""
+        (no maximum distance, as in the reference) -- or, with `ranges` (as for intersect), within the ray's range."""
         o, d = _rays(origins, directions)
         out = np.zeros(o.shape[0], dtype=np.uint8)
         V = C.POINTER(_lib.rm_vec3)
+        if ranges is not None:
+            r = _ranges(ranges, o.shape[0])
+            _lib.check(self.L.rm_occluded_rays_ranged(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V),
+                                                      r.ctypes.data_as(C.POINTER(_lib.rm_range)), o.shape[0],
+                                                      out.ctypes.data_as(C.POINTER(C.c_uint8))), self.ptr)
+            return out.view(np.bool_)
         _lib.check(self.L.rm_occluded_rays(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V), o.shape[0],
                                            out.ctypes.data_as(C.POINTER(C.c_uint8))), self.ptr)
         return out.view(np.bool_)
 
-    def _device_rays(self, origins, directions):
+    def _device_rays(self, origins, directions, names=("origins", "directions")):
         torch = _torch()
-        for name, t in (("origins", origins), ("directions", directions)):
+        for name, t in zip(names, (origins, directions)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
                 raise ValueError("%s must be a float64 torch tensor of shape (N, 3)" % name)
             if t.device.type != "cuda" or t.device.index != self.device:
@@ -185,8 +218,23 @@ class Context:
             if not t.is_contiguous():
                 raise ValueError("%s must be contiguous" % name)
         if origins.shape != directions.shape:
-            raise ValueError("origins %s and directions %s differ in shape" % (tuple(origins.shape), tuple(directions.shape)))
+            raise ValueError("%s %s and %s %s differ in shape" % (names[0], tuple(origins.shape), names[1], tuple(directions.shape)))
         return origins.shape[0]
+
+    def _device_ranges(self, ranges, like):
+        """A contiguous (N, 2) float64 tensor next to `like` from one, or from one (t_min, t_max) pair."""
+        torch = _torch()
+        n = like.shape[0]
+        if not isinstance(ranges, torch.Tensor):
+            r = np.asarray(ranges, dtype=np.float64)
+            if r.shape != (2,):
+                raise ValueError("ranges must be one (t_min, t_max) pair or a float64 torch tensor of shape (%d, 2)" % n)
+            return torch.from_numpy(np.ascontiguousarray(np.broadcast_to(r, (n, 2)))).to(like.device)
+        if ranges.dtype != torch.float64 or tuple(ranges.shape) != (n, 2) or not ranges.is_contiguous():
+            raise ValueError("ranges must be a contiguous float64 torch tensor of shape (%d, 2), got %s" % (n, tuple(ranges.shape)))
+        if ranges.device != like.device:
+            raise ValueError("ranges must live on %s, not %s" % (like.device, ranges.device))
+        return ranges
 
     def _stream(self, stream):
         """The HIP stream of a call: `stream` (a torch stream or a raw handle), else torch's current stream."""
@@ -195,23 +243,85 @@ class Context:
             stream = torch.cuda.current_stream(self.device)
         return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
 
-    def intersect_device(self, origins, directions, stream=None):
+    def intersect_device(self, origins, directions, stream=None, ranges=None):
         """intersect() on torch tensors of the context's device, asynchronous on `stream` (torch's current one by
-        default): DeviceHits, no copy to the host."""
+        default): DeviceHits, no copy to the host.  ranges: an (N, 2) tensor there, or one pair."""
         torch = _torch()
         n = self._device_rays(origins, directions)
         raw = torch.empty((n, 9), dtype=torch.float64, device=origins.device)
+        if ranges is not None:
+            r = self._device_ranges(ranges, origins)
+            _lib.check(self.L.rm_intersect_rays_ranged_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                                              C.c_void_p(r.data_ptr()), n, C.c_void_p(raw.data_ptr()),
+                                                              C.c_void_p(self._stream(stream))), self.ptr)
+            return _device_hits(raw)
         _lib.check(self.L.rm_intersect_rays_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                                    n, C.c_void_p(raw.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
         return _device_hits(raw)
 
-    def occluded_device(self, origins, directions, stream=None):
+    def occluded_device(self, origins, directions, stream=None, ranges=None):
         """occluded() on torch tensors of the context's device: a bool tensor there, asynchronous on `stream`."""
         torch = _torch()
         n = self._device_rays(origins, directions)
         out = torch.empty((n,), dtype=torch.uint8, device=origins.device)
+        if ranges is not None:
+            r = self._device_ranges(ranges, origins)
+            _lib.check(self.L.rm_occluded_rays_ranged_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                                             C.c_void_p(r.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                                             C.c_void_p(self._stream(stream))), self.ptr)
+            return out.view(torch.bool)
         _lib.check(self.L.rm_occluded_rays_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                                   n, C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return out.view(torch.bool)
+
+    def visible(self, a, b, skin=0.):
+        """rm_visible_segments: can a[i] see b[i]?  (N, 3) float64 endpoints -> a bool array, True where nothing lies on the
+        segment between `skin` and its length less `skin` (the guard against the surfaces the endpoints lie on)."""
+        a, b = _pairs(a, b, ("a", "b"))
+        out = np.zeros(a.shape[0], dtype=np.uint8)
+        V = C.POINTER(_lib.rm_vec3)
+        _lib.check(self.L.rm_visible_segments(self.ptr, a.ctypes.data_as(V), b.ctypes.data_as(V), a.shape[0], float(skin),
+                                              out.ctypes.data_as(C.POINTER(C.c_uint8))), self.ptr)
+        return out.view(np.bool_)
+
+    def visible_device(self, a, b, skin=0., stream=None):
+        """visible() on torch tensors of the context's device: a bool tensor there, asynchronous on `stream`."""
+        torch = _torch()
+        n = self._device_rays(a, b, ("a", "b"))
+        out = torch.empty((n,), dtype=torch.uint8, device=a.device)
+        _lib.check(self.L.rm_visible_segments_device(self.ptr, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, float(skin),
+                                                     C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return out.view(torch.bool)
+
+    def n_lights(self):
+        """Lights of the uploaded scene (what sizes lights_visible's answer)."""
+        if self._uploaded is None:
+            raise _lib.BackendError(_lib.RM_ERR_NO_SCENE, "no scene uploaded")
+        d = self._uploaded.desc() if hasattr(self._uploaded, "desc") else self._uploaded
+        return int(d.n_lights)
+
+    def lights_visible(self, points, normals, clipped=False):
+        """rm_lights_visible: which lights reach each surface point -- an (N, n_lights) bool array.  clipped=False: the
+        decision direct_lighting takes (renderer.rs:166-174), a shape behind the light shadows; True: the shadow ray ends
+        at the light."""
+        p, nrm = _pairs(points, normals, ("points", "normals"))
+        nl = self.n_lights()
+        out = np.zeros((p.shape[0], nl), dtype=np.uint8)
+        V = C.POINTER(_lib.rm_vec3)
+        _lib.check(self.L.rm_lights_visible(self.ptr, p.ctypes.data_as(V), nrm.ctypes.data_as(V), p.shape[0], nl,
+                                            _lib.RM_LIGHTS_CLIPPED if clipped else _lib.RM_LIGHTS_AS_RENDERED,
+                                            out.ctypes.data_as(C.POINTER(C.c_uint8))), self.ptr)
+        return out.view(np.bool_)
+
+    def lights_visible_device(self, points, normals, clipped=False, stream=None):
+        """lights_visible() on torch tensors of the context's device: an (N, n_lights) bool tensor there."""
+        torch = _torch()
+        n = self._device_rays(points, normals, ("points", "normals"))
+        nl = self.n_lights()
+        out = torch.empty((n, nl), dtype=torch.uint8, device=points.device)
+        _lib.check(self.L.rm_lights_visible_device(self.ptr, C.c_void_p(points.data_ptr()), C.c_void_p(normals.data_ptr()), n, nl,
+                                                   _lib.RM_LIGHTS_CLIPPED if clipped else _lib.RM_LIGHTS_AS_RENDERED,
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
         return out.view(torch.bool)
 
     def primary_hits_device(self, params, out=None, stream=None):

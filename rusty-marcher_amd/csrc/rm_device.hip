@@ -298,7 +298,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {

@@ -29,7 +29,27 @@ struct QueryArgs {
     double cam_rx, cam_ry, cam_rz, cam_ux, cam_uy, cam_uz, cam_fx, cam_fy, cam_fz;
 };
 
+// The ranged queries (rm_*_ranged, rm_visible_segments, rm_lights_visible): kernels and an argument block of their own, beside
+// the ones above.
+enum { RM_RANGED_CLOSEST = 0, RM_RANGED_OCCLUDED = 1, RM_RANGED_SEGMENTS = 2, RM_RANGED_LIGHTS = 3 };
+
+struct RangedArgs {
+    rm_dev_header H;
+    const uint32_t *pid_map;
+    // one lane per answer: ray (CLOSEST / OCCLUDED), segment (SEGMENTS), (point, light) pair with the point index major (LIGHTS)
+    uint64_t n;
+    const rm_vec3 *a, *b;                    // origins, directions | from, to | points, normals
+    const rm_range *ranges;                  // CLOSEST / OCCLUDED
+    double skin;                             // SEGMENTS
+    uint32_t n_lights, mode;                 // LIGHTS (mode: RM_LIGHTS_AS_RENDERED / RM_LIGHTS_CLIPPED)
+    rm_hit *hits;                            // CLOSEST
+    uint8_t *out;                            // OCCLUDED: occluded; SEGMENTS: visible; LIGHTS: lit
+};
+
 }  // namespace rmdev
+
+// The kernel of a ranged query launch (64 lanes a workgroup, arguments: scene blob, RangedArgs).
+const void *rm_ranged_kernel(int kind, bool bvh);
 
 // The kernel of a query launch (64 lanes a workgroup, arguments: scene blob, QueryArgs).
 // bvh: the scene carries a hierarchy (rm_dev_header::off_bvh_spheres / off_bvh_triangles).

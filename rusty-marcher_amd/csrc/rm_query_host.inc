@@ -193,3 +193,244 @@ rm_status rm_primary_hits_device(rm_ctx *ctx, const rm_params *params, void *dev
 }
 
 }  // extern "C"
+
+// ---- ranged queries: rays with a range, segments, lights (rm_query.hip's ranged kernels) ----------------------------------
+static rm_status launch_ranged(rm_ctx *ctx, const char *who, int kind, RangedArgs &q, hipStream_t stream) {
+    q.H = ctx->H;
+    q.pid_map = ctx->d_pid_map;
+    const uint64_t blocks = (q.n + 63u) / 64u;
+    if (blocks > 0x7FFFFFFFull) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": too many answers for one launch");
+    const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (as launch_query)
+    const void *fn = rm_ranged_kernel(kind, bvh);
+    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "ranged query: no such kernel");
+    void *args[] = {(void *)&ctx->d_scene, (void *)&q};
+    RM_HIP(ctx, hipLaunchKernel(fn, dim3((uint32_t)blocks), dim3(64), args, 0, stream));
+    return RM_OK;
+}
+
+static bool finite3(const rm_vec3 &v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
+
+static rm_status check_ranges(rm_ctx *ctx, const char *who, const rm_range *r, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        const bool nan = std::isnan(r[i].t_min) || std::isnan(r[i].t_max);
+        if (nan || !(r[i].t_min >= 0.) || !(r[i].t_max >= r[i].t_min)) {
+            char buf[224];
+            std::snprintf(buf, sizeof buf, "%s: ray %u: range [%g, %g]: %s", who, i, r[i].t_min, r[i].t_max,
+                          nan ? "not a number" : !(r[i].t_min >= 0.) ? "t_min < 0" : "t_max < t_min");
+            return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+        }
+    }
+    return RM_OK;
+}
+
+static rm_status check_skin(rm_ctx *ctx, const char *who, double skin) {
+    if (std::isfinite(skin) && skin >= 0.) return RM_OK;
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "%s: skin %g must be finite and >= 0", who, skin);
+    return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+}
+
+static rm_status check_segments(rm_ctx *ctx, const char *who, const rm_vec3 *a, const rm_vec3 *b, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        const bool finite = finite3(a[i]) && finite3(b[i]);
+        if (!finite || (a[i].x == b[i].x && a[i].y == b[i].y && a[i].z == b[i].z)) {
+            char buf[256];
+            std::snprintf(buf, sizeof buf, "%s: segment %u: from (%g, %g, %g) to (%g, %g, %g): %s", who, i, a[i].x, a[i].y, a[i].z,
+                          b[i].x, b[i].y, b[i].z, finite ? "from == to" : "not finite");
+            return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+        }
+    }
+    return RM_OK;
+}
+
+static rm_status check_points(rm_ctx *ctx, const char *who, const rm_vec3 *p, const rm_vec3 *nrm, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        const bool finite = finite3(p[i]) && finite3(nrm[i]);
+        if (!finite || (nrm[i].x == 0. && nrm[i].y == 0. && nrm[i].z == 0.)) {
+            char buf[256];
+            std::snprintf(buf, sizeof buf, "%s: point %u: (%g, %g, %g), normal (%g, %g, %g): %s", who, i, p[i].x, p[i].y, p[i].z,
+                          nrm[i].x, nrm[i].y, nrm[i].z, finite ? "the normal is zero" : "not finite");
+            return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+        }
+    }
+    return RM_OK;
+}
+
+// mode and n_lights of rm_lights_visible*: what a host can get wrong without touching an element
+static rm_status check_lights_call(rm_ctx *ctx, const char *who, uint32_t n_lights, uint32_t mode) {
+    if (mode != RM_LIGHTS_AS_RENDERED && mode != RM_LIGHTS_CLIPPED) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "%s: mode %u is neither RM_LIGHTS_AS_RENDERED (0) nor RM_LIGHTS_CLIPPED (1)", who, mode);
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+    }
+    if (n_lights != ctx->H.n_lights) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "%s: n_lights %u, the resident scene has %u", who, n_lights, ctx->H.n_lights);
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+    }
+    return RM_OK;
+}
+
+// What every ranged entry point asks first.  *done: nothing (more) to do, return the status.
+static rm_status ranged_preamble(rm_ctx *ctx, const char *who, uint64_t n, bool *done) {
+    *done = true;
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    if (!ctx->have_scene) return ctx_fail(ctx, RM_ERR_NO_SCENE, std::string(who) + ": no scene uploaded (rm_scene_upload)");
+    *done = n == 0;
+    return RM_OK;
+}
+
+// Host variant: `n_in` arrays of n elements go across (sizes in `in_bytes`), the kernel runs, out_bytes come back.
+struct RangedHostIn { const void *src; size_t bytes; };
+static rm_status ranged_host_run(rm_ctx *ctx, const char *who, int kind, RangedArgs &q, const RangedHostIn (&in)[3], void *out,
+                                 size_t out_bytes) {
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    char *buf = nullptr;
+    if (rm_status sst = query_staging(ctx, in[0].bytes + in[1].bytes + in[2].bytes + out_bytes, &buf)) return sst;
+    char *at[4] = {buf, buf + in[0].bytes, buf + in[0].bytes + in[1].bytes, buf + in[0].bytes + in[1].bytes + in[2].bytes};
+    for (int k = 0; k < 3; k++)
+        if (in[k].bytes) RM_HIP(ctx, hipMemcpyAsync(at[k], in[k].src, in[k].bytes, hipMemcpyHostToDevice, ctx->stream));
+    q.a = reinterpret_cast<const rm_vec3 *>(at[0]);
+    q.b = reinterpret_cast<const rm_vec3 *>(at[1]);
+    q.ranges = reinterpret_cast<const rm_range *>(at[2]);
+    if (kind == RM_RANGED_CLOSEST) q.hits = reinterpret_cast<rm_hit *>(at[3]);
+    else q.out = reinterpret_cast<uint8_t *>(at[3]);
+    if (rm_status qst = launch_ranged(ctx, who, kind, q, ctx->stream)) return qst;
+    RM_HIP(ctx, hipMemcpyAsync(out, at[3], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RM_OK;
+}
+
+static rm_status rays_ranged_host_impl(rm_ctx *ctx, const char *who, bool occlusion, const rm_vec3 *origins, const rm_vec3 *directions,
+                                       const rm_range *ranges, uint32_t n_rays, void *out) {
+    bool done;
+    if (rm_status st = ranged_preamble(ctx, who, n_rays, &done)) return st;
+    if (done) return RM_OK;
+    if (!origins || !directions || !ranges || !out) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL array");
+    if (rm_status cst = check_rays(ctx, who, origins, directions, n_rays)) return cst;
+    if (rm_status cst = check_ranges(ctx, who, ranges, n_rays)) return cst;
+    RangedArgs q{};
+    q.n = n_rays;
+    const size_t vb = (size_t)n_rays * sizeof(rm_vec3);
+    return ranged_host_run(ctx, who, occlusion ? RM_RANGED_OCCLUDED : RM_RANGED_CLOSEST, q,
+                           {{origins, vb}, {directions, vb}, {ranges, (size_t)n_rays * sizeof(rm_range)}}, out,
+                           (size_t)n_rays * (occlusion ? sizeof(uint8_t) : sizeof(rm_hit)));
+}
+
+static rm_status rays_ranged_device_impl(rm_ctx *ctx, const char *who, bool occlusion, const void *origins, const void *directions,
+                                         const void *ranges, uint32_t n_rays, void *out, void *hip_stream) {
+    bool done;
+    if (rm_status st = ranged_preamble(ctx, who, n_rays, &done)) return st;
+    if (done) return RM_OK;
+    if (!origins || !directions || !ranges || !out) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL device buffer");
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RangedArgs q{};
+    q.n = n_rays;
+    q.a = static_cast<const rm_vec3 *>(origins);
+    q.b = static_cast<const rm_vec3 *>(directions);
+    q.ranges = static_cast<const rm_range *>(ranges);
+    if (occlusion) q.out = static_cast<uint8_t *>(out);
+    else q.hits = static_cast<rm_hit *>(out);
+    return launch_ranged(ctx, who, occlusion ? RM_RANGED_OCCLUDED : RM_RANGED_CLOSEST, q, (hipStream_t)hip_stream);
+}
+
+static rm_status segments_impl(rm_ctx *ctx, const char *who, bool device, const void *from, const void *to, uint32_t n, double skin,
+                               void *visible, void *hip_stream) {
+    bool done;
+    if (rm_status st = ranged_preamble(ctx, who, n, &done)) return st;
+    if (done) return RM_OK;
+    if (!from || !to || !visible) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + (device ? ": NULL device buffer" : ": NULL array"));
+    if (rm_status cst = check_skin(ctx, who, skin)) return cst;
+    RangedArgs q{};
+    q.n = n;
+    q.skin = skin;
+    if (!device) {
+        if (rm_status cst = check_segments(ctx, who, static_cast<const rm_vec3 *>(from), static_cast<const rm_vec3 *>(to), n)) return cst;
+        const size_t vb = (size_t)n * sizeof(rm_vec3);
+        return ranged_host_run(ctx, who, RM_RANGED_SEGMENTS, q, {{from, vb}, {to, vb}, {nullptr, 0}}, visible, (size_t)n);
+    }
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    q.a = static_cast<const rm_vec3 *>(from);
+    q.b = static_cast<const rm_vec3 *>(to);
+    q.out = static_cast<uint8_t *>(visible);
+    return launch_ranged(ctx, who, RM_RANGED_SEGMENTS, q, (hipStream_t)hip_stream);
+}
+
+static rm_status lights_impl(rm_ctx *ctx, const char *who, bool device, const void *points, const void *normals, uint32_t n_points,
+                             uint32_t n_lights, uint32_t mode, void *lit, void *hip_stream) {
+    bool done;
+    if (rm_status st = ranged_preamble(ctx, who, n_points, &done)) return st;
+    if (done) return RM_OK;
+    if (rm_status cst = check_lights_call(ctx, who, n_lights, mode)) return cst;
+    if (n_lights == 0) return RM_OK;                                  // a scene without lights: nothing to write
+    if (!points || !normals || !lit) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + (device ? ": NULL device buffer" : ": NULL array"));
+    RangedArgs q{};
+    q.n = (uint64_t)n_points * n_lights;
+    q.n_lights = n_lights;
+    q.mode = mode;
+    if (!device) {
+        if (rm_status cst = check_points(ctx, who, static_cast<const rm_vec3 *>(points), static_cast<const rm_vec3 *>(normals), n_points)) return cst;
+        const size_t vb = (size_t)n_points * sizeof(rm_vec3);
+        return ranged_host_run(ctx, who, RM_RANGED_LIGHTS, q, {{points, vb}, {normals, vb}, {nullptr, 0}}, lit, (size_t)q.n);
+    }
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    q.a = static_cast<const rm_vec3 *>(points);
+    q.b = static_cast<const rm_vec3 *>(normals);
+    q.out = static_cast<uint8_t *>(lit);
+    return launch_ranged(ctx, who, RM_RANGED_LIGHTS, q, (hipStream_t)hip_stream);
+}
+
+extern "C" {
+
+rm_status rm_intersect_rays_ranged(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions, const rm_range *ranges, uint32_t n_rays,
+                                   rm_hit *hits) {
+    return guarded(ctx, "rm_intersect_rays_ranged",
+                   [&]() { return rays_ranged_host_impl(ctx, "rm_intersect_rays_ranged", false, origins, directions, ranges, n_rays, hits); });
+}
+
+rm_status rm_occluded_rays_ranged(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions, const rm_range *ranges, uint32_t n_rays,
+                                  uint8_t *occluded) {
+    return guarded(ctx, "rm_occluded_rays_ranged",
+                   [&]() { return rays_ranged_host_impl(ctx, "rm_occluded_rays_ranged", true, origins, directions, ranges, n_rays, occluded); });
+}
+
+rm_status rm_intersect_rays_ranged_device(rm_ctx *ctx, const void *device_origins, const void *device_directions, const void *device_ranges,
+                                          uint32_t n_rays, void *device_hits, void *hip_stream) {
+    return guarded(ctx, "rm_intersect_rays_ranged_device", [&]() {
+        return rays_ranged_device_impl(ctx, "rm_intersect_rays_ranged_device", false, device_origins, device_directions, device_ranges, n_rays,
+                                       device_hits, hip_stream);
+    });
+}
+
+rm_status rm_occluded_rays_ranged_device(rm_ctx *ctx, const void *device_origins, const void *device_directions, const void *device_ranges,
+                                         uint32_t n_rays, void *device_occluded, void *hip_stream) {
+    return guarded(ctx, "rm_occluded_rays_ranged_device", [&]() {
+        return rays_ranged_device_impl(ctx, "rm_occluded_rays_ranged_device", true, device_origins, device_directions, device_ranges, n_rays,
+                                       device_occluded, hip_stream);
+    });
+}
+
+rm_status rm_visible_segments(rm_ctx *ctx, const rm_vec3 *from, const rm_vec3 *to, uint32_t n, double skin, uint8_t *visible) {
+    return guarded(ctx, "rm_visible_segments", [&]() { return segments_impl(ctx, "rm_visible_segments", false, from, to, n, skin, visible, nullptr); });
+}
+
+rm_status rm_visible_segments_device(rm_ctx *ctx, const void *device_from, const void *device_to, uint32_t n, double skin,
+                                     void *device_visible, void *hip_stream) {
+    return guarded(ctx, "rm_visible_segments_device",
+                   [&]() { return segments_impl(ctx, "rm_visible_segments_device", true, device_from, device_to, n, skin, device_visible, hip_stream); });
+}
+
+rm_status rm_lights_visible(rm_ctx *ctx, const rm_vec3 *points, const rm_vec3 *normals, uint32_t n_points, uint32_t n_lights, uint32_t mode,
+                            uint8_t *lit) {
+    return guarded(ctx, "rm_lights_visible",
+                   [&]() { return lights_impl(ctx, "rm_lights_visible", false, points, normals, n_points, n_lights, mode, lit, nullptr); });
+}
+
+rm_status rm_lights_visible_device(rm_ctx *ctx, const void *device_points, const void *device_normals, uint32_t n_points, uint32_t n_lights,
+                                   uint32_t mode, void *device_lit, void *hip_stream) {
+    return guarded(ctx, "rm_lights_visible_device", [&]() {
+        return lights_impl(ctx, "rm_lights_visible_device", true, device_points, device_normals, n_points, n_lights, mode, device_lit, hip_stream);
+    });
+}
+
+}  // extern "C"

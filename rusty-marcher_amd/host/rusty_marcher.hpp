@@ -343,6 +343,24 @@ struct Renderer {
         check(rm_pick(ctx_, &p, x, y, &hit), ctx_);
         return hit;
     }
+    // Can a see b in sc (rm_visible_segments)?  Nothing may lie on the segment between `skin` and its length less `skin`: the
+    // guard against the surfaces the two points lie on (the render's own is 1e-3).
+    bool visible(const scene::Scene &sc, Vec3f a, Vec3f b, double skin = 0.) {
+        upload(sc);
+        const rm_vec3 from = a.c(), to = b.c();
+        uint8_t seen = 0;
+        check(rm_visible_segments(ctx_, &from, &to, 1, skin, &seen), ctx_);
+        return seen != 0;
+    }
+    // Which of sc.lights reach the surface point `point` with normal `normal` -- a pick's (rm_lights_visible).  clipped false:
+    // the decision direct_lighting takes (renderer.rs:166-174), a shape behind the light shadows; true: the ray ends at the light.
+    std::vector<bool> lit_by(const scene::Scene &sc, Vec3f point, Vec3f normal, bool clipped = false) {
+        upload(sc);
+        const rm_vec3 p = point.c(), n = normal.c();
+        std::vector<uint8_t> lit(sc.lights.size());
+        check(rm_lights_visible(ctx_, &p, &n, 1, (uint32_t)lit.size(), clipped ? RM_LIGHTS_CLIPPED : RM_LIGHTS_AS_RENDERED, lit.data()), ctx_);
+        return std::vector<bool>(lit.begin(), lit.end());
+    }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
     void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }
@@ -365,12 +383,9 @@ struct Renderer {
 
   private:
     rm_ctx *ctx_ = nullptr;
-    rm_params prepare(size_t width_px, size_t height_px, const scene::Scene &sc, bool announce = true) {
+    // the whole Scene goes to every call, as the reference hands it to render() (the library copies only what changed)
+    void upload(const scene::Scene &sc) {
         if (!ctx_) check(rm_init(0, &ctx_));
-        if (announce) {
-            if (height_px % 32 != 0 || width_px % 32 != 0) std::printf("Dimensions mismatch\n");
-            std::printf("Rendering using patches of size %d, using %zu patches overall\n", 32, (height_px / 32) * (width_px / 32));
-        }
         bool owned = false;
         rm_scene *flat = sc.flatten(&owned);
         rm_scene_desc d;
@@ -378,6 +393,14 @@ struct Renderer {
         const rm_status up = rm_scene_upload(ctx_, &d);
         if (owned) rm_scene_free(flat);
         check(up, ctx_);
+    }
+    rm_params prepare(size_t width_px, size_t height_px, const scene::Scene &sc, bool announce = true) {
+        if (!ctx_) check(rm_init(0, &ctx_));
+        if (announce) {
+            if (height_px % 32 != 0 || width_px % 32 != 0) std::printf("Dimensions mismatch\n");
+            std::printf("Rendering using patches of size %d, using %zu patches overall\n", 32, (height_px / 32) * (width_px / 32));
+        }
+        upload(sc);
         rm_params p;
         rm_create_renderer(fov, height, width, &p);
         p.frame_width = (uint32_t)width_px;

@@ -122,6 +122,18 @@ pub struct RmHit {
     pub _pad: u32,
 }
 
+/// `rm_range`: the closed range [t_min, t_max] of the ray parameter a ranged query accepts hits in (16 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmRange {
+    pub t_min: f64,
+    pub t_max: f64,
+}
+
+/// `rm_lights_visible`'s modes: the decision direct_lighting takes / the shadow ray ended at the light.
+pub const RM_LIGHTS_AS_RENDERED: u32 = 0;
+pub const RM_LIGHTS_CLIPPED: u32 = 1;
+
 /// `rm_camera_basis`: the oriented camera's view direction, three world-space unit vectors (72 bytes).
 /// The reference's fixed view is right (1,0,0), up (0,1,0), forward (0,0,-1).
 #[repr(C)]
@@ -206,6 +218,14 @@ extern "C" {
     fn rm_occluded_rays_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, n_rays: u32, device_occluded: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_pick(ctx: *mut RmCtx, params: *const RmParams, x: u32, y: u32, hit: *mut RmHit) -> c_int;
     fn rm_primary_hits_device(ctx: *mut RmCtx, params: *const RmParams, device_hits: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_intersect_rays_ranged(ctx: *mut RmCtx, origins: *const RmVec3, directions: *const RmVec3, ranges: *const RmRange, n_rays: u32, hits: *mut RmHit) -> c_int;
+    fn rm_occluded_rays_ranged(ctx: *mut RmCtx, origins: *const RmVec3, directions: *const RmVec3, ranges: *const RmRange, n_rays: u32, occluded: *mut u8) -> c_int;
+    fn rm_intersect_rays_ranged_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, device_ranges: *const c_void, n_rays: u32, device_hits: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_occluded_rays_ranged_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, device_ranges: *const c_void, n_rays: u32, device_occluded: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_visible_segments(ctx: *mut RmCtx, from: *const RmVec3, to: *const RmVec3, n: u32, skin: f64, visible: *mut u8) -> c_int;
+    fn rm_visible_segments_device(ctx: *mut RmCtx, device_from: *const c_void, device_to: *const c_void, n: u32, skin: f64, device_visible: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_lights_visible(ctx: *mut RmCtx, points: *const RmVec3, normals: *const RmVec3, n_points: u32, n_lights: u32, mode: u32, lit: *mut u8) -> c_int;
+    fn rm_lights_visible_device(ctx: *mut RmCtx, device_points: *const c_void, device_normals: *const c_void, n_points: u32, n_lights: u32, mode: u32, device_lit: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -403,6 +423,28 @@ impl Gpu {
         } else {
             None
         }
+    }
+
+    /// Can `a` see `b` in `scene`?  Nothing may lie on the segment between `skin` and its length less `skin` -- the guard
+    /// against the surfaces the two points lie on (the render's own is 1e-3).
+    pub fn visible(&mut self, scene: &::scene::Scene, a: Vec3f, b: Vec3f, skin: f64) -> bool {
+        self.upload(scene);
+        let (from, to): (RmVec3, RmVec3) = (a.into(), b.into());
+        let mut seen: u8 = 0;
+        check(unsafe { rm_visible_segments(self.ctx, &from, &to, 1, skin, &mut seen) }, self.ctx);
+        seen != 0
+    }
+
+    /// Which of `scene.lights` reach the surface point `point` with normal `normal` (a `pick`'s, say): one bool per
+    /// light.  `clipped` false: the decision direct_lighting takes (renderer.rs:166-174), where a shape behind the light
+    /// shadows; true: the shadow ray ends at the light.
+    pub fn lit_by(&mut self, scene: &::scene::Scene, point: Vec3f, normal: Vec3f, clipped: bool) -> Vec<bool> {
+        self.upload(scene);
+        let (p, n): (RmVec3, RmVec3) = (point.into(), normal.into());
+        let mut lit = vec![0u8; scene.lights.len()];
+        let mode = if clipped { RM_LIGHTS_CLIPPED } else { RM_LIGHTS_AS_RENDERED };
+        check(unsafe { rm_lights_visible(self.ctx, &p, &n, 1, lit.len() as u32, mode, lit.as_mut_ptr()) }, self.ctx);
+        lit.iter().map(|&b| b != 0).collect()
     }
 
     /// The view direction of every later `render`, `render_display` and `pick`; None: the reference's fixed view
