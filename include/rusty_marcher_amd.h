@@ -641,6 +641,62 @@ rm_status rm_camera_basis_turn(const rm_camera_basis *in, double yaw, double pit
 /* RM_OK where rm_camera_orient would accept the basis. */
 rm_status rm_camera_basis_check(const rm_camera_basis *basis);
 
+/* ---- radiance queries: the caller's rays and sub-pixel samples, shaded ---------------------
+ * The queries above stop before shading.  These return what cast_ray (renderer.rs:254-309) returns
+ * along a ray: closest hit, direct lighting, reflected and refracted children -- for rays the caller
+ * names, and for real-valued sample positions of the frame `params` describes (anti-aliasing, a
+ * sparse second view).  Additive to ABI version 5; a host detects them by " radiance" in
+ * rm_build_info().  Everything "Semantics common to every query" says holds: the resident scene
+ * (RM_ERR_NO_SCENE without one), the strict numeric flavour whatever params->flags says
+ * (RM_FLAG_FAST_FP tolerated and ignored, no other flag), the default band only, device variants
+ * asynchronous on hip_stream and host variants blocking, n == 0 is RM_OK, no render state touched.
+ *
+ *   - Depth.  Every ray is cast as the render casts a primary ray, n_recursion = 1, with the cap
+ *     max_depth in place of the reference's 3.  A ray that leaves the scene returns exactly
+ *     (+0, +0, +0), not the background (renderer.rs:302-306); a child that leaves the scene adds its
+ *     weight times the background, and so does a child beyond the cap (renderer.rs:262-264).
+ *     max_depth == 0 returns the background for every ray; max_depth > RM_MAX_DEPTH is RM_ERR_DEPTH.
+ *   - Viewer direction.  direct_lighting's dir_to_viewer is normalize(origin - point)
+ *     (renderer.rs:149).  A caller's direction is unit length only within the reference's assert,
+ *     |d.d - 1| < 1e-4, and reflect() does not renormalise (optics.rs:4-6), so a reflected child
+ *     inherits its parent's length: the specular term takes -normalized(dir) at every ray step.
+ *     Everything else -- the intersection tests, the reflected and refracted children -- takes the
+ *     direction as it is, as the reference does.
+ *   - Shadow rays are walked without the per-primitive occluder masks of the render (they hold for
+ *     rays cast from near the scene; a ray list has no such bound).  The decisions are the same.
+ *   - Sample rays.  A sample (sx, sy), sx the real-valued column and sy the row, is the ray
+ *     backproject (renderer.rs:128-135) would form there: with params' Renderer
+ *         bx = 2 * (sx / width - 0.5) * half_fov * ratio
+ *         by = -2 * (sy / height - 0.5) * half_fov
+ *     every operation rounded once, in this order, with exact divisions -- for integer (sx, sy) the
+ *     numbers of the render's own pixel, bit for bit, and there is no pixel-centre offset.  The ray
+ *     leaves the context's camera position along normalized(bx, by, -1), or under an oriented
+ *     context along normalized((bx * right + by * up) + forward) as the camera section states it.
+ *     frame_width need not be a multiple of 32, and the frame_height % 32 rows the render leaves
+ *     untouched are answered too, as for rm_pick.  max_depth and background are params'.
+ *   - The host variants check everything before anything is launched: what the ray queries check
+ *     of origins and directions; shading != NULL and a finite background; samples finite with
+ *     0 <= sx < frame_width and 0 <= sy < frame_height.  RM_ERR_INVALID_ARG names the first offender
+ *     in rm_last_error, nothing is computed and the output is untouched.  For the device variants
+ *     the per-element conditions are preconditions: a bad element gets an unspecified answer for
+ *     that element, never a fault.
+ */
+typedef struct rm_shading {
+    rm_vec3  background;
+    uint32_t max_depth;
+    uint32_t _pad;
+} rm_shading;           /* 32 bytes */
+
+/* rgb[i] = cast_ray(origins[i], directions[i], scene.shapes, scene.lights, background, 1) with the cap max_depth. */
+rm_status rm_radiance_rays(rm_ctx *ctx, const rm_vec3 *origins, const rm_vec3 *directions, uint32_t n_rays,
+                           const rm_shading *shading, rm_vec3 *rgb);
+rm_status rm_radiance_rays_device(rm_ctx *ctx, const void *device_origins, const void *device_directions,
+                                  uint32_t n_rays, const rm_shading *shading, void *device_rgb, void *hip_stream);
+/* xy: n pairs (sx, sy) of real-valued pixel coordinates; rgb[i] the radiance along the ray of sample i. */
+rm_status rm_radiance_samples(rm_ctx *ctx, const rm_params *params, const double *xy, uint32_t n, rm_vec3 *rgb);
+rm_status rm_radiance_samples_device(rm_ctx *ctx, const rm_params *params, const void *device_xy, uint32_t n,
+                                     void *device_rgb, void *hip_stream);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

@@ -93,6 +93,11 @@ class rm_range(C.Structure):
     _fields_ = [("t_min", C.c_double), ("t_max", C.c_double)]
 
 
+class rm_shading(C.Structure):
+    """Background and depth cap of a radiance query over a ray list (32 bytes)."""
+    _fields_ = [("background", rm_vec3), ("max_depth", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class rm_camera_basis(C.Structure):
     """The oriented camera's view direction: three world-space unit vectors (72 bytes)."""
     _fields_ = [("right", rm_vec3), ("up", rm_vec3), ("forward", rm_vec3)]
@@ -175,6 +180,10 @@ SIGNATURES = {
     "rm_visible_segments_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_double, _VP, _VP]),
     "rm_lights_visible": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint8)]),
     "rm_lights_visible_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, _VP, _VP]),
+    "rm_radiance_rays": (C.c_int, [_VP, _P(rm_vec3), _P(rm_vec3), C.c_uint32, _P(rm_shading), _P(rm_vec3)]),
+    "rm_radiance_rays_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _P(rm_shading), _VP, _VP]),
+    "rm_radiance_samples": (C.c_int, [_VP, _P(rm_params), _P(C.c_double), C.c_uint32, _P(rm_vec3)]),
+    "rm_radiance_samples_device": (C.c_int, [_VP, _P(rm_params), _VP, C.c_uint32, _VP, _VP]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -45,6 +45,21 @@ def _pairs(a, b, names):
     return a, b
 
 
+def _samples(xy):
+    """(N, 2) float64 sample positions (sx = column, sy = row), C-contiguous."""
+    a = np.ascontiguousarray(xy, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("xy must be a float64 array of shape (N, 2), got %s" % (a.shape,))
+    return a
+
+
+def _shading(max_depth, background):
+    """rm_shading of a ray-list radiance call."""
+    if int(max_depth) != max_depth or max_depth < 0:
+        raise ValueError("max_depth must be a non-negative integer, got %r" % (max_depth,))
+    return _lib.rm_shading(_lib.vec3(background), int(max_depth), 0)
+
+
 def _device_hits(raw):
     """DeviceHits over a float64 tensor whose last dimension is one rm_hit (9 words)."""
     ints = raw.view(_torch().int32)                       # 18 int32 a record: shape, element, hit are 14, 15, 16
@@ -323,6 +338,54 @@ class Context:
                                                    _lib.RM_LIGHTS_CLIPPED if clipped else _lib.RM_LIGHTS_AS_RENDERED,
                                                    C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
         return out.view(torch.bool)
+
+    # ---- radiance queries (include/rusty_marcher_amd.h, "radiance queries") ----
+    def radiance(self, origins, directions, max_depth=3, background=(.1, .1, .1)):
+        """rm_radiance_rays: cast_ray (renderer.rs:254-309) along N rays of the caller's own, (N, 3) float64 origins and
+        unit directions -> (N, 3) float64 radiance.  A ray that leaves the scene returns exactly zero."""
+        o, d = _rays(origins, directions)
+        sh = _shading(max_depth, background)
+        out = np.zeros((o.shape[0], 3), dtype=np.float64)
+        V = C.POINTER(_lib.rm_vec3)
+        _lib.check(self.L.rm_radiance_rays(self.ptr, o.ctypes.data_as(V), d.ctypes.data_as(V), o.shape[0], C.byref(sh),
+                                           out.ctypes.data_as(V)), self.ptr)
+        return out
+
+    def radiance_device(self, origins, directions, max_depth=3, background=(.1, .1, .1), stream=None):
+        """radiance() on torch tensors of the context's device, asynchronous on `stream` (torch's current one by
+        default): an (N, 3) float64 tensor there."""
+        torch = _torch()
+        n = self._device_rays(origins, directions)
+        sh = _shading(max_depth, background)
+        out = torch.empty((n, 3), dtype=torch.float64, device=origins.device)
+        _lib.check(self.L.rm_radiance_rays_device(self.ptr, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
+                                                  C.byref(sh), C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return out
+
+    def radiance_samples(self, params, xy):
+        """rm_radiance_samples: the radiance at N real-valued positions (sx = column, sy = row) of the frame `params`
+        describes, from the context's camera; depth cap and background are params'.  (N, 2) float64 -> (N, 3) float64."""
+        a = _samples(xy)
+        out = np.zeros((a.shape[0], 3), dtype=np.float64)
+        _lib.check(self.L.rm_radiance_samples(self.ptr, C.byref(params), a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0],
+                                              out.ctypes.data_as(C.POINTER(_lib.rm_vec3))), self.ptr)
+        return out
+
+    def radiance_samples_device(self, params, xy, stream=None):
+        """radiance_samples() on a contiguous (N, 2) float64 torch tensor of the context's device, asynchronous on
+        `stream`: an (N, 3) float64 tensor there."""
+        torch = _torch()
+        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2:
+            raise ValueError("xy must be a float64 torch tensor of shape (N, 2)")
+        if xy.device.type != "cuda" or xy.device.index != self.device:
+            raise ValueError("xy must live on cuda:%d (the context's device), not %s" % (self.device, xy.device))
+        if not xy.is_contiguous():
+            raise ValueError("xy must be contiguous")
+        n = xy.shape[0]
+        out = torch.empty((n, 3), dtype=torch.float64, device=xy.device)
+        _lib.check(self.L.rm_radiance_samples_device(self.ptr, C.byref(params), C.c_void_p(xy.data_ptr()), n,
+                                                     C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return out
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

@@ -20,6 +20,7 @@
 #include "rm_kernel_args.hpp"
 #include "rm_plan.hpp"
 #include "rm_query.hpp"
+#include "rm_radiance.hpp"
 
 using namespace rmdev;
 
@@ -298,7 +299,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1485,3 +1486,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_exchange.inc"
 #include "rm_hostio.inc"
 #include "rm_query_host.inc"
+#include "rm_radiance_host.inc"

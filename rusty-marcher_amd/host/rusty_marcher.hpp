@@ -361,6 +361,30 @@ struct Renderer {
         check(rm_lights_visible(ctx_, &p, &n, 1, (uint32_t)lit.size(), clipped ? RM_LIGHTS_CLIPPED : RM_LIGHTS_AS_RENDERED, lit.data()), ctx_);
         return std::vector<bool>(lit.begin(), lit.end());
     }
+    // What comes back along rays of the caller's own in sc (rm_radiance_rays): cast_ray (renderer.rs:254-309) with this
+    // Renderer's max_depth and the render's background, one colour per ray.  Directions are unit vectors; a ray that leaves
+    // the scene returns zero, as a primary ray of the render does.
+    std::vector<Vec3f> radiance(const scene::Scene &sc, const std::vector<Vec3f> &origins, const std::vector<Vec3f> &directions) {
+        if (origins.size() != directions.size()) throw std::invalid_argument("radiance: origins and directions differ in length");
+        upload(sc);
+        std::vector<rm_vec3> o(origins.size()), d(origins.size()), rgb(origins.size());
+        for (size_t i = 0; i < origins.size(); i++) { o[i] = origins[i].c(); d[i] = directions[i].c(); }
+        const rm_shading shading{rm_vec3{0.1, 0.1, 0.1}, max_depth, 0u};                  // renderer.rs:40-44
+        check(rm_radiance_rays(ctx_, o.data(), d.data(), (uint32_t)o.size(), &shading, rgb.data()), ctx_);
+        std::vector<Vec3f> out(rgb.size());
+        for (size_t i = 0; i < rgb.size(); i++) out[i] = Vec3f{rgb[i].x, rgb[i].y, rgb[i].z};
+        return out;
+    }
+    // The radiance at real-valued positions (sx = column, sy = row; xy holds the pairs back to back) of the width x height
+    // frame render() would draw (rm_radiance_samples): sub-pixel samples; integer positions are the render's own pixels.
+    std::vector<Vec3f> radiance_samples(size_t width_px, size_t height_px, const scene::Scene &sc, const std::vector<double> &xy) {
+        const rm_params p = prepare(width_px, height_px, sc, false);
+        std::vector<rm_vec3> rgb(xy.size() / 2);
+        check(rm_radiance_samples(ctx_, &p, xy.data(), (uint32_t)rgb.size(), rgb.data()), ctx_);
+        std::vector<Vec3f> out(rgb.size());
+        for (size_t i = 0; i < rgb.size(); i++) out[i] = Vec3f{rgb[i].x, rgb[i].y, rgb[i].z};
+        return out;
+    }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
     void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }

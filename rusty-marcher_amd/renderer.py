@@ -47,6 +47,46 @@ class Renderer:
         print("%d compute units used" % info["cus"])                     # renderer.rs:124 prints the thread count
         return message
 
+    def render_supersampled(self, frame, scene, n):
+        """render() with n x n rays a pixel: pixel (x, y) is the mean of the radiance at (x + i/n, y + j/n), i, j in
+        0..n-1 -- no pixel-centre offset, so n = 1 casts the render's own ray.  One radiance query over sample positions
+        built on the device (rm_radiance_samples_device), averaged there in float64; the whole patch rows of
+        frame.buffer are filled, rows from height - height % 32 on are left untouched, as render() leaves them."""
+        if int(n) != n or not 1 <= n <= 8:
+            raise ValueError("n must be an integer in 1..8, got %r" % (n,))
+        n = int(n)
+        import torch
+        t0 = time.perf_counter()
+        ctx = backend.default_context(self.device)
+        if frame.height % 32 != 0 or frame.width % 32 != 0:
+            print("Dimensions mismatch")                                   # renderer.rs:49-51
+        rows = (frame.height // 32) * 32
+        print("Rendering using patches of size %d, using %d patches overall" % (32, (frame.height // 32) * (frame.width // 32)))
+
+        p = backend.make_params(self.fov, self.height, self.width, self.max_depth)
+        p.frame_width, p.frame_height = frame.width, frame.height
+        ctx.upload(scene.flatten())
+        ctx.orient(getattr(scene, "basis", None))
+        if rows:
+            dev = torch.device("cuda:%d" % self.device)
+            f64 = torch.float64
+            sub = torch.arange(n, dtype=f64, device=dev) / n               # i / n: one rounding, as the samples are defined
+            sx = (torch.arange(frame.width, dtype=f64, device=dev)[:, None] + sub[None, :])       # [x][i]
+            sy = (torch.arange(rows, dtype=f64, device=dev)[:, None] + sub[None, :])              # [y][j]
+            xy = torch.empty((rows, frame.width, n, n, 2), dtype=f64, device=dev)                 # [y][x][j][i]
+            xy[..., 0] = sx[None, :, None, :]
+            xy[..., 1] = sy[:, None, :, None]
+            rgb = ctx.radiance_samples_device(p, xy.view(-1, 2))
+            mean = rgb.view(rows, frame.width, n * n, 3).sum(dim=2) / float(n * n)
+            frame.buffer[:rows] = mean.cpu().numpy()
+
+        ms = int((time.perf_counter() - t0) * 1000.)
+        buf = C.create_string_buffer(256)
+        _lib.lib().rm_format_status(buf, 256, ms, frame.width, frame.height)
+        message = buf.value.decode()
+        print(message)
+        return message
+
     def pick(self, frame, scene, x, y):
         """What render(frame, scene) shows at pixel (x = column, y = row): the closest hit of the ray renderer.rs:80
         casts there (bit for bit the strict render's direction), or None where that ray leaves the scene."""

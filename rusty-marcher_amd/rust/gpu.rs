@@ -130,6 +130,15 @@ pub struct RmRange {
     pub t_max: f64,
 }
 
+/// `rm_shading`: background and depth cap of a radiance query over a ray list (32 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmShading {
+    pub background: RmVec3,
+    pub max_depth: u32,
+    pub _pad: u32,
+}
+
 /// `rm_lights_visible`'s modes: the decision direct_lighting takes / the shadow ray ended at the light.
 pub const RM_LIGHTS_AS_RENDERED: u32 = 0;
 pub const RM_LIGHTS_CLIPPED: u32 = 1;
@@ -226,6 +235,10 @@ extern "C" {
     fn rm_visible_segments_device(ctx: *mut RmCtx, device_from: *const c_void, device_to: *const c_void, n: u32, skin: f64, device_visible: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_lights_visible(ctx: *mut RmCtx, points: *const RmVec3, normals: *const RmVec3, n_points: u32, n_lights: u32, mode: u32, lit: *mut u8) -> c_int;
     fn rm_lights_visible_device(ctx: *mut RmCtx, device_points: *const c_void, device_normals: *const c_void, n_points: u32, n_lights: u32, mode: u32, device_lit: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_radiance_rays(ctx: *mut RmCtx, origins: *const RmVec3, directions: *const RmVec3, n_rays: u32, shading: *const RmShading, rgb: *mut RmVec3) -> c_int;
+    fn rm_radiance_rays_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, n_rays: u32, shading: *const RmShading, device_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_radiance_samples(ctx: *mut RmCtx, params: *const RmParams, xy: *const f64, n: u32, rgb: *mut RmVec3) -> c_int;
+    fn rm_radiance_samples_device(ctx: *mut RmCtx, params: *const RmParams, device_xy: *const c_void, n: u32, device_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -445,6 +458,46 @@ impl Gpu {
         let mode = if clipped { RM_LIGHTS_CLIPPED } else { RM_LIGHTS_AS_RENDERED };
         check(unsafe { rm_lights_visible(self.ctx, &p, &n, 1, lit.len() as u32, mode, lit.as_mut_ptr()) }, self.ctx);
         lit.iter().map(|&b| b != 0).collect()
+    }
+
+    /// What comes back along rays of the caller's own in `scene`: cast_ray (renderer.rs:254-309) with the depth cap
+    /// `max_depth` and the render's background, one colour per ray.  `rays`: (origin, unit direction) pairs.  A ray that
+    /// leaves the scene returns zero, as a primary ray of the render does.
+    pub fn radiance(&mut self, scene: &::scene::Scene, rays: &[(Vec3f, Vec3f)], max_depth: u32) -> Vec<Vec3f> {
+        self.upload(scene);
+        let origins: Vec<RmVec3> = rays.iter().map(|r| r.0.into()).collect();
+        let directions: Vec<RmVec3> = rays.iter().map(|r| r.1.into()).collect();
+        let shading = RmShading { background: RmVec3 { x: 0.1, y: 0.1, z: 0.1 }, max_depth: max_depth, _pad: 0 }; // renderer.rs:40-44
+        let mut rgb = vec![RmVec3 { x: 0., y: 0., z: 0. }; rays.len()];
+        check(
+            unsafe { rm_radiance_rays(self.ctx, origins.as_ptr(), directions.as_ptr(), rays.len() as u32, &shading, rgb.as_mut_ptr()) },
+            self.ctx,
+        );
+        rgb.iter().map(|c| Vec3f { x: c.x, y: c.y, z: c.z }).collect()
+    }
+
+    /// The radiance at real-valued positions (sx = column, sy = row) of the frame `render` would draw: sub-pixel samples
+    /// for anti-aliasing, a sparse view.  `xy` holds the pairs back to back; integer positions are the render's own pixels.
+    pub fn radiance_samples(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        scene: &::scene::Scene,
+        xy: &[f64],
+    ) -> Vec<Vec3f> {
+        self.upload(scene);
+        let mut p: RmParams = unsafe { ::std::mem::zeroed() };
+        unsafe { rm_create_renderer(fov, height, width, &mut p) };
+        p.frame_width = frame_width as u32;
+        p.frame_height = frame_height as u32;
+        p.max_depth = 3; // renderer.rs:262
+        let n = xy.len() / 2;
+        let mut rgb = vec![RmVec3 { x: 0., y: 0., z: 0. }; n];
+        check(unsafe { rm_radiance_samples(self.ctx, &p, xy.as_ptr(), n as u32, rgb.as_mut_ptr()) }, self.ctx);
+        rgb.iter().map(|c| Vec3f { x: c.x, y: c.y, z: c.z }).collect()
     }
 
     /// The view direction of every later `render`, `render_display` and `pick`; None: the reference's fixed view
