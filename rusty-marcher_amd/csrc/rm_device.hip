@@ -158,6 +158,7 @@ struct rm_ctx {
     bool integer_exponents = false;   // every material's specular_exponent is a small non-negative integer
     const rm_knobs knobs = rm_knobs_from_env();   // A/B knobs and test hooks: the environment as rm_init found it
     double occ_camera_limit = 0.;     // the resident image's: cameras farther out (L1 norm) render without its masks
+    double dead_camera_limit = 0.;    // ... and without its empty half-spaces (0: it has none)
     // checked numerics (rm_trace.inc RM_CHECKED): the resident image's verdict, the last render launch's, and the tiles the
     // context's launches rendered again because a lane's guard fired (device word, counted up by the kernels)
     bool scene_exact_only = false, last_launch_exact_only = false;
@@ -417,6 +418,8 @@ struct rm_image {
     std::vector<double> blob;
     std::vector<uint32_t> pid_map;
     double occ_camera_limit = 0.;      // |camera|_1 beyond which the render does not use the occluder masks
+    std::vector<unsigned char> empty_sides;   // per pid: the sides of its plane that hold nothing (rm_build_empty_sides; scenes of up to 64 pids)
+    double dead_camera_limit = 0.;     // |camera|_1 beyond which the render does not use them (0: no glass word carries any)
     bool exact_only = false;           // outside what the checked numerics are proven for (scene_exact_only)
 };
 
@@ -749,6 +752,35 @@ static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, 
     if (H.off_bvh_spheres) std::memcpy(&blob[H.off_bvh_spheres], bvh_s.nodes.data(), bvh_s.nodes.size() * sizeof(double));
     if (H.off_bvh_triangles) std::memcpy(&blob[H.off_bvh_triangles], bvh_t.nodes.data(), bvh_t.nodes.size() * sizeof(double));
 
+    // the camera beyond which neither table below is used (the hit points' rounding: 1e-7 of the scene's size
+    // is the builders' margin), from the coordinates they are built from
+    auto camera_limit = [&]() {
+        double size = 0.;
+        for (uint32_t q = 0; q < n_prims; q++) {
+            const double *w = &blob[H.off_bounds + 4u * q];
+            if (w[3] >= 0.) size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]) + w[3]);
+        }
+        for (uint32_t l = 0; l < H.n_lights; l++) {
+            const double *w = &blob[H.off_lights + RM_LIGHT_WORDS * l];
+            size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]));
+        }
+        return std::isfinite(size) ? 1e6 * (1. + size) : 0.;
+    };
+    // The planar primitives' empty half-spaces (rm_build_empty_sides) for the same scenes: a glass-like one carries them in
+    // its glass word, which every reader but the plain-walk kernels' render_tile tests for != 0 only.
+    if (n_prims > 0u && n_prims <= RM_SHADOW_MASK_MAX_PRIMS) {
+        img.empty_sides.assign(n_prims, 0);
+        rm_build_empty_sides(blob.data(), H, img.empty_sides.data());
+        bool any = false;
+        for (uint32_t q = 0; q < n_prims; q++) {
+            double &glass = blob[H.off_materials + RM_MATERIAL_WORDS * q + 8];
+            if (glass != 0. && img.empty_sides[q]) {
+                glass = 1. + ((img.empty_sides[q] & RM_EMPTY_SIDE_POS) ? 2. : 0.) + ((img.empty_sides[q] & RM_EMPTY_SIDE_NEG) ? 4. : 0.);
+                any = true;
+            }
+        }
+        if (any) img.dead_camera_limit = std::fmin(camera_limit(), RM_EMPTY_SIDES_CAMERA_MAX);
+    }
     // The shadow rays' occluder masks (rm_build_shadow_masks) for the plain-walk kernels' scenes, behind the
     // image the staged kernels copy (the walks read them with scalar loads): scenes of up to 64 pids.
     if (shadow_masks && n_prims > 0u && n_prims <= RM_SHADOW_MASK_MAX_PRIMS && H.n_lights > 0u) {
@@ -757,18 +789,7 @@ static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, 
             H.off_occ = H.total_words;
             blob.resize((size_t)H.total_words + ((words + 1u) & ~1ull), 0.);
             rm_build_shadow_masks(blob.data(), H, reinterpret_cast<unsigned long long *>(&blob[H.off_occ]));
-            // the camera beyond which the table is not used (the hit points' rounding: 1e-7 of the scene's size
-            // is the builder's margin), from the coordinates it was built from
-            double size = 0.;
-            for (uint32_t q = 0; q < n_prims; q++) {
-                const double *w = &blob[H.off_bounds + 4u * q];
-                if (w[3] >= 0.) size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]) + w[3]);
-            }
-            for (uint32_t l = 0; l < H.n_lights; l++) {
-                const double *w = &blob[H.off_lights + RM_LIGHT_WORDS * l];
-                size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]));
-            }
-            img.occ_camera_limit = std::isfinite(size) ? 1e6 * (1. + size) : 0.;
+            img.occ_camera_limit = camera_limit();
         }
     }
     img.exact_only = scene_exact_only(d);
@@ -855,6 +876,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     }
     ctx->H = H;
     ctx->occ_camera_limit = img.occ_camera_limit;
+    ctx->dead_camera_limit = img.dead_camera_limit;
     ctx->scene_exact_only = img.exact_only;
     ctx->camera = d->camera;
     ctx->have_scene = true;
@@ -889,6 +911,28 @@ extern "C" rm_status rmi_shadow_masks(const rm_scene_desc *d, uint64_t *occ, uin
     if (H.off_occ && occ && shape_of && (uint64_t)n * H.n_lights <= cap) {
         std::memcpy(occ, &img.blob[H.off_occ], (size_t)n * H.n_lights * sizeof(uint64_t));
         for (uint32_t q = 0; q < n; q++) shape_of[q] = img.pid_map[2u * q];
+    }
+    return RM_OK;
+}
+
+// Test hook, not part of the ABI (tests/test_dead_children.py): the empty half-spaces the upload of `d` finds.  dims[0] = pids,
+// dims[1] = 1 where there is a table; then, when there is and cap >= pids, sides[pid] (RM_EMPTY_SIDE_POS | RM_EMPTY_SIDE_NEG),
+// glass[pid] = the pid's glass word as the kernels read it, and shape_of[pid] = the pid's index into Scene.shapes;
+// *camera_limit = the camera beyond which a render does not use them.  Host work only: no device is needed.
+extern "C" rm_status rmi_empty_sides(const rm_scene_desc *d, uint8_t *sides, double *glass, uint32_t *shape_of, uint32_t cap, uint32_t *dims, double *camera_limit) {
+    if (!d || !dims) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rmi_empty_sides: NULL argument");
+    rm_image img;
+    if (rm_status st = build_image(nullptr, d, true, true, img)) return st;
+    const rm_dev_header &H = img.H;
+    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
+    dims[0] = n; dims[1] = img.empty_sides.empty() ? 0u : 1u;
+    if (camera_limit) *camera_limit = img.dead_camera_limit;
+    if (dims[1] && sides && glass && shape_of && n <= cap) {
+        for (uint32_t q = 0; q < n; q++) {
+            sides[q] = img.empty_sides[q];
+            glass[q] = img.blob[H.off_materials + RM_MATERIAL_WORDS * q + 8];
+            shape_of[q] = img.pid_map[2u * q];
+        }
     }
     return RM_OK;
 }
@@ -1085,7 +1129,7 @@ static rm_status void_frame_check(rm_ctx *ctx, const char *who) {
 
 static rm_plan_scene plan_scene_of(const rm_ctx *ctx) {
     return rm_plan_scene{&ctx->H, ctx->scene_epoch, ctx->occ_camera_limit, ctx->integer_exponents, ctx->oriented,
-                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, ctx->scene_exact_only};
+                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, ctx->scene_exact_only, ctx->dead_camera_limit};
 }
 
 static rm_status no_kernel(rm_ctx *ctx) { return ctx_fail(ctx, RM_ERR_INVALID_ARG, "render: no kernel for this scene / depth combination"); }

@@ -25,6 +25,8 @@ const char *rm_get_host_error();
 //   triangles 12 words each: nx ny nz  cx cy cz  v0x v0y v1x v1y v2x v2y
 //   materials 10 words per pid: diffusion dcx dcy dcz specular exponent
 //                               reflection refractive_index is_glass 1/refractive_index
+//                               (is_glass: 0, or 1 + 2 x empty(+) + 4 x empty(-) -- the sides of a glass-like
+//                               polygon's / triangle's plane that hold nothing, rm_build_empty_sides)
 //   lights    8 words each : px py pz  cx cy cz  intensity 0
 //   keys      1 u32 per pid (2 per word): position in Scene.shapes order, used
 //                               only to break exact distance ties (shapes.rs:130)
@@ -60,6 +62,16 @@ struct rm_dev_header {
 // occ[pid][light] from the image's bounds, lifted vertices, lights and shadow_rho (rm_scene.cpp)
 void rm_build_shadow_masks(const double *blob, const rm_dev_header &H, unsigned long long *occ);
 #define RM_SHADOW_MASK_MAX_PRIMS 64u
+
+// sides[pid]: bit 0 -- nothing of the scene lies on the side of the polygon's / triangle's plane its normal points to, bit 1 --
+// nothing on the other side (spheres, and anything in doubt: 0).  From the image's plane records, bounds, lifted vertices and
+// shadow_rho (rm_scene.cpp); scenes of up to RM_SHADOW_MASK_MAX_PRIMS pids.
+void rm_build_empty_sides(const double *blob, const rm_dev_header &H, unsigned char *sides);
+#define RM_EMPTY_SIDE_POS 1u
+#define RM_EMPTY_SIDE_NEG 2u
+// ... which the render reads only while the camera's L1 norm is at most this (a hit point then rounds far below the 1e-4 by
+// which a child ray starts off its surface)
+#define RM_EMPTY_SIDES_CAMERA_MAX 1e9
 
 #define RM_SPHERE_WORDS 4u
 #define RM_POLYGON_WORDS 16u   /* normal, plane point, (first vertex | count), pad, x/y of the first four vertices */

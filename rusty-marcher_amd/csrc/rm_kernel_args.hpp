@@ -188,7 +188,9 @@ struct KernelArgs {
     // is rendered by the exact twin (a scene or a camera outside what the range-free sequences are proven for, or
     // RM_CHECKED_NUMERICS=0); redo_count -- the context's count of tiles rendered again because a lane's guard fired.
     uint32_t exact_only;
-    uint32_t _pad_checked;
+    // != 0 (plain-walk kernels only): a child ray that leaves a polygon / triangle into a half-space its glass word says is
+    // empty (rm_internal.h, rm_build_empty_sides) is not walked -- the lane adds weight x background at once (render_tile)
+    uint32_t dead_children;
     uint32_t *redo_count;
 };
 

@@ -51,6 +51,7 @@ const knob k_knobs[] = {
     {"RM_FORCE_FAST_FP", &rm_knobs::force_fast_fp, IS_1},
     {"RM_FORCE_UNSTAGED", &rm_knobs::force_unstaged, IS_1},
     {"RM_SHADOW_MASKS", &rm_knobs::shadow_masks, NOT_0},
+    {"RM_DEAD_CHILDREN", &rm_knobs::dead_children, NOT_0},
     {"RM_DISABLE_BVH", &rm_knobs::disable_bvh, IS_1},
     {"RM_FORCE_STACK", &rm_knobs::force_stack, ATOI},
     {"RM_FEEDBACK", &rm_knobs::feedback_mode, ONE_OR_ZERO},
@@ -263,6 +264,11 @@ bool plan_launch(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p
     if (!choose_kernel(kn, sc, p, a.n_tiles, &P.k)) return false;
     const rm_kernel_choice &k = P.k;
     const uint32_t n_prims = k.n_prims, n_planar = k.n_planar;
+    // children that leave a planar primitive into an empty half-space are not walked (render_tile): the plain-walk kernels
+    // only, and -- like the occluder masks -- only while the camera is near enough for its hit points to round far below
+    // the offset such a child starts with
+    a.dead_children = (kn.dead_children && !k.bvh && !k.cull && sc.dead_camera_limit > 0. &&
+                       std::fabs(sc.camera.x) + std::fabs(sc.camera.y) + std::fabs(sc.camera.z) <= sc.dead_camera_limit) ? 1u : 0u;
     // A cull step handles 64 primitives for ~25 vector instructions, ~110 when it holds planar
     // primitives and the edge test runs; a bundle pays for every step.  The hierarchy walk finds a
     // bundle's few primitives in a few hundred instructions whatever their number, so scenes whose
@@ -619,6 +625,31 @@ extern "C" rm_status rmi_plan_launches(const rmi_plan_case *cases, uint32_t n, r
         if (P.ordered) order_cap = P.order_cap;
         if (P.feedback) fb = P.feedback_after;
     }
+    return RM_OK;
+}
+
+// Test hook, not part of the ABI (tests/test_dead_children.py): what a launch of a scene of these counts whose upload found
+// empty half-spaces up to `dead_camera_limit` carries with this camera, with the knobs as the environment has them now --
+// out[0] = KernelArgs::dead_children, out[1] = 1 where the kernel is a plain-walk one.  No device is needed.
+extern "C" rm_status rmi_plan_dead_children(const rm_vec3 *camera, double dead_camera_limit, uint32_t n_spheres, uint32_t n_polygons,
+                                            uint32_t n_triangles, uint32_t total_words, uint32_t *out) {
+    if (!camera || !out) { rm_set_host_error("rmi_plan_dead_children: NULL argument"); return RM_ERR_INVALID_ARG; }
+    const rm_knobs kn = rm_knobs_from_env();
+    rm_dev_header H{};
+    H.n_spheres = n_spheres; H.n_polygons = n_polygons; H.n_triangles = n_triangles; H.total_words = total_words;
+    const rm_camera_basis basis{rm_vec3{1., 0., 0.}, rm_vec3{0., 1., 0.}, rm_vec3{0., 0., -1.}};
+    const rm_plan_scene sc{&H, 1u, 0., true, false, *camera, &basis, 256u, false, dead_camera_limit};
+    rm_params p{};
+    p.half_fov = 0.75; p.height = 64.; p.width = 64.; p.ratio = 1.;
+    p.frame_width = 64; p.frame_height = 64; p.max_depth = 3;
+    rm_band band;
+    rm_launch_plan P;
+    if (!rm_band_of(p, &band) || !plan_launch(kn, sc, p, band, rm_stream_state{}, 0u, rm_feedback_state{}, 0ull, &P)) {
+        rm_set_host_error("rmi_plan_dead_children: no plan");
+        return RM_ERR_INVALID_ARG;
+    }
+    out[0] = P.args.dead_children;
+    out[1] = (!P.k.bvh && !P.k.cull) ? 1u : 0u;
     return RM_OK;
 }
 

@@ -43,6 +43,9 @@ struct rm_knobs {
     // The shadow rays' occluder masks of the plain-walk kernels (rm_build_shadow_masks): RM_SHADOW_MASKS=0 uploads no
     // table, and every shadow walk tests every primitive
     bool shadow_masks = true;
+    // Children of a glass-like polygon / triangle that leave it into an empty half-space (rm_build_empty_sides) are not
+    // walked by the plain-walk kernels: RM_DEAD_CHILDREN=0 walks them all the same (the A/B switch; frames are bit-equal)
+    bool dead_children = true;
     int force_stack = 0;              // RM_FORCE_STACK=4|8|16|32: a deeper ray stack than the depth cap needs
     bool debug_empty = false;         // RM_DEBUG_EMPTY=1: measure the dispatch floor of a launch geometry
     // frame-to-frame feedback (rm_feedback): RM_FEEDBACK=0 never, 1 always, unset: launches of
@@ -109,6 +112,7 @@ struct rm_plan_scene {
     const rm_camera_basis *basis;     // (the fixed view's own while the oriented state is off)
     uint32_t n_cus;
     bool exact_only = false;          // the resident scene is outside what the checked numerics are proven for (rm_device.hip scene_exact_only)
+    double dead_camera_limit = 0.;    // cameras farther out (L1 norm) walk every child ray (0: the image has no empty half-space, rm_build_empty_sides)
 };
 
 // Checked numerics (rm_trace.inc RM_CHECKED): a coordinate, radius, camera or light word is inside the proven range when it is

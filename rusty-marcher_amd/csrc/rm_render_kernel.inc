@@ -101,6 +101,10 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
     // (Culling only the tile's primary bundle in that kernel -- 40 % of its tiles see nothing but
     // sky -- was measured too: 85.9 against 83.9 us; a cull step costs what it saves there.)
     constexpr bool HANDOVER = CULL;
+    // Children that leave a glass-like polygon / triangle into an empty half-space (rm_scene.cpp rm_build_empty_sides; the
+    // launch plan says whether the image's flags hold for this camera) are not walked: per-lane kernels only -- the others
+    // form one fused term per step, and the sum would round differently.
+    const bool dead_children = DIV && own_sgpr(a.dead_children) != 0u;   // wave-uniform
     uint32_t step = 0;
     for (;; step++) {                                          // one ray step; the loop itself is wave-uniform
         // Critical-path scheduling: a launch ends with its deepest tiles (8 steps where the mean
@@ -138,14 +142,32 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
                 if (where<DIV>(glass)) {
                     const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];   // (1 / ri: the upload's division, rm_device.hip put_material)
                     V3 ro, rd, to, td;
-                    const bool has_r = glass & reflect_child<DIV>(dir, s, ri, inv_ri, ro, rd);   // renderer.rs:195-222
-                    const bool has_t = glass & refract_child(dir, s, ri, inv_ri, glass, to, td RM_SUS_ARG);   // renderer.rs:225-252
+                    double dn_r, dn_t;                          // rd . normal, td . normal: the dots the children's origins were offset by
+                    const bool has_r = glass & reflect_child<DIV>(dir, s, ri, inv_ri, ro, rd, dn_r);   // renderer.rs:195-222
+                    const bool has_t = glass & refract_child(dir, s, ri, inv_ri, glass, to, td, dn_t RM_SUS_ARG);   // renderer.rs:225-252
                     const double wr = weight * reflection, wt = weight * (1. - reflection);
                     // a child beyond the cap returns the background (renderer.rs:262-264)
                     const bool capped = depth + 1u > max_depth;
                     w_cap = ((capped & has_r) ? wr : 0.) + ((capped & has_t) ? wt : 0.);
                     if (DIV && capped) acc = acc + scaled(bg, w_cap);
-                    const bool live_r = has_r & !capped, live_t = has_t & !capped;
+                    bool live_r = has_r & !capped, live_t = has_t & !capped;
+                    if (DIV && dead_children) {
+                        // A child starts on the side of the surface its direction points to (optics.rs:41-45, :82-86): where
+                        // the glass word (1 + 2 x empty(+) + 4 x empty(-)) says that side of the plane holds nothing, its step
+                        // would find no hit -- the plane's own test rejects it on the sign of the dot its origin was offset by -- and add
+                        // weight x background: added here, in its place (a term of its own: 0. + w is not always w), and the
+                        // ray is dropped.  d . normal == 0 leaves it alive.  The order of the pixel's terms stays what it was:
+                        // the refracted child is walked first, and the reflected one is dropped only where it would be next.
+                        const uint32_t sides = (uint32_t)s.mat[8];
+                        const bool dead_t = live_t & (((dn_t > 0.) & ((sides & 2u) != 0u)) | ((dn_t < 0.) & ((sides & 4u) != 0u)));
+                        if (dead_t) acc = acc + scaled(bg, wt);
+                        live_t = live_t & !dead_t;
+                        if (live_r & !live_t) {
+                            const bool dead_r = ((dn_r > 0.) & ((sides & 2u) != 0u)) | ((dn_r < 0.) & ((sides & 4u) != 0u));
+                            if (dead_r) acc = acc + scaled(bg, wr);
+                            live_r = live_r & !dead_r;
+                        }
+                    }
                     // both children: park the reflected sibling (the stores are per-lane branches)
                     const bool park = live_r & live_t, park_l0 = park & (n_deep == 0u) & !l0_full;
                     if (park_l0) {

@@ -617,6 +617,67 @@ void rm_build_shadow_masks(const double *blob, const rm_dev_header &H, unsigned 
     }
 }
 
+// ---- empty half-spaces of the planar primitives (rm_internal.h: the glass word; rm_render_kernel.inc render_tile) --------
+// A child ray of a hit on a polygon or triangle P (optics.rs:8-89) starts 1e-4 of P's normal off the hit point, on the side
+// its direction d points to (:41-45, :82-86: the side sign(d . normal)), and never comes back to P's plane.  Where every other
+// primitive lies strictly on the OTHER side of that plane such a ray can hit nothing: not P -- its test rejects a ray that
+// runs away from its plane on the sign of the very same dot product -- and nothing else.  The kernel then adds what the
+// ray's own step would have added, weight x background, and does not walk it.
+// sides[P] bit 0: the side P's normal points to is empty, bit 1: the other one.  A primitive Q is on the other side when its
+// lifted vertices (the hull of its hit points) all are, or its bounding sphere is, by
+//   1e-4 + shadow_rho + 1e-7 x (1 + the coordinates' magnitudes)
+// -- the scale of the occluder masks' margins, far beyond the rounding of a hit point.  Anything that is not a finite number,
+// a normal that is not unit to 1e-6, a coordinate of 1e6 and more (the hit points' rounding must stay far below the 1e-4
+// offset) leaves both bits clear.  Primitives that can never be hit (radius -1) are ignored and get no bits themselves.
+void rm_build_empty_sides(const double *blob, const rm_dev_header &H, unsigned char *sides) {
+    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
+    const double rho = H.shadow_rho, big = 1e6;
+    auto finite3 = [](rm_vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+    auto mag = [](rm_vec3 v) { return std::fabs(v.x) + std::fabs(v.y) + std::fabs(v.z); };
+    for (uint32_t P = 0; P < n; P++) sides[P] = 0;
+    if (!(rho >= 0.) || !std::isfinite(rho)) return;
+    for (uint32_t P = H.n_spheres; P < n; P++) {
+        const double *rec = P < H.n_spheres + H.n_polygons ? blob + H.off_polygons + RM_POLYGON_WORDS * (P - H.n_spheres)
+                                                           : blob + H.off_triangles + RM_TRIANGLE_WORDS * (P - H.n_spheres - H.n_polygons);
+        const rm_vec3 nrm = v3(rec[0], rec[1], rec[2]), pp = v3(rec[3], rec[4], rec[5]);
+        const double *bp = blob + H.off_bounds + 4u * P;
+        const rm_vec3 c = v3(bp[0], bp[1], bp[2]);
+        if (!(bp[3] >= 0.) || !std::isfinite(bp[3]) || !finite3(c) || !finite3(nrm) || !finite3(pp)) continue;
+        if (!(std::fabs(std::sqrt(dot(nrm, nrm)) - 1.) <= 1e-6)) continue;
+        if (!(mag(c) + bp[3] < big) || !(mag(pp) < big)) continue;
+        bool pos = true, neg = true;                                  // the side the normal points to / the other one is empty
+        for (uint32_t Q = 0; Q < n && (pos || neg); Q++) {
+            if (Q == P) continue;
+            const double *bq = blob + H.off_bounds + 4u * Q;
+            if (bq[3] < 0.) continue;                                 // never hit
+            const rm_vec3 cq = v3(bq[0], bq[1], bq[2]);
+            if (!std::isfinite(bq[3]) || !finite3(cq) || !(mag(cq) + bq[3] < big)) { pos = neg = false; break; }
+            // by its bounding sphere
+            const double marg = 1e-4 + rho + 1e-7 * (1. + mag(pp) + mag(cq) + bq[3]);
+            const double h = dot(cq - pp, nrm);
+            bool below = h + bq[3] < -marg, above = h - bq[3] > marg;
+            // ... or by its lifted vertices, all of them
+            if (!below && !above && Q >= H.n_spheres) {
+                const double *pl = blob + H.off_planar + 16u * (Q - H.n_spheres);
+                const uint32_t nv = pl[12] == 3. ? 3u : pl[12] == 4. ? 4u : 0u;   // 0: no lifted vertices
+                bool lo = nv != 0u, hi = nv != 0u;
+                for (uint32_t i = 0; i < nv; i++) {
+                    const rm_vec3 w = v3(pl[3 * i], pl[3 * i + 1], pl[3 * i + 2]);
+                    if (!finite3(w) || !(mag(w) < big)) { lo = hi = false; break; }
+                    const double mw = 1e-4 + rho + 1e-7 * (1. + mag(pp) + mag(w));
+                    const double hw = dot(w - pp, nrm);
+                    lo = lo && hw < -mw;
+                    hi = hi && hw > mw;
+                }
+                below = lo; above = hi;
+            }
+            pos = pos && below;
+            neg = neg && above;
+        }
+        sides[P] = (unsigned char)((pos ? RM_EMPTY_SIDE_POS : 0u) | (neg ? RM_EMPTY_SIDE_NEG : 0u));
+    }
+}
+
 // ---- the oriented camera's host arithmetic (include/rusty_marcher_amd.h, "the oriented camera") ----------------
 // No device, no context: the CPU tests and every binding reach these.
 namespace {

@@ -1343,20 +1343,29 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
 // reflect(i, -n) == reflect(i, n) bit for bit, and c enters only squared.
 // LAZY (per-lane kernels): the reflected ray exists under total reflection only -- no lane of
 // most waves has one -- and is computed under that branch.
+// `dn`: d . normal, the dot that decides the side of the surface the child starts on (where the child was computed; else 0).
 template <bool LAZY>
-__device__ __forceinline__ bool reflect_child(V3 incident, const Surface &s, double ri, double inv_ri, V3 &o, V3 &d) {
+__device__ __forceinline__ bool reflect_child(V3 incident, const Surface &s, double ri, double inv_ri, V3 &o, V3 &d, double &dn) {
     const double c = dot(s.normal, incident);                         // optics.rs:16 (no sign flip)
     const double r = (c < 0.) ? ri : inv_ri;
     const double cos_theta_2 = 1. - r * r * (1. - c * c);
     const bool has = !(cos_theta_2 > 0.);                             // :33-35
+    dn = 0.;
     if (!LAZY || has) {
         d = reflect(incident, s.normal);
-        o = s.point + scaled(s.normal, (dot(d, s.normal) < 0.) ? -1e-4 : 1e-4);   // :41-45, un-flipped normal
+        dn = dot(d, s.normal);
+        o = s.point + scaled(s.normal, (dn < 0.) ? -1e-4 : 1e-4);     // :41-45, un-flipped normal
     }
     return has;
 }
+template <bool LAZY>
+__device__ __forceinline__ bool reflect_child(V3 incident, const Surface &s, double ri, double inv_ri, V3 &o, V3 &d) {
+    double dn;
+    return reflect_child<LAZY>(incident, s, ri, inv_ri, o, d, dn);
+}
 
-__device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, double ri, double inv_ri, bool glass, V3 &o, V3 &d RM_SUS_PARAM) {
+// `dn`: d . normal (the un-flipped normal), the dot that decides the side of the surface the child starts on.
+__device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, double ri, double inv_ri, bool glass, V3 &o, V3 &d, double &dn RM_SUS_PARAM) {
     (void)glass;
     const double c0 = -dot(s.normal, incident);                       // optics.rs:57
     const bool flip = c0 < 0.;                                        // :60-68: then c = -c, normal = -normal
@@ -1366,10 +1375,14 @@ __device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, dou
     const double k = r * c - __builtin_sqrt(cos_theta_2);
     // (under total reflection k is NaN and there is no such ray: its lanes' flags do not count)
     d = RM_NORMALIZED(scaled(incident, r) + scaled(s.normal, flip ? -k : k), glass & !(cos_theta_2 < 0.));   // :78-79 (flipped normal * k)
-    const double dn = dot(d, s.normal);                               // d . flipped normal = -(d . normal) when flipped
+    dn = dot(d, s.normal);                                            // d . flipped normal = -(d . normal) when flipped
     const bool along = flip ? (dn < 0.) : (dn > 0.);                  // :82 `dir.dot(normal) > 0` with the flipped normal
     o = s.point + scaled(s.normal, (along != flip) ? 1e-4 : -1e-4);   // :82-86: point +- flipped normal * 1e-4
     return !(cos_theta_2 < 0.);                                       // :74
+}
+__device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, double ri, double inv_ri, bool glass, V3 &o, V3 &d RM_SUS_PARAM) {
+    double dn;
+    return refract_child(incident, s, ri, inv_ri, glass, o, d, dn RM_SUS_ARG);
 }
 
 }  // namespace RM_FLAVOR_NS
