@@ -697,6 +697,67 @@ rm_status rm_radiance_samples(rm_ctx *ctx, const rm_params *params, const double
 rm_status rm_radiance_samples_device(rm_ctx *ctx, const rm_params *params, const void *device_xy, uint32_t n,
                                      void *device_rgb, void *hip_stream);
 
+/* ---- adaptive anti-aliasing: refine only the high-contrast pixels of a rendered frame --------
+ * A render casts one ray a pixel; these calls find the pixels that differ strongly from a neighbour
+ * and replace those alone by the mean of n x n radiance samples, on the device, in place.  Additive
+ * to ABI version 5; a host detects them by " antialias" in rm_build_info().
+ *
+ * Let rows = frame_height - frame_height % 32, the rows a render writes, and f the frame
+ * rm_render_device wrote for `params`: [frame_height][frame_width][3] doubles, the plain layout (no
+ * compact flag), the default band.
+ *
+ *   - Contrast.  The contrast of pixel (x, y), y < rows, is the largest |f[y][x][c] - f[q][c]| over
+ *     the three channels c and over its up-to-four neighbours q (left, right, above, below) that lie
+ *     in [0, frame_width) x [0, rows): row rows - 1 never looks at row rows, and a pixel without a
+ *     neighbour has contrast 0.  It is taken on the radiance as rendered, neither normalised nor
+ *     clamped; a NaN makes its comparisons false.
+ *   - Mask.  A pixel is refined iff its contrast is > threshold.  threshold = +inf refines nothing,
+ *     a negative threshold every pixel of [0, rows).  The mask is the unrefined frame's for every
+ *     pixel: it is complete before any pixel is overwritten.
+ *   - Refined value.  The mean of the radiance at (x + i/n, y + j/n), i, j in 0..n-1.  Each sample
+ *     is what rm_radiance_samples returns for that position with the same params: the "sample rays"
+ *     rule above (the oriented context's where the context is oriented), the strict flavour,
+ *     params' max_depth and background, occluder masks off.  The samples are summed per channel in
+ *     the order j outer, i inner, by plain additions, and the sum is divided once by (double)(n*n).
+ *     All n*n samples are cast, the one at i = j = 0 included: a frame refined with a negative
+ *     threshold is the supersampled frame.
+ *   - Unrefined pixels keep the bytes the render wrote; rows from `rows` on are not touched.
+ *
+ * rm_refine_device is asynchronous on hip_stream: no host synchronisation, nothing copied back.
+ * After it the first uint32_t of the workspace holds the number of refined pixels and their indices
+ * y * frame_width + x follow, in no particular order -- the list is an output.  device_mask, where
+ * given, gets 1 or 0 for every pixel of [0, rows) and is untouched below.  Everything "Semantics
+ * common to every query" says holds: the resident scene (RM_ERR_NO_SCENE without one),
+ * RM_FLAG_FAST_FP tolerated and ignored and any other flag RM_ERR_INVALID_ARG, the default band
+ * only, no render state touched; frame_width % 32 != 0 is RM_ERR_DIMENSIONS and max_depth >
+ * RM_MAX_DEPTH is RM_ERR_DEPTH.  n outside 1..8, a NaN threshold, a non-finite background, or a
+ * NULL refine, frame or workspace is RM_ERR_INVALID_ARG with the offender named in rm_last_error;
+ * nothing is launched then.  rows == 0 is RM_OK and does nothing.  All state lives in the
+ * workspace: two calls with different workspaces may be in flight on different streams.
+ *
+ * rm_render_antialiased is what a host calls for an anti-aliased frame: it renders exactly as
+ * rm_render does with params (the render state advances as a render's does), refines the context's
+ * resident frame on the context's stream with a workspace the context owns (grown on demand, freed
+ * by rm_destroy), copies the rows [0, rows) to host_rgb and the count to n_refined, and blocks.
+ * Compact flags or a non-default band are RM_ERR_INVALID_ARG.  timing->kernel_ms covers render plus
+ * refine.
+ */
+typedef struct rm_refine {
+    uint32_t n;           /* n x n samples a refined pixel, 1..8 */
+    uint32_t _pad;
+    double   threshold;   /* a pixel is refined iff its contrast is > threshold */
+} rm_refine;            /* 16 bytes */
+
+/* bytes of device memory rm_refine_device needs for `params`: 4 * (1 + rows * frame_width), rounded up to 256 */
+rm_status rm_refine_workspace(const rm_params *params, size_t *bytes);
+/* refines, in place, a frame rm_render_device wrote with the same params, camera and scene */
+rm_status rm_refine_device(rm_ctx *ctx, const rm_params *params, const rm_refine *refine, void *device_rgb,
+                           void *device_workspace, void *device_mask /* optional: [frame_height][frame_width] bytes */,
+                           void *hip_stream);
+/* rm_render + refine + copy */
+rm_status rm_render_antialiased(rm_ctx *ctx, const rm_params *params, const rm_refine *refine, double *host_rgb,
+                                uint32_t *n_refined /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

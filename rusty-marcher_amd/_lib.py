@@ -98,6 +98,11 @@ class rm_shading(C.Structure):
     _fields_ = [("background", rm_vec3), ("max_depth", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class rm_refine(C.Structure):
+    """What an adaptive anti-aliasing call refines: n x n samples for every pixel whose contrast is > threshold (16 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("_pad", C.c_uint32), ("threshold", C.c_double)]
+
+
 class rm_camera_basis(C.Structure):
     """The oriented camera's view direction: three world-space unit vectors (72 bytes)."""
     _fields_ = [("right", rm_vec3), ("up", rm_vec3), ("forward", rm_vec3)]
@@ -184,6 +189,9 @@ SIGNATURES = {
     "rm_radiance_rays_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _P(rm_shading), _VP, _VP]),
     "rm_radiance_samples": (C.c_int, [_VP, _P(rm_params), _P(C.c_double), C.c_uint32, _P(rm_vec3)]),
     "rm_radiance_samples_device": (C.c_int, [_VP, _P(rm_params), _VP, C.c_uint32, _VP, _VP]),
+    "rm_refine_workspace": (C.c_int, [_P(rm_params), _P(C.c_size_t)]),
+    "rm_refine_device": (C.c_int, [_VP, _P(rm_params), _P(rm_refine), _VP, _VP, _VP, _VP]),
+    "rm_render_antialiased": (C.c_int, [_VP, _P(rm_params), _P(rm_refine), _P(C.c_double), _P(C.c_uint32), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -60,6 +60,16 @@ def _shading(max_depth, background):
     return _lib.rm_shading(_lib.vec3(background), int(max_depth), 0)
 
 
+def _refine(n, threshold):
+    """rm_refine of an adaptive anti-aliasing call: n an integer in 1..8, threshold any number but NaN."""
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= 8:
+        raise ValueError("n must be an integer in 1..8, got %r" % (n,))
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold must not be NaN")
+    return _lib.rm_refine(int(n), 0, threshold)
+
+
 def _device_hits(raw):
     """DeviceHits over a float64 tensor whose last dimension is one rm_hit (9 words)."""
     ints = raw.view(_torch().int32)                       # 18 int32 a record: shape, element, hit are 14, 15, 16
@@ -386,6 +396,44 @@ class Context:
         _lib.check(self.L.rm_radiance_samples_device(self.ptr, C.byref(params), C.c_void_p(xy.data_ptr()), n,
                                                      C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
         return out
+
+    # ---- adaptive anti-aliasing (include/rusty_marcher_amd.h, "adaptive anti-aliasing") ----
+    def refine_workspace(self, params):
+        """rm_refine_workspace: bytes of device memory refine_device needs for `params`."""
+        b = C.c_size_t(0)
+        _lib.check(self.L.rm_refine_workspace(C.byref(params), C.byref(b)), None)
+        return b.value
+
+    def refine_device(self, params, frame_tensor, n, threshold, mask=None, stream=None):
+        """rm_refine_device: refines in place the frame render_device wrote into `frame_tensor` -- a contiguous float64
+        tensor of shape (frame_height, frame_width, 3) on the context's device -- with n x n samples for every pixel whose
+        contrast is > threshold; asynchronous on `stream` (torch's current one by default).  mask: optionally a contiguous
+        uint8 tensor (frame_height, frame_width) there, which gets 1 / 0 per pixel of the whole patch rows.  -> the workspace,
+        an int32 tensor: ws[0] is the number of refined pixels, ws[1:1 + ws[0]] their indices y * frame_width + x."""
+        torch = _torch()
+        r = _refine(n, threshold)
+        h, w = params.frame_height, params.frame_width
+        for name, t, dtype, shape in (("frame_tensor", frame_tensor, torch.float64, (h, w, 3)), ("mask", mask, torch.uint8, (h, w))):
+            if t is None and name == "mask":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, shape))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
+        ws = torch.empty((self.refine_workspace(params) // 4,), dtype=torch.int32, device=frame_tensor.device)
+        _lib.check(self.L.rm_refine_device(self.ptr, C.byref(params), C.byref(r), C.c_void_p(frame_tensor.data_ptr()),
+                                           C.c_void_p(ws.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                           C.c_void_p(self._stream(stream))), self.ptr)
+        return ws
+
+    def render_antialiased(self, params, host_array, n, threshold):
+        """rm_render_antialiased: render(), then n x n samples for every pixel whose contrast is > threshold, then the copy
+        into host_array.  -> (rm_timing, number of refined pixels)."""
+        r = _refine(n, threshold)
+        t, count = _lib.rm_timing(), C.c_uint32(0)
+        ptr = host_array.ctypes.data_as(C.POINTER(C.c_double)) if host_array is not None else None
+        _lib.check(self.L.rm_render_antialiased(self.ptr, C.byref(params), C.byref(r), ptr, C.byref(count), C.byref(t)), self.ptr)
+        return t, count.value
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

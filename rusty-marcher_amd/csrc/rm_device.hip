@@ -13,6 +13,7 @@
 #include <limits>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rm_bvh.hpp"
@@ -21,6 +22,7 @@
 #include "rm_plan.hpp"
 #include "rm_query.hpp"
 #include "rm_radiance.hpp"
+#include "rm_refine.hpp"
 
 using namespace rmdev;
 
@@ -205,6 +207,12 @@ struct rm_ctx {
     void *d_query = nullptr;
     size_t query_bytes = 0;
 
+    // adaptive anti-aliasing (rm_refine_host.inc): the workspace of rm_render_antialiased (grown on demand), and what
+    // hipOccupancyMaxActiveBlocksPerMultiprocessor said of the shade kernels launched so far
+    void *d_refine_ws = nullptr;
+    size_t refine_ws_bytes = 0;
+    std::vector<std::pair<const void *, int>> refine_occupancy;
+
     // post-process scratch
     unsigned long long *d_max = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -300,7 +308,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -375,6 +383,7 @@ void rm_destroy(rm_ctx *ctx) {
         if (ctx->d_backproject) (void)hipFree(ctx->d_backproject);
         if (ctx->d_pid_map) (void)hipFree(ctx->d_pid_map);
         if (ctx->d_query) (void)hipFree(ctx->d_query);
+        if (ctx->d_refine_ws) (void)hipFree(ctx->d_refine_ws);
         if (ctx->d_max) (void)hipFree(ctx->d_max);
         if (ctx->d_redo) (void)hipFree(ctx->d_redo);
         if (ctx->d_rgb8) (void)hipFree(ctx->d_rgb8);
@@ -1531,3 +1540,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_hostio.inc"
 #include "rm_query_host.inc"
 #include "rm_radiance_host.inc"
+#include "rm_refine_host.inc"

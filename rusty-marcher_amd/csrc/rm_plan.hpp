@@ -88,6 +88,7 @@ struct rm_knobs {
     // RM_CHECKED_NUMERICS=0: every launch of the strict plain-walk kernels is exact only -- the compiler's own square roots and
     // divisions throughout (the A/B switch, and what the bit-equality tests compare with)
     bool checked_numerics = true;
+    uint32_t refine_max_blocks = 0;      // RM_REFINE_MAX_BLOCKS=n: at most n workgroups shade the pixels an anti-aliased frame refines, each then loops over more groups (unset / 0: what the device holds at once; results do not change)
     bool debug_tail = false;             // RM_DEBUG_TAIL (set at all): every ordered launch is waited for and its order dumped to stderr; no launch is frozen
 };
 rm_knobs rm_knobs_from_env();

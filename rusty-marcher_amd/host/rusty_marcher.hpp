@@ -299,6 +299,7 @@ struct Renderer {
     uint32_t max_depth = 3;        // renderer.rs:262, exposed
     uint32_t flags = RM_FLAG_NONE;
     rm_timing last_timing{};
+    uint32_t last_refined = 0;     // render_antialiased: pixels it refined
 
     ~Renderer() { rm_destroy(ctx_); }
     Renderer(const Renderer &) = delete;
@@ -384,6 +385,23 @@ struct Renderer {
         std::vector<Vec3f> out(rgb.size());
         for (size_t i = 0; i < rgb.size(); i++) out[i] = Vec3f{rgb[i].x, rgb[i].y, rgb[i].z};
         return out;
+    }
+    // render() with adaptive anti-aliasing (rm_render_antialiased): rendered once, then every pixel that differs from a
+    // neighbour by more than `threshold` in a channel is replaced by the mean of n x n radiance samples (n in 1..8), found,
+    // shaded and resolved on the device.  Fills the whole patch rows of `frame`; the pixels refined are left in last_refined.
+    std::string render_antialiased(framebuffer::FrameBuffer &frame, const scene::Scene &sc, uint32_t n, double threshold) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_refine refine{n, 0u, threshold};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3);
+        check(rm_render_antialiased(ctx_, &p, &refine, flat.data(), &last_refined, &last_timing), ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
     }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.

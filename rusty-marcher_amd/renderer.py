@@ -22,6 +22,7 @@ class Renderer:
         self.max_depth = 3
         self.device = 0
         self.last_timing = None
+        self.last_refined = None                                           # render_antialiased: pixels it refined
 
     def render(self, frame, scene):
         t0 = time.perf_counter()
@@ -85,6 +86,36 @@ class Renderer:
         _lib.lib().rm_format_status(buf, 256, ms, frame.width, frame.height)
         message = buf.value.decode()
         print(message)
+        return message
+
+    def render_antialiased(self, frame, scene, n, threshold):
+        """render() with adaptive anti-aliasing (rm_render_antialiased): the frame is rendered once, and every pixel that
+        differs from a left / right / upper / lower neighbour by more than `threshold` in a channel -- on the radiance as
+        rendered -- is replaced by the mean of the radiance at (x + i/n, y + j/n), i, j in 0..n-1, the samples of
+        render_supersampled.  Found, shaded and resolved on the device; the whole patch rows of frame.buffer are filled,
+        rows from height - height % 32 on are left untouched.  Prints and returns what render() does; the number of refined
+        pixels is left in self.last_refined."""
+        backend._refine(n, threshold)                                      # ValueError before the library sees anything
+        t0 = time.perf_counter()
+        ctx = backend.default_context(self.device)
+        if frame.height % 32 != 0 or frame.width % 32 != 0:
+            print("Dimensions mismatch")                                   # renderer.rs:49-51
+        n_patches = (frame.height // 32) * (frame.width // 32)
+        print("Rendering using patches of size %d, using %d patches overall" % (32, n_patches))
+
+        p = backend.make_params(self.fov, self.height, self.width, self.max_depth)
+        p.frame_width, p.frame_height = frame.width, frame.height
+        ctx.upload(scene.flatten())
+        ctx.orient(getattr(scene, "basis", None))
+        self.last_timing, self.last_refined = ctx.render_antialiased(p, frame.buffer, n, threshold)
+
+        ms = int((time.perf_counter() - t0) * 1000.)
+        buf = C.create_string_buffer(256)
+        _lib.lib().rm_format_status(buf, 256, ms, frame.width, frame.height)
+        message = buf.value.decode()
+        print(message)
+        info = ctx.device_info()
+        print("%d compute units used" % info["cus"])
         return message
 
     def pick(self, frame, scene, x, y):

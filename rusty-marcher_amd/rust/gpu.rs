@@ -139,6 +139,16 @@ pub struct RmShading {
     pub _pad: u32,
 }
 
+/// `rm_refine`: what an adaptive anti-aliasing call refines -- n x n samples (n in 1..8) for every pixel whose contrast
+/// is > threshold (16 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmRefine {
+    pub n: u32,
+    pub _pad: u32,
+    pub threshold: f64,
+}
+
 /// `rm_lights_visible`'s modes: the decision direct_lighting takes / the shadow ray ended at the light.
 pub const RM_LIGHTS_AS_RENDERED: u32 = 0;
 pub const RM_LIGHTS_CLIPPED: u32 = 1;
@@ -239,6 +249,9 @@ extern "C" {
     fn rm_radiance_rays_device(ctx: *mut RmCtx, device_origins: *const c_void, device_directions: *const c_void, n_rays: u32, shading: *const RmShading, device_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_radiance_samples(ctx: *mut RmCtx, params: *const RmParams, xy: *const f64, n: u32, rgb: *mut RmVec3) -> c_int;
     fn rm_radiance_samples_device(ctx: *mut RmCtx, params: *const RmParams, device_xy: *const c_void, n: u32, device_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_refine_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
+    fn rm_refine_device(ctx: *mut RmCtx, params: *const RmParams, refine: *const RmRefine, device_rgb: *mut c_void, device_workspace: *mut c_void, device_mask: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_antialiased(ctx: *mut RmCtx, params: *const RmParams, refine: *const RmRefine, host_rgb: *mut f64, n_refined: *mut u32, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -384,6 +397,42 @@ impl Gpu {
         let mut timing = RmTiming::default();
         check(unsafe { rm_render_rows(self.ctx, &p, rows.as_ptr(), &mut timing) }, self.ctx);
         Gpu::status(now, frame.width, frame.height)
+    }
+
+    /// `render` with adaptive anti-aliasing: the frame is rendered once, then every pixel that differs from a left / right /
+    /// upper / lower neighbour by more than `threshold` in a channel is replaced by the mean of `n` x `n` radiance samples
+    /// (`n` in 1..8) -- found, shaded and resolved on the GPU in one library call.  Fills the whole patch rows of
+    /// `frame.buffer`; returns the status string and the number of pixels refined.
+    pub fn render_antialiased(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        n: u32,
+        threshold: f64,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let refine = RmRefine { n: n, _pad: 0, threshold: threshold };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3];
+        let mut refined: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe { rm_render_antialiased(self.ctx, &p, &refine, flat.as_mut_ptr(), &mut refined, &mut timing) },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), refined)
     }
 
     /// `render` with a device-resident FrameBuffer: the f64 frame stays on the GPU and only
