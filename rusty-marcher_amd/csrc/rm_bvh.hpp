@@ -54,7 +54,7 @@ struct rm_bvh {
 // split alone has no depth bound (spheres whose radii double along a line give one level per
 // sphere), so below RM_BVH_SAH_DEPTH levels the builder splits at the median: from there the
 // depth is at most log2(count), and the whole tree stays under RM_BVH_MAX_DEPTH for any
-// primitive count a 32-bit index can address.  rm_scene_upload checks `depth` all the same.
+// primitive count a 32-bit index can address.  rm_build_image (rm_image.cpp) checks `depth` all the same.
 #define RM_BVH_SAH_DEPTH 24u
 #define RM_BVH_MAX_DEPTH 60u
 

@@ -16,7 +16,7 @@
 #include <utility>
 #include <vector>
 
-#include "rm_bvh.hpp"
+#include "rm_image.hpp"
 #include "rm_internal.h"
 #include "rm_kernel_args.hpp"
 #include "rm_plan.hpp"
@@ -144,7 +144,7 @@ struct rm_ctx {
 
     // uploaded scene
     bool have_scene = false;
-    rm_dev_header H{};
+    rm_image image;                   // the resident image as the host built it (rm_scene_upload skips identical ones); the device's copies:
     double *d_scene = nullptr;
     size_t d_scene_words = 0;
     rm_vec3 camera{0., 0., 0.};
@@ -153,17 +153,13 @@ struct rm_ctx {
     // the state off) and every launch takes the oriented kernels.  The context's, like `camera`: an upload leaves it alone.
     bool oriented = false;
     rm_camera_basis basis{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
-    std::vector<double> host_blob;    // the device image of the resident scene (rm_scene_upload skips identical ones)
     uint64_t upload_calls = 0, upload_copies = 0;
     std::vector<unsigned char> desc_bytes;   // the description arrays the resident image was built from, back to back
     size_t desc_sizes[6] = {0, 0, 0, 0, 0, 0};
-    bool integer_exponents = false;   // every material's specular_exponent is a small non-negative integer
     const rm_knobs knobs = rm_knobs_from_env();   // A/B knobs and test hooks: the environment as rm_init found it
-    double occ_camera_limit = 0.;     // the resident image's: cameras farther out (L1 norm) render without its masks
-    double dead_camera_limit = 0.;    // ... and without its empty half-spaces (0: it has none)
-    // checked numerics (rm_trace.inc RM_CHECKED): the resident image's verdict, the last render launch's, and the tiles the
-    // context's launches rendered again because a lane's guard fired (device word, counted up by the kernels)
-    bool scene_exact_only = false, last_launch_exact_only = false;
+    // checked numerics (rm_trace.inc RM_CHECKED): the last render launch's verdict (the resident image's: image.exact_only), and
+    // the tiles the context's launches rendered again because a lane's guard fired (device word, counted up by the kernels)
+    bool last_launch_exact_only = false;
     uint32_t *d_redo = nullptr;
     std::vector<rm_feedback> feedback;
     uint64_t feedback_clock = 0, scene_epoch = 0;
@@ -203,7 +199,6 @@ struct rm_ctx {
     // whether the render kernels copy the scene into LDS) -- and the host variants' staging buffer
     uint32_t *d_pid_map = nullptr;
     size_t pid_map_words = 0;
-    std::vector<uint32_t> host_pid_map;
     void *d_query = nullptr;
     size_t query_bytes = 0;
 
@@ -258,12 +253,6 @@ static T *entry_of(std::vector<T> &v, hipStream_t stream) {
         if (e__ != hipSuccess)                                                                     \
             return ctx_fail(ctx, RM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
-
-// RM_ERR_SCENE_LIMIT is left for what the blob's 32-bit word offsets cannot address.
-static constexpr uint64_t RM_SCENE_MAX_WORDS = 0xFFFFFFF0ull;
-// A hierarchy is built over a kind once it has this many primitives (below, the flat walk
-// is as fast: the demo scene has 4 spheres).
-static constexpr size_t RM_BVH_MIN_SPHERES = 16, RM_BVH_MIN_TRIANGLES = 12;
 
 
 // The kernel instantiations live in rm_kernels.hip, one object per numeric flavour and kernel
@@ -402,11 +391,9 @@ rm_status rm_device_info(rm_ctx *ctx, char *name_buf, size_t buflen, int *n_cus,
     return RM_OK;
 }
 
-static uint64_t pack_u32x2(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
-
 // The queries' pid -> (shape, element) map of a new resident image into its device buffer (the device is idle: the
-// caller has synchronised it).  Swaps `map` into the context.
-static rm_status upload_pid_map(rm_ctx *ctx, std::vector<uint32_t> &map) {
+// caller has synchronised it).
+static rm_status upload_pid_map(rm_ctx *ctx, const std::vector<uint32_t> &map) {
     const size_t words = std::max<size_t>(map.size(), 2u);
     if (ctx->pid_map_words < words) {
         if (ctx->d_pid_map) RM_HIP(ctx, hipFree(ctx->d_pid_map));
@@ -416,402 +403,14 @@ static rm_status upload_pid_map(rm_ctx *ctx, std::vector<uint32_t> &map) {
         ctx->pid_map_words = words;
     }
     if (!map.empty()) RM_HIP(ctx, hipMemcpy(ctx->d_pid_map, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    ctx->host_pid_map.swap(map);
-    return RM_OK;
-}
-
-// The device image of a description: header, blob, the queries' pid -> (shape, element) map.  Host work
-// only (rm_scene_upload copies it; rmi_shadow_masks hands its occluder masks to the tests).
-struct rm_image {
-    rm_dev_header H{};
-    std::vector<double> blob;
-    std::vector<uint32_t> pid_map;
-    double occ_camera_limit = 0.;      // |camera|_1 beyond which the render does not use the occluder masks
-    std::vector<unsigned char> empty_sides;   // per pid: the sides of its plane that hold nothing (rm_build_empty_sides; scenes of up to 64 pids)
-    double dead_camera_limit = 0.;     // |camera|_1 beyond which the render does not use them (0: no glass word carries any)
-    bool exact_only = false;           // outside what the checked numerics are proven for (scene_exact_only)
-};
-
-// Checked numerics (rm_trace.inc RM_CHECKED; the bounds: rm_plan.hpp): a scene is rendered by the exact code alone when any
-// coordinate, radius or light word of its description is not finite or beyond RM_CHECKED_COORD_MAX in magnitude --
-// within it no intermediate of a sphere test overflows into a NaN whose payload the two square-root sequences might carry
-// differently -- or a sphere's radius_square lies outside the range in which the discriminant's root needs no scaling.
-// (The camera is the launch's: rm_camera_update can set it to anything, and the plan looks at the one a launch carries.)
-static bool scene_exact_only(const rm_scene_desc *d) {
-    bool ok = true;
-    auto v3 = [&](const rm_vec3 &v) { ok = ok && rm_checked_coord_ok(v.x) && rm_checked_coord_ok(v.y) && rm_checked_coord_ok(v.z); };
-    for (uint32_t i = 0; i < d->n_spheres; i++) {
-        v3(d->spheres[i].center);
-        const double r2 = d->spheres[i].radius_square;
-        ok = ok && r2 >= RM_CHECKED_R2_MIN && r2 <= RM_CHECKED_R2_MAX && rm_checked_coord_ok(r2);
-    }
-    for (uint32_t i = 0; i < d->n_polygons; i++) { v3(d->polygons[i].plane_normal); v3(d->polygons[i].plane_point); }
-    for (uint32_t i = 0; i < d->n_polygon_vertices; i++) v3(d->polygon_vertices[i]);
-    for (uint32_t i = 0; i < d->n_triangles; i++) {
-        const rm_triangle &t = d->triangles[i];
-        v3(t.normal); v3(t.center);
-        for (const rm_vec3 &v : t.vertices) v3(v);
-    }
-    for (uint32_t i = 0; i < d->n_lights; i++) {
-        v3(d->lights[i].position); v3(d->lights[i].color);
-        ok = ok && rm_checked_coord_ok(d->lights[i].intensity);
-    }
-    return !ok;
-}
-static rm_status build_image(rm_ctx *ctx, const rm_scene_desc *d, bool use_bvh, bool shadow_masks, rm_image &img) {
-    // ---- regroup Scene.shapes by kind, remembering list order for ties ----
-    std::vector<uint32_t> sphere_src, polygon_src, tri_src;   // indices into desc arrays
-    std::vector<uint32_t> sphere_key, polygon_key, tri_key;   // ordinal in flattened list order
-    std::vector<uint32_t> ordinal_shape;                      // ordinal -> (index into Scene.shapes, triangle index inside the Obj)
-    uint32_t ordinal = 0;
-    for (uint32_t i = 0; i < d->n_shapes; i++) {
-        const rm_shape_ref &r = d->shapes[i];
-        switch (r.kind) {
-        case RM_SHAPE_SPHERE:
-            if (r.first >= d->n_spheres || r.count != 1) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad sphere ref");
-            sphere_src.push_back(r.first); sphere_key.push_back(ordinal++);
-            ordinal_shape.insert(ordinal_shape.end(), {i, 0u});
-            break;
-        case RM_SHAPE_POLYGON:
-            if (r.first >= d->n_polygons || r.count != 1) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad polygon ref");
-            polygon_src.push_back(r.first); polygon_key.push_back(ordinal++);
-            ordinal_shape.insert(ordinal_shape.end(), {i, 0u});
-            break;
-        case RM_SHAPE_MESH:
-            if ((uint64_t)r.first + r.count > d->n_triangles) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad mesh ref");
-            for (uint32_t t = 0; t < r.count; t++) {
-                tri_src.push_back(r.first + t); tri_key.push_back(ordinal++);
-                ordinal_shape.insert(ordinal_shape.end(), {i, t});
-            }
-            break;
-        default:
-            return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: unknown shape kind");
-        }
-    }
-    // ---- hierarchies over the spheres and the mesh triangles (rm_bvh.hpp): primitives of
-    // a kind are re-ordered into leaf order; their list-order keys travel with them
-    rm_bvh bvh_s, bvh_t;
-    if (use_bvh && sphere_src.size() >= RM_BVH_MIN_SPHERES) {
-        std::vector<rm_aabb> boxes(sphere_src.size());
-        for (size_t i = 0; i < sphere_src.size(); i++) {
-            const rm_sphere &sp = d->spheres[sphere_src[i]];
-            const double r = std::sqrt(sp.radius_square) * (1. + 1e-12);
-            const double c[3] = {sp.center.x, sp.center.y, sp.center.z};
-            for (int a = 0; a < 3; a++) { boxes[i].lo[a] = c[a] - r; boxes[i].hi[a] = c[a] + r; }
-        }
-        bvh_s = rm_build_bvh(boxes, 4);
-        std::vector<uint32_t> src(sphere_src.size()), key(sphere_src.size());
-        for (size_t k = 0; k < src.size(); k++) { src[k] = sphere_src[bvh_s.order[k]]; key[k] = sphere_key[bvh_s.order[k]]; }
-        sphere_src.swap(src);
-        sphere_key.swap(key);
-    }
-    if (use_bvh && tri_src.size() >= RM_BVH_MIN_TRIANGLES) {
-        std::vector<rm_aabb> boxes(tri_src.size());
-        for (size_t i = 0; i < tri_src.size(); i++) {
-            const rm_triangle &t = d->triangles[tri_src[i]];
-            boxes[i].reset();
-            for (const rm_vec3 &v : t.vertices) {
-                const double c[3] = {v.x, v.y, v.z};
-                for (int a = 0; a < 3; a++) { boxes[i].lo[a] = std::min(boxes[i].lo[a], c[a]); boxes[i].hi[a] = std::max(boxes[i].hi[a], c[a]); }
-            }
-        }
-        bvh_t = rm_build_bvh(boxes, 2);
-        std::vector<uint32_t> src(tri_src.size()), key(tri_src.size());
-        for (size_t k = 0; k < src.size(); k++) { src[k] = tri_src[bvh_t.order[k]]; key[k] = tri_key[bvh_t.order[k]]; }
-        tri_src.swap(src);
-        tri_key.swap(key);
-    }
-
-    std::vector<uint32_t> keys;
-    keys.insert(keys.end(), sphere_key.begin(), sphere_key.end());
-    keys.insert(keys.end(), polygon_key.begin(), polygon_key.end());
-    keys.insert(keys.end(), tri_key.begin(), tri_key.end());
-    bool ordered = true;
-    for (size_t i = 1; i < keys.size(); i++) ordered = ordered && keys[i - 1] < keys[i];
-    // the queries' way back from a device primitive to the reference's (shape, element): through the same keys
-    std::vector<uint32_t> &pid_map = img.pid_map;
-    pid_map.assign(2u * keys.size(), 0u);
-    for (size_t q = 0; q < keys.size(); q++) {
-        pid_map[2u * q] = ordinal_shape[2u * keys[q]];
-        pid_map[2u * q + 1u] = ordinal_shape[2u * keys[q] + 1u];
-    }
-
-    rm_dev_header &H = img.H;
-    H = rm_dev_header{};
-    H.n_spheres = (uint32_t)sphere_src.size();
-    H.n_polygons = (uint32_t)polygon_src.size();
-    H.n_triangles = (uint32_t)tri_src.size();
-    H.n_lights = d->n_lights;
-    const uint32_t n_prims = H.n_spheres + H.n_polygons + H.n_triangles;
-    H.list_ordered = ordered ? 1u : 0u;
-
-    uint32_t n_pverts = 0;
-    for (uint32_t src : polygon_src) {
-        const rm_polygon &p = d->polygons[src];
-        if (p.n_vertices < 3 || (uint64_t)p.first_vertex + p.n_vertices > d->n_polygon_vertices)
-            return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: bad polygon vertex range");
-        n_pverts += p.n_vertices;
-    }
-
-    // 32-bit word offsets: refuse scenes they cannot address
-    const uint64_t need_words = (uint64_t)H.n_spheres * RM_SPHERE_WORDS + (uint64_t)H.n_polygons * RM_POLYGON_WORDS +
-                                ((uint64_t)n_pverts + 1u) * RM_PVERT_WORDS + (uint64_t)H.n_triangles * RM_TRIANGLE_WORDS +
-                                (uint64_t)n_prims * (RM_MATERIAL_WORDS + 1u + 4u + 16u + 1u) + (uint64_t)H.n_lights * RM_LIGHT_WORDS +
-                                bvh_s.nodes.size() + bvh_t.nodes.size() + 256u;
-    if (need_words > RM_SCENE_MAX_WORDS)
-        return ctx_fail(ctx, RM_ERR_SCENE_LIMIT, "rm_scene_upload: scene exceeds the 32 GiB the device layout can address");
-    uint32_t off = 0;
-    auto take = [&](uint32_t words) { uint32_t o = off; off += (words + 1u) & ~1u; return o; };
-    H.off_spheres = take(H.n_spheres * RM_SPHERE_WORDS);
-    H.off_polygons = take(H.n_polygons * RM_POLYGON_WORDS);
-    H.off_pverts = take((n_pverts + 1u) * RM_PVERT_WORDS);   // +1: the loops fetch four vertices at a time
-    H.off_triangles = take(H.n_triangles * RM_TRIANGLE_WORDS);
-    H.off_materials = take(n_prims * RM_MATERIAL_WORDS);
-    H.off_lights = take(H.n_lights * RM_LIGHT_WORDS);
-    H.off_keys = take((n_prims + 1u) / 2u);
-    H.off_bounds = take(n_prims * 4u);
-    H.off_planar = take((H.n_polygons + H.n_triangles) * 16u);
-    const uint32_t n_groups = (n_prims + 63u) / 64u;
-    H.off_groups = (n_groups >= 3u && n_groups <= 64u) ? take(n_groups * 4u) : 0u;
-    // The wave's hierarchy stack holds 64 entries, one parked sibling per level: the builder
-    // keeps every tree under RM_BVH_MAX_DEPTH levels (rm_bvh.hpp); a tree that is deeper all
-    // the same is not walked (its primitives keep their leaf order and are walked flat).
-    if (bvh_s.depth > RM_BVH_MAX_DEPTH) bvh_s.nodes.clear();
-    if (bvh_t.depth > RM_BVH_MAX_DEPTH) bvh_t.nodes.clear();
-    H.off_bvh_spheres = bvh_s.nodes.empty() ? 0u : take((uint32_t)bvh_s.nodes.size());
-    H.off_bvh_triangles = bvh_t.nodes.empty() ? 0u : take((uint32_t)bvh_t.nodes.size());
-    take(64u);                                               // batch loads may read past the last record
-    H.total_words = off;
-
-    std::vector<double> &blob = img.blob;
-    blob.assign(H.total_words ? H.total_words : 2, 0.);
-    auto put_material = [&](uint32_t pid, const rm_reflectance &r) {
-        double *m = &blob[H.off_materials + RM_MATERIAL_WORDS * pid];
-        m[0] = r.diffusion;
-        m[1] = r.diffuse_color.x; m[2] = r.diffuse_color.y; m[3] = r.diffuse_color.z;
-        m[4] = r.specular; m[5] = r.specular_exponent;
-        m[6] = r.reflection; m[7] = r.refractive_index;
-        m[8] = r.is_glass_like ? 1. : 0.;
-        m[9] = 1. / r.refractive_index;   // reflect_child / refract_child read it: one IEEE division here, the bits of the device's per ray
-    };
-    // Bounding sphere of everything of primitive `pid` a ray can hit, for the bundle cull
-    // (rm_trace.inc): inflated by 1e-7 relative + 1e-9 of the coordinates' magnitude -- far
-    // beyond the rounding of any hit test, so a primitive some ray hits is never culled.
-    // Anything that is not a finite number makes the primitive a candidate for every bundle.
-    double max_normal = 1.;                                   // sphere normals are unit (sphere.rs:58)
-    auto put_bounds = [&](uint32_t pid, double cx, double cy, double cz, double r) {
-        double *w = &blob[H.off_bounds + 4u * pid];
-        const double mag = std::fabs(cx) + std::fabs(cy) + std::fabs(cz);
-        double rr = r * (1. + 1e-7) + 1e-9 * (1. + mag);
-        if (!(rr >= 0.) || !std::isfinite(rr) || !std::isfinite(mag)) { cx = cy = cz = 0.; rr = std::numeric_limits<double>::infinity(); }
-        w[0] = cx; w[1] = cy; w[2] = cz; w[3] = rr;
-    };
-    // A planar primitive is hit where the ray meets the plane (point, normal) AND the x, y of
-    // that point pass the 2-D edge tests (polygon.rs:54-56, triangle.rs:69-77), i.e. lie in
-    // the convex hull of the vertices' x, y: the hit points are the hull of the vertices
-    // LIFTED onto that plane along z -- the vertices themselves when they are coplanar with
-    // it, as they are for everything the reference's constructors build.  That holds for ANY vertex
-    // list, convex or not: a point that is to the left of every edge is wound round by the closed
-    // line at least once, so it lies inside the line's hull (bow ties, darts, clockwise lists:
-    // tests/test_gpu_grazing.py test_odd_vertex_lists).
-    auto planar_bounds = [&](uint32_t pid, const rm_vec3 &n, const rm_vec3 &pp, const rm_vec3 *v, uint32_t nv) {
-        max_normal = std::max(max_normal, std::sqrt(n.x * n.x + n.y * n.y + n.z * n.z));
-        double *pl = &blob[H.off_planar + 16u * (pid - H.n_spheres)];   // zero-filled: count 0 = no edge test
-        // The inside test reads only x and y (polygon.rs:54-56): with every vertex at the SAME x
-        // (or the same y) its cross products are differences of the same rounded products, sum to
-        // zero exactly and can never all be positive -- the primitive is never hit (the floor and
-        // ceiling of the Cornell box, any wall along z).  Radius -1: the cull drops it outright.
-        bool same_x = true, same_y = true;
-        for (uint32_t i = 1; i < nv; i++) { same_x = same_x && v[i].x == v[0].x; same_y = same_y && v[i].y == v[0].y; }
-        // Likewise two CONSECUTIVE vertices with the same x and the same y (a wall along z cut into triangles:
-        // the red wall of the Cornell box): the cross product of that edge is x y' - y x' with (x, y) == (x', y')
-        // bit for bit -- the same product twice, exactly zero, never > 0 -- for every hit point.
-        bool twin_edge = false;
-        for (uint32_t i = 0; i < nv; i++) {
-            const rm_vec3 &p = v[i], &q = v[(i + 1u) % nv];
-            twin_edge = twin_edge || (p.x == q.x && p.y == q.y);
-        }
-        if (same_x || same_y || twin_edge) {
-            double *w = &blob[H.off_bounds + 4u * pid];
-            w[0] = w[1] = w[2] = 0.; w[3] = -1.;
-            return;
-        }
-        if (!(std::fabs(n.z) > 1e-12 * (std::fabs(n.x) + std::fabs(n.y) + std::fabs(n.z)))) {
-            // plane along z: the x, y of its points are a line; no finite bound holds the lifted hull
-            put_bounds(pid, 0., 0., 0., std::numeric_limits<double>::infinity());
-            return;
-        }
-        std::vector<rm_vec3> lifted(nv);
-        double cx = 0., cy = 0., cz = 0.;
-        for (uint32_t i = 0; i < nv; i++) {
-            const double z = pp.z - (n.x * (v[i].x - pp.x) + n.y * (v[i].y - pp.y)) / n.z;
-            lifted[i] = rm_vec3{v[i].x, v[i].y, z};
-            cx += v[i].x; cy += v[i].y; cz += z;
-        }
-        cx /= nv; cy /= nv; cz /= nv;
-        double r2 = 0.;
-        for (const rm_vec3 &q : lifted) r2 = std::max(r2, (q.x - cx) * (q.x - cx) + (q.y - cy) * (q.y - cy) + (q.z - cz) * (q.z - cz));
-        put_bounds(pid, cx, cy, cz, std::sqrt(r2));
-        // the lifted vertices for the cull's edge test (triangles and quads; a triangle
-        // repeats its first vertex so that edge 2-3 closes it)
-        bool with_edges = nv == 3u || nv == 4u;
-        for (const rm_vec3 &q : lifted) with_edges = with_edges && std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z);
-        // The edge test takes the side of an edge's plane that holds the vertices' mean for the inner one (rm_trace.inc
-        // cull_edge): true of a convex list of either winding, not of any list -- a dart's mean lies on the OUTER side
-        // of the edges at its reflex vertex, and the bundles that hit it between them would be dropped
-        // (tests/test_gpu_grazing.py).  Only lists whose x, y turn one way at every vertex, strictly, get the record;
-        // the others keep their bounding sphere alone.
-        int turn = 0;
-        for (uint32_t i = 0; i < nv && with_edges; i++) {
-            const rm_vec3 &p = lifted[i], &q = lifted[(i + 1u) % nv];
-            for (uint32_t k = 0; k < nv && with_edges; k++) {
-                if (k == i || k == (i + 1u) % nv) continue;
-                const double c = (q.x - p.x) * (lifted[k].y - p.y) - (q.y - p.y) * (lifted[k].x - p.x);
-                const int sgn = c > 0. ? 1 : c < 0. ? -1 : 0;
-                with_edges = sgn != 0 && (turn == 0 || sgn == turn);
-                turn = sgn;
-            }
-        }
-        if (with_edges) {
-            for (uint32_t i = 0; i < 4u; i++) {
-                const rm_vec3 &q = lifted[i < nv ? i : 0u];
-                pl[3 * i] = q.x; pl[3 * i + 1] = q.y; pl[3 * i + 2] = q.z;
-            }
-            pl[12] = (double)nv;
-        }
-    };
-    uint32_t pid = 0;
-    for (uint32_t i = 0; i < H.n_spheres; i++, pid++) {
-        const rm_sphere &s = d->spheres[sphere_src[i]];
-        double *w = &blob[H.off_spheres + RM_SPHERE_WORDS * i];
-        w[0] = s.center.x; w[1] = s.center.y; w[2] = s.center.z; w[3] = s.radius_square;
-        put_material(pid, s.reflectance);
-        put_bounds(pid, s.center.x, s.center.y, s.center.z, std::sqrt(s.radius_square));
-    }
-    uint32_t pv = 0;
-    for (uint32_t i = 0; i < H.n_polygons; i++, pid++) {
-        const rm_polygon &p = d->polygons[polygon_src[i]];
-        double *w = &blob[H.off_polygons + RM_POLYGON_WORDS * i];
-        w[0] = p.plane_normal.x; w[1] = p.plane_normal.y; w[2] = p.plane_normal.z;
-        w[3] = p.plane_point.x; w[4] = p.plane_point.y; w[5] = p.plane_point.z;
-        const uint64_t packed = pack_u32x2(pv, p.n_vertices);
-        std::memcpy(&w[6], &packed, sizeof packed);
-        w[7] = 0.;
-        for (uint32_t v = 0; v < p.n_vertices; v++, pv++) {
-            const rm_vec3 &q = d->polygon_vertices[p.first_vertex + v];
-            blob[H.off_pverts + RM_PVERT_WORDS * pv] = q.x;
-            blob[H.off_pverts + RM_PVERT_WORDS * pv + 1] = q.y;
-            // the first four also travel in the record: one fetch per polygon, not two dependent ones
-            if (v < 4) { w[8 + 2 * v] = q.x; w[9 + 2 * v] = q.y; }
-        }
-        put_material(pid, p.reflectance);
-        planar_bounds(pid, p.plane_normal, p.plane_point, &d->polygon_vertices[p.first_vertex], p.n_vertices);
-    }
-    for (uint32_t i = 0; i < H.n_triangles; i++, pid++) {
-        const rm_triangle &t = d->triangles[tri_src[i]];
-        double *w = &blob[H.off_triangles + RM_TRIANGLE_WORDS * i];
-        w[0] = t.normal.x; w[1] = t.normal.y; w[2] = t.normal.z;
-        w[3] = t.center.x; w[4] = t.center.y; w[5] = t.center.z;
-        for (int v = 0; v < 3; v++) { w[6 + 2 * v] = t.vertices[v].x; w[7 + 2 * v] = t.vertices[v].y; }
-        put_material(pid, t.reflectance);
-        planar_bounds(pid, t.normal, t.center, t.vertices, 3u);
-    }
-    // The cull's first step in scenes of 3+ steps: a sphere around the bounding spheres of each 64
-    // consecutive pids (box centre of the members; primitives that can never be hit -- radius -1 --
-    // do not count, a group of nothing else is never visited).
-    for (uint32_t g = 0; H.off_groups && g < n_groups; g++) {
-        const uint32_t first = g * 64u, last = std::min(n_prims, first + 64u);
-        double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-        bool any = false, unbounded = false;
-        for (uint32_t q = first; q < last; q++) {
-            const double *w = &blob[H.off_bounds + 4u * q];
-            if (w[3] < 0.) continue;
-            any = true;
-            if (!std::isfinite(w[3])) { unbounded = true; continue; }
-            for (int c = 0; c < 3; c++) { lo[c] = std::min(lo[c], w[c] - w[3]); hi[c] = std::max(hi[c], w[c] + w[3]); }
-        }
-        double *o = &blob[H.off_groups + 4u * g];
-        if (!any) { o[0] = o[1] = o[2] = 0.; o[3] = -1.; continue; }
-        if (unbounded) { o[0] = o[1] = o[2] = 0.; o[3] = std::numeric_limits<double>::infinity(); continue; }
-        const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
-        double r = 0.;
-        for (uint32_t q = first; q < last; q++) {
-            const double *w = &blob[H.off_bounds + 4u * q];
-            if (w[3] < 0.) continue;
-            const double dx = w[0] - cx, dy = w[1] - cy, dz = w[2] - cz;
-            r = std::max(r, std::sqrt(dx * dx + dy * dy + dz * dz) + w[3]);
-        }
-        const double mag = std::fabs(cx) + std::fabs(cy) + std::fabs(cz);
-        double rr = r * (1. + 1e-9) + 1e-12 * (1. + mag);
-        if (!std::isfinite(rr) || !std::isfinite(mag)) { o[0] = o[1] = o[2] = 0.; rr = std::numeric_limits<double>::infinity(); }
-        else { o[0] = cx; o[1] = cy; o[2] = cz; }
-        o[3] = rr;
-    }
-    // renderer.rs:168-172: a shadow ray starts 1e-3 of the normal off the hit point and runs
-    // along normalize(light - point): it passes within 1e-3 |normal| of the light
-    H.shadow_rho = 1e-3 * max_normal * (1. + 1e-6) + 1e-12;
-    for (uint32_t l = 0; l < H.n_lights; l++) {
-        const rm_light &lt = d->lights[l];
-        double *w = &blob[H.off_lights + RM_LIGHT_WORDS * l];
-        w[0] = lt.position.x; w[1] = lt.position.y; w[2] = lt.position.z;
-        w[3] = lt.color.x; w[4] = lt.color.y; w[5] = lt.color.z;
-        w[6] = lt.intensity; w[7] = 0.;
-    }
-    if (!keys.empty()) std::memcpy(&blob[H.off_keys], keys.data(), keys.size() * sizeof(uint32_t));
-    if (H.off_bvh_spheres) std::memcpy(&blob[H.off_bvh_spheres], bvh_s.nodes.data(), bvh_s.nodes.size() * sizeof(double));
-    if (H.off_bvh_triangles) std::memcpy(&blob[H.off_bvh_triangles], bvh_t.nodes.data(), bvh_t.nodes.size() * sizeof(double));
-
-    // the camera beyond which neither table below is used (the hit points' rounding: 1e-7 of the scene's size
-    // is the builders' margin), from the coordinates they are built from
-    auto camera_limit = [&]() {
-        double size = 0.;
-        for (uint32_t q = 0; q < n_prims; q++) {
-            const double *w = &blob[H.off_bounds + 4u * q];
-            if (w[3] >= 0.) size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]) + w[3]);
-        }
-        for (uint32_t l = 0; l < H.n_lights; l++) {
-            const double *w = &blob[H.off_lights + RM_LIGHT_WORDS * l];
-            size = std::fmax(size, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]));
-        }
-        return std::isfinite(size) ? 1e6 * (1. + size) : 0.;
-    };
-    // The planar primitives' empty half-spaces (rm_build_empty_sides) for the same scenes: a glass-like one carries them in
-    // its glass word, which every reader but the plain-walk kernels' render_tile tests for != 0 only.
-    if (n_prims > 0u && n_prims <= RM_SHADOW_MASK_MAX_PRIMS) {
-        img.empty_sides.assign(n_prims, 0);
-        rm_build_empty_sides(blob.data(), H, img.empty_sides.data());
-        bool any = false;
-        for (uint32_t q = 0; q < n_prims; q++) {
-            double &glass = blob[H.off_materials + RM_MATERIAL_WORDS * q + 8];
-            if (glass != 0. && img.empty_sides[q]) {
-                glass = 1. + ((img.empty_sides[q] & RM_EMPTY_SIDE_POS) ? 2. : 0.) + ((img.empty_sides[q] & RM_EMPTY_SIDE_NEG) ? 4. : 0.);
-                any = true;
-            }
-        }
-        if (any) img.dead_camera_limit = std::fmin(camera_limit(), RM_EMPTY_SIDES_CAMERA_MAX);
-    }
-    // The shadow rays' occluder masks (rm_build_shadow_masks) for the plain-walk kernels' scenes, behind the
-    // image the staged kernels copy (the walks read them with scalar loads): scenes of up to 64 pids.
-    if (shadow_masks && n_prims > 0u && n_prims <= RM_SHADOW_MASK_MAX_PRIMS && H.n_lights > 0u) {
-        const uint64_t words = (uint64_t)n_prims * H.n_lights;
-        if ((uint64_t)H.total_words + words + 2u <= RM_SCENE_MAX_WORDS) {
-            H.off_occ = H.total_words;
-            blob.resize((size_t)H.total_words + ((words + 1u) & ~1ull), 0.);
-            rm_build_shadow_masks(blob.data(), H, reinterpret_cast<unsigned long long *>(&blob[H.off_occ]));
-            img.occ_camera_limit = camera_limit();
-        }
-    }
-    img.exact_only = scene_exact_only(d);
     return RM_OK;
 }
 
 static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL ctx");
     if (!d) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL desc");
-    if ((d->n_shapes && !d->shapes) || (d->n_spheres && !d->spheres) || (d->n_polygons && !d->polygons) ||
-        (d->n_polygon_vertices && !d->polygon_vertices) || (d->n_triangles && !d->triangles) ||
-        (d->n_lights && !d->lights))
-        return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL array with non-zero count");
+    // (before the comparison below reads the arrays; rm_build_image refuses such a description with the same text)
+    if (!rm_desc_arrays_present(d)) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rm_scene_upload: NULL array with non-zero count");
 
     // The reference's hosts hand the whole Scene to every render() call (main.rs:331-333).  A
     // description byte-identical to the one the resident image was built from (cameras apart:
@@ -850,20 +449,20 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     }
 
     rm_image img;
-    if (rm_status bst = build_image(ctx, d, !ctx->knobs.disable_bvh, ctx->knobs.shadow_masks, img)) return bst;
-    const rm_dev_header &H = img.H;
-    std::vector<double> &blob = img.blob;
-    std::vector<uint32_t> &pid_map = img.pid_map;
-    const uint32_t n_prims = H.n_spheres + H.n_polygons + H.n_triangles;
+    std::string refusal;
+    if (rm_status bst = rm_build_image(d, rm_image_options{!ctx->knobs.disable_bvh, ctx->knobs.shadow_masks}, img, refusal))
+        return ctx_fail(ctx, bst, refusal);
+    rm_image &resident = ctx->image;
 
     // (a different description that builds the same device image -- an edit undone -- is not copied either)
-    if (ctx->have_scene && blob == ctx->host_blob && std::memcmp(&H, &ctx->H, sizeof H) == 0) {
+    if (ctx->have_scene && img.blob == resident.blob && std::memcmp(&img.H, &resident.H, sizeof img.H) == 0) {
         // (the same image can come from another shape list -- one Obj of two triangles, or two of one --: the
         // queries' map is the image's too, and goes across alone where only it differs)
-        if (pid_map != ctx->host_pid_map) {
+        if (img.pid_map != resident.pid_map) {
             RM_HIP(ctx, hipSetDevice(ctx->device));
             RM_HIP(ctx, hipDeviceSynchronize());          // a query may still be reading the old map
-            if (rm_status mst = upload_pid_map(ctx, pid_map)) return mst;
+            if (rm_status mst = upload_pid_map(ctx, img.pid_map)) return mst;
+            resident.pid_map.swap(img.pid_map);
         }
         ctx->camera = d->camera;
         keep_description();
@@ -872,32 +471,21 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     RM_HIP(ctx, hipSetDevice(ctx->device));
     RM_HIP(ctx, hipDeviceSynchronize());   // a render (on any stream: the caller's, a frame slot's) may still be reading the old blob
     ctx->upload_copies++;
-    if (ctx->d_scene_words < blob.size()) {
+    if (ctx->d_scene_words < img.blob.size()) {
         if (ctx->d_scene) RM_HIP(ctx, hipFree(ctx->d_scene));
         ctx->d_scene = nullptr;
-        RM_HIP(ctx, hipMalloc(&ctx->d_scene, blob.size() * sizeof(double)));
-        ctx->d_scene_words = blob.size();
+        RM_HIP(ctx, hipMalloc(&ctx->d_scene, img.blob.size() * sizeof(double)));
+        ctx->d_scene_words = img.blob.size();
     }
-    RM_HIP(ctx, hipMemcpy(ctx->d_scene, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (rm_status mst = upload_pid_map(ctx, pid_map)) {
+    RM_HIP(ctx, hipMemcpy(ctx->d_scene, img.blob.data(), img.blob.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (rm_status mst = upload_pid_map(ctx, img.pid_map)) {
         ctx->have_scene = false;                             // (the blob went across, its map did not: no half image)
         return mst;
     }
-    ctx->H = H;
-    ctx->occ_camera_limit = img.occ_camera_limit;
-    ctx->dead_camera_limit = img.dead_camera_limit;
-    ctx->scene_exact_only = img.exact_only;
+    std::swap(resident, img);                                // both copies are across: the new image is the resident one
     ctx->camera = d->camera;
     ctx->have_scene = true;
     ctx->scene_epoch++;                                      // (the feedback of another scene's frames is void)
-    // specular_pow<POW_INTEGER> applies when pow(x, y) is a plain integer power for every material
-    bool int_exp = true;
-    for (uint32_t q = 0; q < n_prims; q++) {
-        const double y = blob[H.off_materials + RM_MATERIAL_WORDS * q + 5];
-        int_exp = int_exp && (y >= 0. && y <= 1048576. && y == std::floor(y));
-    }
-    ctx->integer_exponents = int_exp;
-    ctx->host_blob.swap(blob);
     keep_description();
     return RM_OK;
 }
@@ -906,59 +494,6 @@ rm_status rm_scene_upload(rm_ctx *ctx, const rm_scene_desc *d) {
     return guarded(ctx, "rm_scene_upload", [&]() { return rm_scene_upload_impl(ctx, d); });
 }
 
-// Test hook, not part of the ABI (tests/test_shadow_masks.py): the occluder masks the upload of `d` builds, with
-// the knob's default.  dims[0] = pids, dims[1] = lights, dims[2] = 1 where there is a table; then, when there is
-// and cap >= pids x lights, occ[pid * lights + light] and shape_of[pid] = the pid's index into Scene.shapes.
-// Host work only: no device is needed.
-extern "C" rm_status rmi_shadow_masks(const rm_scene_desc *d, uint64_t *occ, uint32_t *shape_of, uint32_t cap, uint32_t *dims) {
-    if (!d || !dims) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rmi_shadow_masks: NULL argument");
-    rm_image img;
-    if (rm_status st = build_image(nullptr, d, true, true, img)) return st;
-    const rm_dev_header &H = img.H;
-    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
-    dims[0] = n; dims[1] = H.n_lights; dims[2] = H.off_occ ? 1u : 0u;
-    if (H.off_occ && occ && shape_of && (uint64_t)n * H.n_lights <= cap) {
-        std::memcpy(occ, &img.blob[H.off_occ], (size_t)n * H.n_lights * sizeof(uint64_t));
-        for (uint32_t q = 0; q < n; q++) shape_of[q] = img.pid_map[2u * q];
-    }
-    return RM_OK;
-}
-
-// Test hook, not part of the ABI (tests/test_dead_children.py): the empty half-spaces the upload of `d` finds.  dims[0] = pids,
-// dims[1] = 1 where there is a table; then, when there is and cap >= pids, sides[pid] (RM_EMPTY_SIDE_POS | RM_EMPTY_SIDE_NEG),
-// glass[pid] = the pid's glass word as the kernels read it, and shape_of[pid] = the pid's index into Scene.shapes;
-// *camera_limit = the camera beyond which a render does not use them.  Host work only: no device is needed.
-extern "C" rm_status rmi_empty_sides(const rm_scene_desc *d, uint8_t *sides, double *glass, uint32_t *shape_of, uint32_t cap, uint32_t *dims, double *camera_limit) {
-    if (!d || !dims) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rmi_empty_sides: NULL argument");
-    rm_image img;
-    if (rm_status st = build_image(nullptr, d, true, true, img)) return st;
-    const rm_dev_header &H = img.H;
-    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
-    dims[0] = n; dims[1] = img.empty_sides.empty() ? 0u : 1u;
-    if (camera_limit) *camera_limit = img.dead_camera_limit;
-    if (dims[1] && sides && glass && shape_of && n <= cap) {
-        for (uint32_t q = 0; q < n; q++) {
-            sides[q] = img.empty_sides[q];
-            glass[q] = img.blob[H.off_materials + RM_MATERIAL_WORDS * q + 8];
-            shape_of[q] = img.pid_map[2u * q];
-        }
-    }
-    return RM_OK;
-}
-
-// Test hooks, not part of the ABI (tests/test_checked_numerics.py, tests/test_gpu_checked_numerics.py).
-// What the upload of `d` decides and builds for the checked numerics: dims[0] = pids, dims[1] = 1 where the scene is exact
-// only; then, when cap >= 10 x pids, the material words of every pid.  Host work only: no device is needed.
-extern "C" rm_status rmi_upload_numerics(const rm_scene_desc *d, double *materials, uint32_t cap, uint32_t *dims) {
-    if (!d || !dims) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rmi_upload_numerics: NULL argument");
-    rm_image img;
-    if (rm_status st = build_image(nullptr, d, true, true, img)) return st;
-    const uint32_t n = img.H.n_spheres + img.H.n_polygons + img.H.n_triangles;
-    dims[0] = n; dims[1] = img.exact_only ? 1u : 0u;
-    if (materials && (uint64_t)n * RM_MATERIAL_WORDS <= cap)
-        std::memcpy(materials, &img.blob[img.H.off_materials], (size_t)n * RM_MATERIAL_WORDS * sizeof(double));
-    return RM_OK;
-}
 // The tiles the context's render launches have rendered again so far because a lane's guard fired (waits for the device),
 // and whether the last render launch was exact only.
 extern "C" rm_status rmi_redone_tiles(rm_ctx *ctx, uint64_t *redone, uint32_t *last_exact_only) {
@@ -1137,8 +672,9 @@ static rm_status void_frame_check(rm_ctx *ctx, const char *who) {
 }
 
 static rm_plan_scene plan_scene_of(const rm_ctx *ctx) {
-    return rm_plan_scene{&ctx->H, ctx->scene_epoch, ctx->occ_camera_limit, ctx->integer_exponents, ctx->oriented,
-                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, ctx->scene_exact_only, ctx->dead_camera_limit};
+    const rm_image &img = ctx->image;
+    return rm_plan_scene{&img.H, ctx->scene_epoch, img.occ_camera_limit, img.integer_exponents, ctx->oriented,
+                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, img.exact_only, img.dead_camera_limit};
 }
 
 static rm_status no_kernel(rm_ctx *ctx) { return ctx_fail(ctx, RM_ERR_INVALID_ARG, "render: no kernel for this scene / depth combination"); }

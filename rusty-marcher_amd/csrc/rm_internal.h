@@ -1,5 +1,6 @@
-// rm_internal.h -- shared between the host (rm_scene.cpp) and device (rm_device.hip)
-// halves of librusty_marcher_amd.so.  Not part of the public ABI.
+// rm_internal.h -- the layout of the device scene image, shared between its builder (rm_image.cpp), the upload and the
+// launchers (rm_device.hip, rm_plan.cpp) and the kernels that read it; and the host error text of librusty_marcher_amd.so
+// (rm_scene.cpp).  Not part of the public ABI.
 #ifndef RM_INTERNAL_H
 #define RM_INTERNAL_H
 
@@ -26,7 +27,7 @@ const char *rm_get_host_error();
 //   materials 10 words per pid: diffusion dcx dcy dcz specular exponent
 //                               reflection refractive_index is_glass 1/refractive_index
 //                               (is_glass: 0, or 1 + 2 x empty(+) + 4 x empty(-) -- the sides of a glass-like
-//                               polygon's / triangle's plane that hold nothing, rm_build_empty_sides)
+//                               polygon's / triangle's plane that hold nothing, rm_image.cpp rm_build_empty_sides)
 //   lights    8 words each : px py pz  cx cy cz  intensity 0
 //   keys      1 u32 per pid (2 per word): position in Scene.shapes order, used
 //                               only to break exact distance ties (shapes.rs:130)
@@ -44,7 +45,7 @@ const char *rm_get_host_error();
 //   occ       1 u64 per pid and light, [pid][light], BEHIND the total_words of the image the
 //                               staged kernels copy into LDS (read with scalar loads only): the
 //                               primitives (bit = pid) a shadow ray cast from a hit on pid
-//                               towards that light can hit at all (rm_build_shadow_masks)
+//                               towards that light can hit at all (rm_image.cpp rm_build_shadow_masks)
 struct rm_dev_header {
     uint32_t n_spheres, n_polygons, n_triangles, n_lights;
     uint32_t off_spheres, off_polygons, off_pverts, off_triangles;
@@ -58,20 +59,6 @@ struct rm_dev_header {
     uint32_t off_occ;             // 0, or (scenes of up to 64 pids) the shadow rays' occluder masks: n_prims x n_lights words
     double shadow_rho;            // every shadow ray passes within this of its light: 1e-3 x the longest normal (renderer.rs:168-172)
 };
-
-// occ[pid][light] from the image's bounds, lifted vertices, lights and shadow_rho (rm_scene.cpp)
-void rm_build_shadow_masks(const double *blob, const rm_dev_header &H, unsigned long long *occ);
-#define RM_SHADOW_MASK_MAX_PRIMS 64u
-
-// sides[pid]: bit 0 -- nothing of the scene lies on the side of the polygon's / triangle's plane its normal points to, bit 1 --
-// nothing on the other side (spheres, and anything in doubt: 0).  From the image's plane records, bounds, lifted vertices and
-// shadow_rho (rm_scene.cpp); scenes of up to RM_SHADOW_MASK_MAX_PRIMS pids.
-void rm_build_empty_sides(const double *blob, const rm_dev_header &H, unsigned char *sides);
-#define RM_EMPTY_SIDE_POS 1u
-#define RM_EMPTY_SIDE_NEG 2u
-// ... which the render reads only while the camera's L1 norm is at most this (a hit point then rounds far below the 1e-4 by
-// which a child ray starts off its surface)
-#define RM_EMPTY_SIDES_CAMERA_MAX 1e9
 
 #define RM_SPHERE_WORDS 4u
 #define RM_POLYGON_WORDS 16u   /* normal, plane point, (first vertex | count), pad, x/y of the first four vertices */

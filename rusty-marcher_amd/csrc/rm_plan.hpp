@@ -112,7 +112,7 @@ struct rm_plan_scene {
     rm_vec3 camera;
     const rm_camera_basis *basis;     // (the fixed view's own while the oriented state is off)
     uint32_t n_cus;
-    bool exact_only = false;          // the resident scene is outside what the checked numerics are proven for (rm_device.hip scene_exact_only)
+    bool exact_only = false;          // the resident scene is outside what the checked numerics are proven for (rm_image.cpp scene_exact_only)
     double dead_camera_limit = 0.;    // cameras farther out (L1 norm) walk every child ray (0: the image has no empty half-space, rm_build_empty_sides)
 };
 

@@ -38,9 +38,9 @@ static rm_status check_rays(rm_ctx *ctx, const char *who, const rm_vec3 *o, cons
 }
 
 static rm_status launch_query(rm_ctx *ctx, int kind, QueryArgs &q, uint32_t blocks, hipStream_t stream) {
-    q.H = ctx->H;
+    q.H = ctx->image.H;
     q.pid_map = ctx->d_pid_map;
-    const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (as launch_render picks its kernels)
+    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (as launch_render picks its kernels)
     const void *fn = rm_query_kernel(kind, bvh, kind == RM_QUERY_PIXELS && ctx->oriented);
     if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "query: no such kernel");
     void *args[] = {(void *)&ctx->d_scene, (void *)&q};
@@ -196,11 +196,11 @@ rm_status rm_primary_hits_device(rm_ctx *ctx, const rm_params *params, void *dev
 
 // ---- ranged queries: rays with a range, segments, lights (rm_query.hip's ranged kernels) ----------------------------------
 static rm_status launch_ranged(rm_ctx *ctx, const char *who, int kind, RangedArgs &q, hipStream_t stream) {
-    q.H = ctx->H;
+    q.H = ctx->image.H;
     q.pid_map = ctx->d_pid_map;
     const uint64_t blocks = (q.n + 63u) / 64u;
     if (blocks > 0x7FFFFFFFull) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": too many answers for one launch");
-    const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (as launch_query)
+    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (as launch_query)
     const void *fn = rm_ranged_kernel(kind, bvh);
     if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "ranged query: no such kernel");
     void *args[] = {(void *)&ctx->d_scene, (void *)&q};
@@ -263,9 +263,9 @@ static rm_status check_lights_call(rm_ctx *ctx, const char *who, uint32_t n_ligh
         std::snprintf(buf, sizeof buf, "%s: mode %u is neither RM_LIGHTS_AS_RENDERED (0) nor RM_LIGHTS_CLIPPED (1)", who, mode);
         return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
     }
-    if (n_lights != ctx->H.n_lights) {
+    if (n_lights != ctx->image.H.n_lights) {
         char buf[160];
-        std::snprintf(buf, sizeof buf, "%s: n_lights %u, the resident scene has %u", who, n_lights, ctx->H.n_lights);
+        std::snprintf(buf, sizeof buf, "%s: n_lights %u, the resident scene has %u", who, n_lights, ctx->image.H.n_lights);
         return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
     }
     return RM_OK;

@@ -6,10 +6,10 @@
 // and basis.  The sample rays are formed in the kernel, so the backproject tables are neither read nor rebuilt.
 
 static rm_status launch_radiance(rm_ctx *ctx, RadianceArgs &q, hipStream_t stream) {
-    q.H = ctx->H;
+    q.H = ctx->image.H;
     q.H.off_occ = 0u;                                                      // the occluder masks hold near the scene only: never here
-    const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (as launch_query)
-    const int pow_mode = (ctx->integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;   // (as choose_kernel)
+    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (as launch_query)
+    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;   // (as choose_kernel)
     // a lane parks at most max_depth - 1 rays (rm_plan.cpp choose_kernel), from a reduced set of stacks
     const void *fn = rm_radiance_kernel(bvh, pow_mode, q.max_depth <= 5u ? 4 : 32);
     if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "radiance: no such kernel");

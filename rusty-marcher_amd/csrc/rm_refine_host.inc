@@ -52,7 +52,7 @@ static rm_status refine_grid(rm_ctx *ctx, const void *fn, uint32_t total, uint32
 // The three steps on `stream`; everything was checked, rows > 0.
 static rm_status launch_refine(rm_ctx *ctx, const rm_params *p, const rm_refine *r, void *frame, void *ws, void *mask, hipStream_t stream) {
     RefineArgs q{};
-    q.H = ctx->H;
+    q.H = ctx->image.H;
     q.H.off_occ = 0u;                                                      // (as launch_radiance)
     q.frame_width = p->frame_width;
     q.rows = refine_rows(p);
@@ -71,8 +71,8 @@ static rm_status launch_refine(rm_ctx *ctx, const rm_params *p, const rm_refine 
     q.ws = static_cast<uint32_t *>(ws);
     q.mask = static_cast<uint8_t *>(mask);
 
-    const bool bvh = ctx->H.off_bvh_spheres != 0 || ctx->H.off_bvh_triangles != 0;   // (the radiance kernels' rules: launch_radiance)
-    const int pow_mode = (ctx->integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
+    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (the radiance kernels' rules: launch_radiance)
+    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
     const void *shade = rm_refine_shade_kernel(bvh, pow_mode, q.max_depth <= 5u ? 4 : 32);
     if (!shade) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "refine: no such kernel");
     const uint32_t total = q.rows * q.frame_width;

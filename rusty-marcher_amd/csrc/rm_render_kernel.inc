@@ -101,7 +101,7 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
     // (Culling only the tile's primary bundle in that kernel -- 40 % of its tiles see nothing but
     // sky -- was measured too: 85.9 against 83.9 us; a cull step costs what it saves there.)
     constexpr bool HANDOVER = CULL;
-    // Children that leave a glass-like polygon / triangle into an empty half-space (rm_scene.cpp rm_build_empty_sides; the
+    // Children that leave a glass-like polygon / triangle into an empty half-space (rm_image.cpp rm_build_empty_sides; the
     // launch plan says whether the image's flags hold for this camera) are not walked: per-lane kernels only -- the others
     // form one fused term per step, and the sum would round differently.
     const bool dead_children = DIV && own_sgpr(a.dead_children) != 0u;   // wave-uniform
@@ -140,7 +140,7 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
                 if (DIV) acc = acc + scaled(L, weight);
                 const bool glass = got & (s.mat[8] != 0.);     // is_glass_like, renderer.rs:277
                 if (where<DIV>(glass)) {
-                    const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];   // (1 / ri: the upload's division, rm_device.hip put_material)
+                    const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];   // (1 / ri: the upload's division, rm_image.cpp put_material)
                     V3 ro, rd, to, td;
                     double dn_r, dn_t;                          // rd . normal, td . normal: the dots the children's origins were offset by
                     const bool has_r = glass & reflect_child<DIV>(dir, s, ri, inv_ri, ro, rd, dn_r);   // renderer.rs:195-222

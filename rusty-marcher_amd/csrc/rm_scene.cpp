@@ -517,167 +517,6 @@ uint32_t rm_abi_version(void) { return RM_ABI_VERSION; }
 
 }  // extern "C"
 
-// ---- the shadow rays' occluder masks (rm_internal.h: occ; rm_trace.inc any_hit2) ----------------------
-// A shadow ray of a hit on primitive P towards light L (renderer.rs:163-174) starts 1e-3 of the normal off
-// the hit point p -- within shadow_rho of it -- and runs along normalize(L - p); the reference's test
-// (shapes.rs:92) reports a hit at ANY distance, beyond the light too.  With p in P's bounding sphere (c, r)
-// every such ray stays within shadow_rho of
-//   (H) the hull of that sphere and L -- the part up to the light -- and
-//   (N) the cone beyond L: apex L, axis L - c, half-angle asin(r / |L - c|).
-// Both lie in the double cone with apex L around a = (c - L) / |c - L|, (H) below (x - L).a <= |c - L| + r.
-// A primitive Q whose hit points all lie farther than shadow_rho from (H) and from (N) cannot occlude any
-// such ray, and its bit stays clear.  Q's bounding sphere against the double cone and that cap decides
-// first; triangles and quads whose sphere is not out -- a large floor's meets most cones -- are tested
-// again by their lifted vertices (the hull of their hit points): Q is out when some plane has all of them
-// beyond (H) and some plane has all of them beyond (N).  The planes tried: normal a, the coordinate axes,
-// Q's own plane, and the planes through L and each of Q's edges, both ways round.
-// Margins: 1e-7 of the coordinates' magnitude on top of the bounds' own inflation, 1e-9 on the cone's
-// sine -- far beyond the rounding of the kernel's tests and of the hit point itself (while the camera
-// stays within 1e6 scene sizes: rm_device.hip drops the table beyond).  P's own bit is always set; a light
-// inside or on P's sphere, or anything that is not a finite number, sets every bit.  Primitives that can
-// never be hit (radius -1, upload) are in no mask.
-namespace {
-
-// planes of normal n through L: all of Q's vertices w (relative to L) beyond (H) -- the hull of the sphere
-// (cl = c - L, r) and the origin -- and beyond (N), the cone (apex 0, axis -a, sine sin_t), by `marg`
-struct PlaneSep { bool h = false, n = false; };
-inline void try_plane(PlaneSep &sep, rm_vec3 n, const rm_vec3 *w, uint32_t nv, rm_vec3 cl, double r, rm_vec3 a, double sin_t,
-                      double marg) {
-    const double len = std::sqrt(dot(n, n));
-    if (!(len > 1e-150) || !std::isfinite(len)) return;
-    n = scaled(n, 1. / len);
-    for (int sign = 0; sign < 2; sign++, n = scaled(n, -1.)) {
-        double lo = HUGE_VAL;
-        for (uint32_t i = 0; i < nv; i++) lo = std::fmin(lo, dot(w[i], n));
-        if (!std::isfinite(lo)) continue;
-        sep.h = sep.h || lo > std::fmax(0., dot(cl, n) + r) + marg;
-        sep.n = sep.n || (dot(a, n) >= sin_t + 1e-9 && lo > marg);
-    }
-}
-
-}  // namespace
-
-void rm_build_shadow_masks(const double *blob, const rm_dev_header &H, unsigned long long *occ) {
-    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles, nl = H.n_lights;
-    const unsigned long long all = n >= 64u ? ~0ull : ((1ull << n) - 1ull);
-    const double rho = H.shadow_rho;
-    auto finite3 = [](rm_vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
-    auto mag = [](rm_vec3 v) { return std::fabs(v.x) + std::fabs(v.y) + std::fabs(v.z); };
-    for (uint32_t l = 0; l < nl; l++) {
-        const double *lw = blob + H.off_lights + RM_LIGHT_WORDS * l;
-        const rm_vec3 L = v3(lw[0], lw[1], lw[2]);
-        for (uint32_t P = 0; P < n; P++) {
-            unsigned long long &m = occ[(size_t)P * nl + l];
-            m = all;
-            const double *bp = blob + H.off_bounds + 4u * P;
-            const rm_vec3 c = v3(bp[0], bp[1], bp[2]);
-            if (!(bp[3] >= 0.) || !std::isfinite(bp[3]) || !finite3(c) || !finite3(L) || !(rho >= 0.) || !std::isfinite(rho)) continue;
-            const double tol = 1e-7 * (1. + mag(L) + mag(c) + bp[3]);
-            const double r = bp[3] + tol;
-            const rm_vec3 cl = c - L;
-            const double D = std::sqrt(dot(cl, cl));
-            if (!(D > r * (1. + 1e-6) + rho + tol)) continue;         // the light inside or on P's sphere
-            const rm_vec3 a = scaled(cl, 1. / D);
-            const double sin_t = std::fmin(1., r / D * (1. + 1e-9) + 1e-9);
-            const double cos_t = std::sqrt(std::fmax(0., 1. - sin_t * sin_t)) * (1. - 1e-9);
-            const double cap = D + r;                                 // (H) ends here along a
-            unsigned long long keep = 1ull << P;
-            for (uint32_t Q = 0; Q < n; Q++) {
-                if (Q == P) continue;
-                const double *bq = blob + H.off_bounds + 4u * Q;
-                if (bq[3] < 0.) continue;                             // never hit
-                const rm_vec3 cq = v3(bq[0], bq[1], bq[2]);
-                if (!std::isfinite(bq[3]) || !finite3(cq)) { keep |= 1ull << Q; continue; }
-                const double marg = rho + tol + 1e-7 * (mag(cq) + bq[3]);
-                const double R = bq[3] + marg;
-                const rm_vec3 v = cq - L, x = cross(v, a);
-                const double h = dot(v, a), q = std::sqrt(dot(x, x));   // along the axis, off it
-                bool out = (q * cos_t - std::fabs(h) * sin_t > R) || (h - R > cap);
-                if (!out && Q >= H.n_spheres) {
-                    const double *pl = blob + H.off_planar + 16u * (Q - H.n_spheres);
-                    const uint32_t nv = pl[12] == 3. ? 3u : pl[12] == 4. ? 4u : 0u;   // 0: no lifted vertices
-                    rm_vec3 w[4];
-                    bool fin = nv != 0u;
-                    for (uint32_t i = 0; i < nv; i++) { w[i] = v3(pl[3 * i], pl[3 * i + 1], pl[3 * i + 2]) - L; fin = fin && finite3(w[i]); }
-                    if (fin) {
-                        PlaneSep sep;
-                        try_plane(sep, a, w, nv, cl, r, a, sin_t, marg);
-                        try_plane(sep, v3(1., 0., 0.), w, nv, cl, r, a, sin_t, marg);
-                        try_plane(sep, v3(0., 1., 0.), w, nv, cl, r, a, sin_t, marg);
-                        try_plane(sep, v3(0., 0., 1.), w, nv, cl, r, a, sin_t, marg);
-                        try_plane(sep, cross(w[1] - w[0], w[2] - w[0]), w, nv, cl, r, a, sin_t, marg);
-                        for (uint32_t i = 0; i < nv; i++) try_plane(sep, cross(w[i], w[(i + 1u) % nv]), w, nv, cl, r, a, sin_t, marg);
-                        out = sep.h && sep.n;
-                    }
-                }
-                if (!out) keep |= 1ull << Q;
-            }
-            m = keep;
-        }
-    }
-}
-
-// ---- empty half-spaces of the planar primitives (rm_internal.h: the glass word; rm_render_kernel.inc render_tile) --------
-// A child ray of a hit on a polygon or triangle P (optics.rs:8-89) starts 1e-4 of P's normal off the hit point, on the side
-// its direction d points to (:41-45, :82-86: the side sign(d . normal)), and never comes back to P's plane.  Where every other
-// primitive lies strictly on the OTHER side of that plane such a ray can hit nothing: not P -- its test rejects a ray that
-// runs away from its plane on the sign of the very same dot product -- and nothing else.  The kernel then adds what the
-// ray's own step would have added, weight x background, and does not walk it.
-// sides[P] bit 0: the side P's normal points to is empty, bit 1: the other one.  A primitive Q is on the other side when its
-// lifted vertices (the hull of its hit points) all are, or its bounding sphere is, by
-//   1e-4 + shadow_rho + 1e-7 x (1 + the coordinates' magnitudes)
-// -- the scale of the occluder masks' margins, far beyond the rounding of a hit point.  Anything that is not a finite number,
-// a normal that is not unit to 1e-6, a coordinate of 1e6 and more (the hit points' rounding must stay far below the 1e-4
-// offset) leaves both bits clear.  Primitives that can never be hit (radius -1) are ignored and get no bits themselves.
-void rm_build_empty_sides(const double *blob, const rm_dev_header &H, unsigned char *sides) {
-    const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
-    const double rho = H.shadow_rho, big = 1e6;
-    auto finite3 = [](rm_vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
-    auto mag = [](rm_vec3 v) { return std::fabs(v.x) + std::fabs(v.y) + std::fabs(v.z); };
-    for (uint32_t P = 0; P < n; P++) sides[P] = 0;
-    if (!(rho >= 0.) || !std::isfinite(rho)) return;
-    for (uint32_t P = H.n_spheres; P < n; P++) {
-        const double *rec = P < H.n_spheres + H.n_polygons ? blob + H.off_polygons + RM_POLYGON_WORDS * (P - H.n_spheres)
-                                                           : blob + H.off_triangles + RM_TRIANGLE_WORDS * (P - H.n_spheres - H.n_polygons);
-        const rm_vec3 nrm = v3(rec[0], rec[1], rec[2]), pp = v3(rec[3], rec[4], rec[5]);
-        const double *bp = blob + H.off_bounds + 4u * P;
-        const rm_vec3 c = v3(bp[0], bp[1], bp[2]);
-        if (!(bp[3] >= 0.) || !std::isfinite(bp[3]) || !finite3(c) || !finite3(nrm) || !finite3(pp)) continue;
-        if (!(std::fabs(std::sqrt(dot(nrm, nrm)) - 1.) <= 1e-6)) continue;
-        if (!(mag(c) + bp[3] < big) || !(mag(pp) < big)) continue;
-        bool pos = true, neg = true;                                  // the side the normal points to / the other one is empty
-        for (uint32_t Q = 0; Q < n && (pos || neg); Q++) {
-            if (Q == P) continue;
-            const double *bq = blob + H.off_bounds + 4u * Q;
-            if (bq[3] < 0.) continue;                                 // never hit
-            const rm_vec3 cq = v3(bq[0], bq[1], bq[2]);
-            if (!std::isfinite(bq[3]) || !finite3(cq) || !(mag(cq) + bq[3] < big)) { pos = neg = false; break; }
-            // by its bounding sphere
-            const double marg = 1e-4 + rho + 1e-7 * (1. + mag(pp) + mag(cq) + bq[3]);
-            const double h = dot(cq - pp, nrm);
-            bool below = h + bq[3] < -marg, above = h - bq[3] > marg;
-            // ... or by its lifted vertices, all of them
-            if (!below && !above && Q >= H.n_spheres) {
-                const double *pl = blob + H.off_planar + 16u * (Q - H.n_spheres);
-                const uint32_t nv = pl[12] == 3. ? 3u : pl[12] == 4. ? 4u : 0u;   // 0: no lifted vertices
-                bool lo = nv != 0u, hi = nv != 0u;
-                for (uint32_t i = 0; i < nv; i++) {
-                    const rm_vec3 w = v3(pl[3 * i], pl[3 * i + 1], pl[3 * i + 2]);
-                    if (!finite3(w) || !(mag(w) < big)) { lo = hi = false; break; }
-                    const double mw = 1e-4 + rho + 1e-7 * (1. + mag(pp) + mag(w));
-                    const double hw = dot(w - pp, nrm);
-                    lo = lo && hw < -mw;
-                    hi = hi && hw > mw;
-                }
-                below = lo; above = hi;
-            }
-            pos = pos && below;
-            neg = neg && above;
-        }
-        sides[P] = (unsigned char)((pos ? RM_EMPTY_SIDE_POS : 0u) | (neg ? RM_EMPTY_SIDE_NEG : 0u));
-    }
-}
-
 // ---- the oriented camera's host arithmetic (include/rusty_marcher_amd.h, "the oriented camera") ----------------
 // No device, no context: the CPU tests and every binding reach these.
 namespace {

@@ -78,7 +78,7 @@ __device__ __forceinline__ double sqrt_unscaled(double x, double &h) {
 }
 // ... with the compiler's select for 0, -0 and +inf (the root of a tangent ray's discriminant is exactly 0).  The argument is
 // r^2 - d^2 of a sphere test: not below r^2 2^-54 unless it is zero, and the upload keeps r^2 within [2^-600, 2^600]
-// (rm_device.hip scene_exact_only) -- no lane needs a guard.
+// (rm_image.cpp scene_exact_only) -- no lane needs a guard.
 __device__ __forceinline__ double sqrt_discriminant(double x) {
     double h;
     const double r = sqrt_unscaled(x, h);

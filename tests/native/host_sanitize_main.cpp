@@ -1,6 +1,7 @@
 // AddressSanitizer / UBSan exercise of the host half of the C ABI (csrc/rm_scene.cpp):
-// scene builder, OBJ ingest (good and malformed files), status formatting, and the
-// hierarchy builder the upload uses (csrc/rm_bvh.hpp).  CPU only.
+// scene builder, OBJ ingest (good and malformed files), status formatting, the hierarchy
+// builder (csrc/rm_bvh.hpp) and the device image the upload builds from a description, good
+// and bad ones (csrc/rm_image.cpp).  CPU only.
 #include <cassert>
 #include <cstdio>
 #include <cstring>
@@ -10,6 +11,7 @@
 #include "rusty_marcher_amd.h"
 #include "rm_internal.h"
 #include "rm_bvh.hpp"
+#include "rm_image.hpp"
 
 // the device half (rm_device.hip) is not part of this CPU-only build: its one symbol the
 // host half's callers need is the error accessor
@@ -63,6 +65,72 @@ static void check_hierarchy(uint32_t n_prims, uint32_t leaf_size) {
     for (int c : seen) assert(c == 1);
 }
 
+// rm_build_image over a good description, every way the upload and the hooks ask for it: the sections inside the blob,
+// the occluder masks behind total_words, a pid map entry per primitive
+static void check_image(const rm_scene_desc &d) {
+    for (const rm_image_options opt : {rm_image_options{true, true}, rm_image_options{false, true}, rm_image_options{true, false}}) {
+        rm_image img;
+        std::string error;
+        assert(rm_build_image(&d, opt, img, error) == RM_OK && error.empty());
+        const rm_dev_header &H = img.H;
+        const uint32_t n = H.n_spheres + H.n_polygons + H.n_triangles;
+        assert(H.n_spheres <= d.n_spheres && H.n_polygons <= d.n_polygons && H.n_triangles <= d.n_triangles && H.n_lights == d.n_lights);
+        assert(img.pid_map.size() == 2u * n && H.total_words >= 64u && H.total_words % 2u == 0u);
+        assert(img.blob.size() == (H.off_occ ? (size_t)H.total_words + (((size_t)n * H.n_lights + 1u) & ~(size_t)1) : (size_t)H.total_words));
+        assert(!H.off_occ || (opt.shadow_masks && H.off_occ == H.total_words));
+        assert(opt.use_bvh || (!H.off_bvh_spheres && !H.off_bvh_triangles));
+        for (uint32_t q = 0; q < n; q++) assert(img.pid_map[2u * q] < d.n_shapes);
+    }
+}
+
+// ... and over descriptions it must refuse: a status and the upload's text, never a crash
+static void check_refusals(const rm_scene_desc &good) {
+    std::vector<rm_shape_ref> shapes(good.shapes, good.shapes + good.n_shapes);
+    std::vector<rm_polygon> polygons(good.polygons, good.polygons + good.n_polygons);
+    auto refused = [&](const rm_scene_desc &d, const char *text) {
+        rm_image img;
+        std::string error;
+        assert(rm_build_image(&d, rm_image_options{}, img, error) == RM_ERR_INVALID_ARG);
+        assert(error == text);
+    };
+    auto with_shape = [&](size_t at, rm_shape_ref ref, const char *text) {
+        std::vector<rm_shape_ref> edited = shapes;
+        edited[at] = ref;
+        rm_scene_desc d = good;
+        d.shapes = edited.data();
+        refused(d, text);
+    };
+    size_t sphere = shapes.size(), polygon = shapes.size(), mesh = shapes.size();
+    for (size_t i = 0; i < shapes.size(); i++) {
+        if (shapes[i].kind == RM_SHAPE_SPHERE) sphere = i;
+        if (shapes[i].kind == RM_SHAPE_POLYGON) polygon = i;
+        if (shapes[i].kind == RM_SHAPE_MESH) mesh = i;
+    }
+    assert(sphere < shapes.size() && polygon < shapes.size() && mesh < shapes.size() && !polygons.empty());
+    with_shape(sphere, rm_shape_ref{RM_SHAPE_SPHERE, good.n_spheres, 1u, 0u}, "rm_scene_upload: bad sphere ref");
+    with_shape(sphere, rm_shape_ref{RM_SHAPE_SPHERE, 0u, 2u, 0u}, "rm_scene_upload: bad sphere ref");
+    with_shape(polygon, rm_shape_ref{RM_SHAPE_POLYGON, good.n_polygons, 1u, 0u}, "rm_scene_upload: bad polygon ref");
+    with_shape(mesh, rm_shape_ref{RM_SHAPE_MESH, good.n_triangles, 1u, 0u}, "rm_scene_upload: bad mesh ref");
+    with_shape(mesh, rm_shape_ref{RM_SHAPE_MESH, 0xFFFFFFFFu, 2u, 0u}, "rm_scene_upload: bad mesh ref");
+    with_shape(sphere, rm_shape_ref{7u, 0u, 1u, 0u}, "rm_scene_upload: unknown shape kind");
+    const uint32_t ranges[3][2] = {{0u, 2u}, {good.n_polygon_vertices - 1u, 3u}, {0xFFFFFFFFu, 3u}};
+    for (const auto &range : ranges) {
+        std::vector<rm_polygon> edited = polygons;
+        edited[shapes[polygon].first].first_vertex = range[0];
+        edited[shapes[polygon].first].n_vertices = range[1];
+        rm_scene_desc d = good;
+        d.polygons = edited.data();
+        refused(d, "rm_scene_upload: bad polygon vertex range");
+    }
+    rm_scene_desc d = good;
+    d.shapes = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count"); d = good;
+    d.spheres = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count"); d = good;
+    d.polygons = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count"); d = good;
+    d.polygon_vertices = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count"); d = good;
+    d.triangles = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count"); d = good;
+    d.lights = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count");
+}
+
 int main(int argc, char **argv) {
     assert(argc >= 3);
     const std::string cornell = argv[1], tmpdir = argv[2];
@@ -71,6 +139,7 @@ int main(int argc, char **argv) {
     rm_scene_desc d;
     assert(rm_scene_get_desc(s, &d) == RM_OK);
     assert(d.n_shapes == 6 && d.n_lights == 2 && d.n_polygon_vertices == 7);
+    check_image(d);
     rm_vec3 off = {1., 2., 3.};
     assert(rm_scene_offset_shape(s, 5, off) == RM_OK);
     assert(rm_scene_offset_shape(s, 0, off) == RM_ERR_INVALID_ARG);
@@ -88,12 +157,15 @@ int main(int argc, char **argv) {
     assert(rm_scene_add_mesh(s, nullptr, 0, off) == RM_OK);
     assert(rm_scene_get_desc(s, &d) == RM_OK);
     assert(d.n_triangles == 100 && d.n_shapes == 9);
+    check_image(d);                                                     // (a hierarchy over its triangles; beyond the masks' 64 pids)
+    check_refusals(d);
     rm_scene_free(s);
 
     rm_scene *c = nullptr;
     assert(rm_scene_open_obj(cornell.c_str(), &c) == RM_OK);
     assert(rm_scene_get_desc(c, &d) == RM_OK);
     assert(d.n_shapes == 8 && d.n_triangles == 36 && d.n_lights == 2);
+    check_image(d);
     rm_scene_free(c);
 
     // malformed inputs: every one must come back as a status, never as a crash

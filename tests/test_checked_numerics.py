@@ -1,5 +1,5 @@
 """CPU checks of the checked numerics' routing (rm_trace.inc RM_CHECKED: the strict plain-walk kernels' range-free square
-roots and reciprocals): which scenes the upload marks "exact only" (rm_device.hip scene_exact_only), which cameras the launch
+roots and reciprocals): which scenes the upload marks "exact only" (rm_image.cpp scene_exact_only), which cameras the launch
 plan does (rm_plan.cpp rm_camera_exact_only, RM_CHECKED_NUMERICS=0 on top), and the material word that holds 1 / refractive_index
 for reflect_child / refract_child.  The internal exports used here (rmi_upload_numerics, rmi_plan_exact_only) are not part of
 the ABI and need no device.  Bounds, from rm_plan.hpp: every coordinate, radius and light word finite and at most 2^200 in

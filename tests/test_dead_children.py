@@ -1,4 +1,4 @@
-"""CPU checks of the planar primitives' empty half-spaces (rm_build_empty_sides, built at upload): a child ray that
+"""CPU checks of the planar primitives' empty half-spaces (csrc/rm_image.cpp rm_build_empty_sides, at upload): a child ray that
 leaves a glass-like polygon or triangle into a side of its plane that holds nothing is not walked by the plain-walk
 kernels.  The flags of the demo scene are pinned; anything in doubt clears them; and for 200 seeded scenes every ray
 that starts 1e-4 off a flagged side and runs into it misses everything by the oracle's own closest-hit search.  The

@@ -56,7 +56,7 @@ Which probe would catch a margin of zero, path by path (the tests assert the ker
   list-only                                           s70, s132
   oriented                                            s40 and the child-ray scene under a yawed, pitched and rolled basis, probes
                                                       built from the oriented oracle helper's rays (test_oriented)
-  host bounds (rm_device.hip put_bounds,              the t = 4000 probes; vertex lists the hull comment was not written for --
+  host bounds (rm_image.cpp put_bounds,               the t = 4000 probes; vertex lists the hull comment was not written for --
   planar_bounds)                                      bow ties, a dart, a non-convex pentagon, clockwise, twin vertices, same x,
                                                       same y -- as polygons and as moved meshes (test_odd_vertex_lists)
 

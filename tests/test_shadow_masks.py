@@ -1,4 +1,4 @@
-"""CPU checks of the shadow rays' occluder masks (rm_build_shadow_masks, built at upload for the
+"""CPU checks of the shadow rays' occluder masks (csrc/rm_image.cpp rm_build_shadow_masks, at upload, for the
 plain-walk kernels): for random scenes, random hit points on every primitive and the reference's
 shadow-ray construction (renderer.rs:163-174), every primitive the oracle's own intersection test
 reports hit must have its bit in occ[P][light].  The demo scene's table is pinned, so that a looser
