@@ -66,5 +66,6 @@ struct rm_dev_header {
 #define RM_TRIANGLE_WORDS 12u
 #define RM_MATERIAL_WORDS 10u
 #define RM_LIGHT_WORDS 8u
+#define RM_BVH_NODE_WORDS 16u   /* two child boxes, two child refs, two words of padding (rm_bvh.hpp) */
 
 #endif

@@ -617,78 +617,6 @@ __device__ __forceinline__ bool box_hit(const double *b, const RayBox &r, double
 // The builder keeps the depth under 60 (rm_bvh.hpp) and the upload checks it: the 64-entry
 // stack cannot overflow; the guard below is the last line of defence (a wave that would
 // overflow stops descending rather than write beyond its LDS block).
-#if RM_BVH4
-// Four-wide nodes (rm_bvh.hpp): one 256-byte scalar fetch, four slab tests, half the levels of the binary tree -- half the
-// dependent fetches, votes and stack traffic.  Children are visited front to back as the MAJORITY of the wave's rays sees
-// them (three votes at the walk's start: the sign of each ray component; the node says along which axes its halves lie).
-template <class Limit, class Done, class Leaf>
-__device__ __forceinline__ void bvh_walk(const SceneView &sc, uint32_t off, const RayBox &rb, Limit limit, Done done,
-                                         Leaf leaf) {
-    const double *__restrict__ G = sc.G;
-    uint32_t sp = 0;
-    uint32_t cur = 0;                                   // inner node index; the root is node 0
-    // (bit a: most rays run towards +a -- the half with the smaller centroids comes first)
-    const uint32_t fwd = (__popcll(__ballot(rb.ix > 0.)) >= 32 ? 1u : 0u) | (__popcll(__ballot(rb.iy > 0.)) >= 32 ? 2u : 0u) |
-                         (__popcll(__ballot(rb.iz > 0.)) >= 32 ? 4u : 0u);
-    for (;;) {
-        const double *nd = G + off + RM_BVH_NODE_WORDS * cur;
-        const double boxes[24] = {nd[0], nd[1], nd[2], nd[3], nd[4], nd[5], nd[6], nd[7], nd[8], nd[9], nd[10], nd[11],
-                                  nd[12], nd[13], nd[14], nd[15], nd[16], nd[17], nd[18], nd[19], nd[20], nd[21], nd[22], nd[23]};
-        const uint32_t *refs = reinterpret_cast<const uint32_t *>(nd + 24);
-        const uint32_t idx[4] = {refs[0], refs[2], refs[4], refs[6]}, cnt[4] = {refs[1], refs[3], refs[5], refs[7]};
-        const uint32_t axes = refs[8];
-        const bool live = !done();
-        if (!__any(live)) return;
-        const double lim = limit();
-        bool any_c[4];
-        #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            double t;
-            any_c[c] = cnt[c] != ~0u && __any(live & box_hit(boxes + 6 * c, rb, lim, t));
-        }
-        // front to back: the near half first, within a half its near child first
-        const uint32_t near_half = ((fwd >> (axes & 3u)) & 1u) ? 0u : 1u;
-        uint32_t order[4];
-        #pragma unroll
-        for (uint32_t h = 0; h < 2u; h++) {
-            const uint32_t half = h ? 1u - near_half : near_half;
-            const uint32_t near_child = ((fwd >> ((axes >> (2u + 2u * half)) & 3u)) & 1u) ? 0u : 1u;
-            order[2u * h] = 2u * half + near_child;
-            order[2u * h + 1u] = 2u * half + 1u - near_child;
-        }
-        // the far ones are parked on the wave's stack, farthest first (entry: bit 31 = leaf, bits 30:29 = count - 1,
-        // bits 28:0 = first primitive or node index); the nearest is taken at once
-        bool have = false;
-        uint32_t take_idx = 0u, take_cnt = 0u;
-        #pragma unroll
-        for (int k = 3; k >= 0; k--) {
-            const uint32_t c = order[k];
-            // (a uniform pick among four: compares, no indexing of registers)
-            const bool hit = c == 0u ? any_c[0] : c == 1u ? any_c[1] : c == 2u ? any_c[2] : any_c[3];
-            const uint32_t ci = c == 0u ? idx[0] : c == 1u ? idx[1] : c == 2u ? idx[2] : idx[3];
-            const uint32_t cc = c == 0u ? cnt[0] : c == 1u ? cnt[1] : c == 2u ? cnt[2] : cnt[3];
-            if (hit) {
-                if (have) {
-                    if (sp >= 64u) return;                        // cannot happen (depth checked at upload)
-                    sc.bstack[sp++] = take_cnt ? (0x80000000u | ((take_cnt - 1u) << 29) | take_idx) : take_idx;
-                }
-                take_idx = ci; take_cnt = cc; have = true;
-            }
-        }
-        bool descended = false;
-        if (have) {
-            if (take_cnt) leaf(take_idx, take_cnt);
-            else { cur = take_idx; descended = true; }
-        }
-        while (!descended) {
-            if (sp == 0) return;
-            const uint32_t e = __builtin_amdgcn_readfirstlane(sc.bstack[--sp]);
-            if (e & 0x80000000u) leaf(e & 0x1FFFFFFFu, ((e >> 29) & 3u) + 1u);
-            else { cur = e; descended = true; }
-        }
-    }
-}
-#else
 template <class Limit, class Done, class Leaf>
 __device__ __forceinline__ void bvh_walk(const SceneView &sc, uint32_t off, const RayBox &rb, Limit limit, Done done,
                                          Leaf leaf) {
@@ -741,8 +669,6 @@ __device__ __forceinline__ void bvh_walk(const SceneView &sc, uint32_t off, cons
         }
     }
 }
-
-#endif
 
 // ---- closest hit ---------------------------------------------------------
 struct ClosestState {
