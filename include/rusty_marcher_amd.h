@@ -758,6 +758,75 @@ rm_status rm_refine_device(rm_ctx *ctx, const rm_params *params, const rm_refine
 rm_status rm_render_antialiased(rm_ctx *ctx, const rm_params *params, const rm_refine *refine, double *host_rgb,
                                 uint32_t *n_refined /* optional */, rm_timing *timing /* optional */);
 
+/* ---- thin-lens camera: depth-of-field frames sampled and resolved on the device -------------
+ * Every camera above is a point.  These calls render a frame through a lens of radius `aperture`
+ * that is sharp at the distance `focus` along the context's forward direction: n_samples rays a
+ * pixel, each through a point of the lens of its own, formed, shaded and averaged on the device --
+ * no ray list, no sample in global memory.  Additive to ABI version 5; a host detects them by
+ * " lens" in rm_build_info().
+ *
+ * A sample table is n_samples rows of four doubles (dx, dy, u, v): (dx, dy) a sub-pixel offset,
+ * 0 <= dx, dy < 1, and (u, v) a point of the unit disc, u*u + v*v <= 1.  Let rows = frame_height -
+ * frame_height % 32.  For pixel (x, y), y < rows, and table row s:
+ *
+ *   1. Direction.  sx = x + dx, sy = y + dy; D is the un-normalised direction of the "sample rays"
+ *      rule above at (sx, sy): per component (bx * right + by * up) + forward with the context's
+ *      basis, exactly (bx, by, -1) under a context that is not oriented.  The forward component of
+ *      D in the camera frame is exactly 1, so cam + D * focus lies in the plane in focus.
+ *   2. Focus point.  Per component F.c = cam.c + D.c * focus: one product and one sum, each
+ *      rounded once, no fused multiply-add.
+ *   3. Lens point.  au = aperture * u, av = aperture * v; per component
+ *      O.c = cam.c + ((au * right.c) + (av * up.c)), the fixed view's right (1,0,0) and up (0,1,0)
+ *      under a context that is not oriented.
+ *   4. Ray.  Origin O, direction normalized(F - O).  Exception: when aperture == 0 the ray is the
+ *      sample ray itself, origin cam and direction normalized(D).  A lens frame with aperture 0 and
+ *      the table (i/n, j/n, 0, 0), j outer and i inner, is therefore the supersampled frame: byte
+ *      for byte what rm_refine_device leaves at a negative threshold.
+ *   5. Radiance.  What rm_radiance_rays returns for that ray with params' max_depth and background:
+ *      n_recursion = 1, a primary ray that leaves the scene returns (+0, +0, +0), the strict
+ *      flavour, occluder masks off.
+ *   6. Pixel value.  The samples are summed per channel in table order by plain additions and the
+ *      sum is divided once by (double)n_samples.  max_depth == 0 writes the background.
+ *   7. Rows from `rows` on are neither read nor written.  Render state is neither read nor
+ *      written; the context's camera position and basis are read, nothing else of the context.
+ *
+ * rm_lens_table fills the library's own table, host arithmetic only (no context, no GPU, no libm
+ * beyond sqrt), every operation rounded once in this order: m = ceil(sqrt(n_samples)) as an
+ * integer; row s has i = s % m, j = s / m, dx = i / m, dy = j / m; the lens cell is decorrelated
+ * from the pixel cell, a = (2*j + 1) / m - 1, b = (2*(m - 1 - i) + 1) / m - 1, and mapped to the
+ * disc by u = a * sqrt(1 - b*b/2), v = b * sqrt(1 - a*a/2).  n_samples == 1 gives (0, 0, 0, 0).
+ * n_samples outside 1..64 or a NULL table is RM_ERR_INVALID_ARG.
+ *
+ * rm_render_lens_device is asynchronous on hip_stream: no host synchronisation.  device_table is
+ * n_samples * 4 doubles in device memory (rm_buffer_alloc / rm_buffer_write), device_rgb is
+ * [frame_height][frame_width][3] doubles, the plain layout.  The table's contents are a
+ * precondition here: a bad row gives unspecified pixels, never a fault.  rm_render_lens takes the
+ * table from host memory, checks every entry of it (finite, 0 <= dx, dy < 1, u*u + v*v <= 1 +
+ * 1e-12), stages it into a buffer the context owns, renders on the context's stream into a lens
+ * frame the context owns (grown on demand, freed by rm_destroy; not the resident frame of
+ * rm_render), copies the rows [0, rows) to host_rgb and blocks.  timing->kernel_ms is the launch.
+ *
+ * Checked before anything is launched, the offender named in rm_last_error, nothing computed and
+ * the output untouched: everything rm_refine_device checks of params (RM_ERR_NO_SCENE;
+ * RM_FLAG_FAST_FP tolerated and ignored, any other flag RM_ERR_INVALID_ARG; the default band only;
+ * frame_width % 32 != 0 is RM_ERR_DIMENSIONS, and so is rows * frame_width >= 2^31; max_depth >
+ * RM_MAX_DEPTH is RM_ERR_DEPTH; a finite background); lens, table and frame not NULL; aperture
+ * finite and >= 0; focus finite and > 0; n_samples in 1..64.  rows == 0 is RM_OK and does nothing.
+ */
+typedef struct rm_lens {
+    double   aperture;    /* lens radius, world units; finite, >= 0 */
+    double   focus;       /* distance of the plane in focus along `forward`; finite, > 0 */
+    uint32_t n_samples;   /* rays a pixel, 1..64 */
+    uint32_t _pad;
+} rm_lens;              /* 24 bytes */
+
+/* the library's sample table for n_samples rays a pixel: n_samples * 4 doubles */
+rm_status rm_lens_table(uint32_t n_samples, double *table);
+rm_status rm_render_lens_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                void *device_rgb, void *hip_stream);
+rm_status rm_render_lens(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *table,
+                         double *host_rgb, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

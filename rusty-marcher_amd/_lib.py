@@ -103,6 +103,11 @@ class rm_refine(C.Structure):
     _fields_ = [("n", C.c_uint32), ("_pad", C.c_uint32), ("threshold", C.c_double)]
 
 
+class rm_lens(C.Structure):
+    """The thin lens of a depth-of-field frame: radius, distance of the plane in focus, rays a pixel (24 bytes)."""
+    _fields_ = [("aperture", C.c_double), ("focus", C.c_double), ("n_samples", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class rm_camera_basis(C.Structure):
     """The oriented camera's view direction: three world-space unit vectors (72 bytes)."""
     _fields_ = [("right", rm_vec3), ("up", rm_vec3), ("forward", rm_vec3)]
@@ -192,6 +197,9 @@ SIGNATURES = {
     "rm_refine_workspace": (C.c_int, [_P(rm_params), _P(C.c_size_t)]),
     "rm_refine_device": (C.c_int, [_VP, _P(rm_params), _P(rm_refine), _VP, _VP, _VP, _VP]),
     "rm_render_antialiased": (C.c_int, [_VP, _P(rm_params), _P(rm_refine), _P(C.c_double), _P(C.c_uint32), _P(rm_timing)]),
+    "rm_lens_table": (C.c_int, [C.c_uint32, _P(C.c_double)]),
+    "rm_render_lens_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, _VP]),
+    "rm_render_lens": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), _P(C.c_double), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -70,6 +70,29 @@ def _refine(n, threshold):
     return _lib.rm_refine(int(n), 0, threshold)
 
 
+def _lens(aperture, focus, n_samples):
+    """rm_lens of a depth-of-field call: aperture finite and >= 0, focus finite and > 0, n_samples an integer in 1..64."""
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= 64:
+        raise ValueError("n_samples must be an integer in 1..64, got %r" % (n_samples,))
+    aperture, focus = float(aperture), float(focus)
+    if not (np.isfinite(aperture) and aperture >= 0.):
+        raise ValueError("aperture must be a finite number >= 0, got %r" % (aperture,))
+    if not (np.isfinite(focus) and focus > 0.):
+        raise ValueError("focus must be a finite number > 0, got %r" % (focus,))
+    return _lib.rm_lens(aperture, focus, int(n_samples), 0)
+
+
+def _lens_rows(table, n_samples):
+    """(n_samples, 4) float64 rows (dx, dy, u, v), C-contiguous, with the conditions rm_render_lens checks."""
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    if t.shape != (n_samples, 4):
+        raise ValueError("table must be a float64 array of shape (%d, 4), got %s" % (n_samples, t.shape))
+    ok = np.isfinite(t).all() and (t[:, :2] >= 0.).all() and (t[:, :2] < 1.).all() and (t[:, 2] * t[:, 2] + t[:, 3] * t[:, 3] <= 1. + 1e-12).all()
+    if not ok:
+        raise ValueError("table rows must be finite (dx, dy, u, v) with 0 <= dx, dy < 1 and u*u + v*v <= 1")
+    return t
+
+
 def _device_hits(raw):
     """DeviceHits over a float64 tensor whose last dimension is one rm_hit (9 words)."""
     ints = raw.view(_torch().int32)                       # 18 int32 a record: shape, element, hit are 14, 15, 16
@@ -434,6 +457,56 @@ class Context:
         ptr = host_array.ctypes.data_as(C.POINTER(C.c_double)) if host_array is not None else None
         _lib.check(self.L.rm_render_antialiased(self.ptr, C.byref(params), C.byref(r), ptr, C.byref(count), C.byref(t)), self.ptr)
         return t, count.value
+
+    # ---- thin-lens camera (include/rusty_marcher_amd.h, "thin-lens camera") ----
+    def lens_table(self, n_samples):
+        """rm_lens_table: the library's sample table for n_samples rays a pixel, (n_samples, 4) float64 rows (dx, dy, u, v).
+        Host arithmetic: needs neither a context nor a GPU."""
+        if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= 64:
+            raise ValueError("n_samples must be an integer in 1..64, got %r" % (n_samples,))
+        t = np.zeros((int(n_samples), 4), dtype=np.float64)
+        _lib.check(self.L.rm_lens_table(int(n_samples), t.ctypes.data_as(C.POINTER(C.c_double))), None)
+        return t
+
+    def render_lens_device(self, params, frame_tensor, aperture, focus, table, stream=None):
+        """rm_render_lens_device: a depth-of-field frame into `frame_tensor` -- a contiguous float64 tensor of shape
+        (frame_height, frame_width, 3) on the context's device --, table.shape[0] rays a pixel through a lens of radius
+        `aperture` that is sharp at the distance `focus`; asynchronous on `stream` (torch's current one by default).  table:
+        a contiguous float64 tensor (n_samples, 4) there, or an array, which is checked and copied over.  -> the table's tensor."""
+        torch = _torch()
+        h, w = params.frame_height, params.frame_width
+        if not isinstance(frame_tensor, torch.Tensor) or frame_tensor.dtype != torch.float64 or tuple(frame_tensor.shape) != (h, w, 3) \
+                or not frame_tensor.is_contiguous():
+            raise ValueError("frame_tensor must be a contiguous float64 torch tensor of shape %s" % ((h, w, 3),))
+        if frame_tensor.device.type != "cuda" or frame_tensor.device.index != self.device:
+            raise ValueError("frame_tensor must live on cuda:%d (the context's device), not %s" % (self.device, frame_tensor.device))
+        if isinstance(table, torch.Tensor):
+            if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+                raise ValueError("table must be a contiguous float64 torch tensor of shape (n_samples, 4)")
+            if table.device != frame_tensor.device:
+                raise ValueError("table must live on %s, not %s" % (frame_tensor.device, table.device))
+            lens = _lens(aperture, focus, table.shape[0])
+        else:
+            rows = np.asarray(table)
+            lens = _lens(aperture, focus, rows.shape[0] if rows.ndim == 2 else 0)
+            table = torch.from_numpy(_lens_rows(rows, lens.n_samples)).to(frame_tensor.device)
+        _lib.check(self.L.rm_render_lens_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                C.c_void_p(frame_tensor.data_ptr()), C.c_void_p(self._stream(stream))), self.ptr)
+        return table
+
+    def render_lens(self, params, host_array, aperture, focus, table):
+        """rm_render_lens: the depth-of-field frame of render_lens_device with a host table, (n_samples, 4) float64, copied
+        into host_array (the whole patch rows).  -> rm_timing."""
+        rows = np.asarray(table)
+        lens = _lens(aperture, focus, rows.shape[0] if rows.ndim == 2 else 0)
+        t = _lens_rows(rows, lens.n_samples)
+        if not isinstance(host_array, np.ndarray) or host_array.dtype != np.float64 or not host_array.flags.c_contiguous \
+                or host_array.size < (params.frame_height - params.frame_height % 32) * params.frame_width * 3:
+            raise ValueError("host_array must be a C-contiguous float64 array that holds the frame's whole patch rows")
+        timing = _lib.rm_timing()
+        _lib.check(self.L.rm_render_lens(self.ptr, C.byref(params), C.byref(lens), t.ctypes.data_as(C.POINTER(C.c_double)),
+                                         host_array.ctypes.data_as(C.POINTER(C.c_double)), C.byref(timing)), self.ptr)
+        return timing
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

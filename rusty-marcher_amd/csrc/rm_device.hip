@@ -23,6 +23,7 @@
 #include "rm_query.hpp"
 #include "rm_radiance.hpp"
 #include "rm_refine.hpp"
+#include "rm_lens.hpp"
 
 using namespace rmdev;
 
@@ -208,6 +209,13 @@ struct rm_ctx {
     size_t refine_ws_bytes = 0;
     std::vector<std::pair<const void *, int>> refine_occupancy;
 
+    // the thin-lens camera (rm_lens_host.inc): the table and the frame rm_render_lens renders with (the frame grown on demand),
+    // and what hipOccupancyMaxActiveBlocksPerMultiprocessor said of the lens kernels launched so far
+    void *d_lens_table = nullptr;
+    void *d_lens_frame = nullptr;
+    size_t lens_frame_bytes = 0;
+    std::vector<std::pair<const void *, int>> lens_occupancy;
+
     // post-process scratch
     unsigned long long *d_max = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -297,7 +305,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -373,6 +381,8 @@ void rm_destroy(rm_ctx *ctx) {
         if (ctx->d_pid_map) (void)hipFree(ctx->d_pid_map);
         if (ctx->d_query) (void)hipFree(ctx->d_query);
         if (ctx->d_refine_ws) (void)hipFree(ctx->d_refine_ws);
+        if (ctx->d_lens_table) (void)hipFree(ctx->d_lens_table);
+        if (ctx->d_lens_frame) (void)hipFree(ctx->d_lens_frame);
         if (ctx->d_max) (void)hipFree(ctx->d_max);
         if (ctx->d_redo) (void)hipFree(ctx->d_redo);
         if (ctx->d_rgb8) (void)hipFree(ctx->d_rgb8);
@@ -1077,3 +1087,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_query_host.inc"
 #include "rm_radiance_host.inc"
 #include "rm_refine_host.inc"
+#include "rm_lens_host.inc"

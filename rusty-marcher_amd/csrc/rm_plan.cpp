@@ -92,6 +92,7 @@ const knob k_knobs[] = {
     {"RM_CULL_EDGES", &rm_knobs::cull_edges, NOT_0},
     {"RM_CHECKED_NUMERICS", &rm_knobs::checked_numerics, NOT_0},
     {"RM_REFINE_MAX_BLOCKS", &rm_knobs::refine_max_blocks, ATOI_MIN_0},
+    {"RM_LENS_MAX_BLOCKS", &rm_knobs::lens_max_blocks, ATOI_MIN_0},
     {"RM_DEBUG_TAIL", &rm_knobs::debug_tail, IS_SET},
 };
 

@@ -403,6 +403,25 @@ struct Renderer {
             }
         return status(t0, frame.width, frame.height);
     }
+    // render() through a thin lens (rm_render_lens): n_samples rays a pixel (1..64), each from a point of its own of a lens of
+    // radius `aperture` towards the point its sample ray reaches at the distance `focus` along the view direction.  The sample
+    // table is the library's (rm_lens_table); sampled, shaded and averaged on the device.  Fills the whole patch rows of `frame`.
+    std::string render_lens(framebuffer::FrameBuffer &frame, const scene::Scene &sc, double aperture, double focus, uint32_t n_samples) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        std::vector<double> table(4 * 64);                                                  // (room for the most rows there can be)
+        check(rm_lens_table(n_samples, table.data()));
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_lens(ctx_, &p, &lens, table.data(), flat.data(), &last_timing), ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
     void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }

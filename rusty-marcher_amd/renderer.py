@@ -118,6 +118,35 @@ class Renderer:
         print("%d compute units used" % info["cus"])
         return message
 
+    def render_depth_of_field(self, frame, scene, aperture, focus, n_samples):
+        """render() through a thin lens (rm_render_lens): n_samples rays a pixel, each from a point of its own of a lens of
+        radius `aperture` towards the point its sample ray reaches at the distance `focus` along the view direction, so
+        what lies at that distance is sharp and the rest blurs with the aperture.  The sample table is the library's
+        (rm_lens_table); sampled, shaded and averaged on the device.  The whole patch rows of frame.buffer are filled, rows
+        from height - height % 32 on are left untouched.  Prints and returns what render() does."""
+        backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        t0 = time.perf_counter()
+        ctx = backend.default_context(self.device)
+        if frame.height % 32 != 0 or frame.width % 32 != 0:
+            print("Dimensions mismatch")                                   # renderer.rs:49-51
+        n_patches = (frame.height // 32) * (frame.width // 32)
+        print("Rendering using patches of size %d, using %d patches overall" % (32, n_patches))
+
+        p = backend.make_params(self.fov, self.height, self.width, self.max_depth)
+        p.frame_width, p.frame_height = frame.width, frame.height
+        ctx.upload(scene.flatten())
+        ctx.orient(getattr(scene, "basis", None))
+        self.last_timing = ctx.render_lens(p, frame.buffer, aperture, focus, ctx.lens_table(n_samples))
+
+        ms = int((time.perf_counter() - t0) * 1000.)
+        buf = C.create_string_buffer(256)
+        _lib.lib().rm_format_status(buf, 256, ms, frame.width, frame.height)
+        message = buf.value.decode()
+        print(message)
+        info = ctx.device_info()
+        print("%d compute units used" % info["cus"])
+        return message
+
     def pick(self, frame, scene, x, y):
         """What render(frame, scene) shows at pixel (x = column, y = row): the closest hit of the ray renderer.rs:80
         casts there (bit for bit the strict render's direction), or None where that ray leaves the scene."""

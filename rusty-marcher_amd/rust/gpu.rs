@@ -149,6 +149,17 @@ pub struct RmRefine {
     pub threshold: f64,
 }
 
+/// `rm_lens`: the thin lens of a depth-of-field frame -- its radius, the distance of the plane in focus along the view
+/// direction, rays a pixel (1..64) (24 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmLens {
+    pub aperture: f64,
+    pub focus: f64,
+    pub n_samples: u32,
+    pub _pad: u32,
+}
+
 /// `rm_lights_visible`'s modes: the decision direct_lighting takes / the shadow ray ended at the light.
 pub const RM_LIGHTS_AS_RENDERED: u32 = 0;
 pub const RM_LIGHTS_CLIPPED: u32 = 1;
@@ -252,6 +263,9 @@ extern "C" {
     fn rm_refine_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
     fn rm_refine_device(ctx: *mut RmCtx, params: *const RmParams, refine: *const RmRefine, device_rgb: *mut c_void, device_workspace: *mut c_void, device_mask: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_antialiased(ctx: *mut RmCtx, params: *const RmParams, refine: *const RmRefine, host_rgb: *mut f64, n_refined: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_lens_table(n_samples: u32, table: *mut f64) -> c_int;
+    fn rm_render_lens_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_lens(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, table: *const f64, host_rgb: *mut f64, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -433,6 +447,44 @@ impl Gpu {
             }
         }
         (Gpu::status(now, frame.width, frame.height), refined)
+    }
+
+    /// `render` through a thin lens: `n_samples` rays a pixel (1..64), each from a point of its own of a lens of radius
+    /// `aperture` towards the point its sample ray reaches at the distance `focus` along the view direction -- what lies at
+    /// that distance is sharp, the rest blurs with the aperture.  The sample table is the library's (`rm_lens_table`);
+    /// sampled, shaded and averaged on the GPU in one library call.  Fills the whole patch rows of `frame.buffer`.
+    pub fn render_lens(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+    ) -> String {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let mut table = vec![0f64; 4 * 64]; // (room for the most rows there can be)
+        check(unsafe { rm_lens_table(n_samples, table.as_mut_ptr()) }, ptr::null());
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let mut timing = RmTiming::default();
+        check(
+            unsafe { rm_render_lens(self.ctx, &p, &lens, table.as_ptr(), flat.as_mut_ptr(), &mut timing) },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        Gpu::status(now, frame.width, frame.height)
     }
 
     /// `render` with a device-resident FrameBuffer: the f64 frame stays on the GPU and only
