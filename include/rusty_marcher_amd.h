@@ -827,6 +827,78 @@ rm_status rm_render_lens_device(rm_ctx *ctx, const rm_params *params, const rm_l
 rm_status rm_render_lens(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *table,
                          double *host_rgb, rm_timing *timing /* optional */);
 
+/* ---- progressive frames: lens samples accumulated across calls on the device ----------------
+ * A lens frame is finished in one call, with at most 64 samples a pixel.  These calls refine a
+ * standing view instead: every call casts a few more samples and continues a per-pixel sum, so a
+ * viewer adds samples a tick while nothing moves and starts again when anything does.  Additive to
+ * ABI version 5; a host detects them by " progressive" in rm_build_info().
+ *
+ * rm_lens_sequence fills rows first .. first + count - 1 of one fixed sample sequence, count * 4
+ * doubles (dx, dy, u, v) per the sample table's conventions above; every prefix of the sequence is
+ * well spread.  Host arithmetic only (no context, no GPU, no libm beyond sqrt), every operation
+ * rounded once in this order.  For index s and base b, in uint64_t: r = 0, q = 1; while s > 0:
+ * r = r*b + s % b, q *= b, s /= b; phi_b(s) = (double)r / (double)q, one division (s = 0 gives 0).
+ * Row s is dx = phi_2(s), dy = phi_3(s); a = 2. * phi_5(s) - 1., b = 2. * phi_7(s) - 1.;
+ * u = a * sqrt(1. - b*b/2.), v = b * sqrt(1. - a*a/2.), the map of rm_lens_table.  Row 0 is
+ * (0, 0, -sqrt(.5), -sqrt(.5)); every row satisfies the table conditions rm_render_lens checks.
+ * first + count > RM_PROGRESSIVE_MAX_SAMPLES is RM_ERR_INVALID_ARG; count == 0 is RM_OK, nothing is
+ * written and table may be NULL; a NULL table with count > 0 is RM_ERR_INVALID_ARG.
+ *
+ * rm_accumulate_lens_device is asynchronous on hip_stream: no host synchronisation.  It neither
+ * reads nor writes render state, as rm_render_lens_device.  lens->n_samples (1..64) rows of
+ * device_table are cast for every pixel of [0, rows) x [0, frame_width), rows = frame_height -
+ * frame_height % 32; rays and radiance are exactly steps 1-5 of the thin-lens camera, the
+ * aperture == 0 exception included.  device_sum, device_mean and device_rgb8 are
+ * [frame_height][frame_width][3] in the plain layout, the first two of doubles, the third of bytes:
+ *
+ *   Sum.    Per channel, S starts as device_sum[pix] when n_before > 0.  When n_before == 0 it
+ *           starts as the first sample itself, and device_sum is not read and may hold anything.
+ *           The remaining samples are added in table order by plain additions, and S is stored to
+ *           device_sum[pix].
+ *   Mean.   S / (double)(n_before + n_samples), one division, is stored to device_mean where given.
+ *   Bytes.  (uint8_t)(255. * fmin(fmax(mean, 0.), 1.)) per channel -- to_vec, the rule of the
+ *           display bytes of rm_render_display -- is stored to device_rgb8 where given.
+ *   max_depth == 0: every sample is the background.
+ *   Rows from `rows` on are neither read nor written in any of the three buffers.
+ *
+ * So with n_before == 0, device_mean is byte for byte what rm_render_lens_device writes for the
+ * same table; and passes over consecutive slices of one table T of at most 64 rows, each taking the
+ * previous total as n_before, are the same left fold as one lens launch: the last device_mean is
+ * byte for byte the lens frame of T.
+ *
+ * Checked before anything is launched, the offender named in rm_last_error, nothing computed and
+ * no buffer touched: everything rm_render_lens_device checks of params and lens; device_table and
+ * device_sum not NULL; device_mean != device_sum; n_before + n_samples <=
+ * RM_PROGRESSIVE_MAX_SAMPLES, else RM_ERR_INVALID_ARG.  rows == 0 is RM_OK and does nothing.
+ *
+ * rm_render_progressive is the call a viewer makes every tick.  The context owns a sum, a mean and
+ * a byte buffer (grown on demand, freed by rm_destroy; not the resident frame of rm_render and not
+ * the lens frame of rm_render_lens), a staged table, the number N of samples in the sum and a key:
+ * the bytes of params' fov, half_fov, height, width, ratio, frame_width, frame_height, max_depth and
+ * background, of lens->aperture and lens->focus, of the context's camera position, oriented flag
+ * and basis, and of the `copies` counter of rm_scene_uploads.  RM_FLAG_FAST_FP is tolerated,
+ * ignored and not part of the key.  If restart != 0, or the key differs from the previous
+ * successful call's, or there was none, N = 0.  The call stages rows [N, N + n_samples) of
+ * rm_lens_sequence, launches the accumulation on the context's stream with n_before = N, sets
+ * N += n_samples, copies the rows [0, rows) of the mean to host_rgb and of the bytes to host_rgb8
+ * where given and the total to *n_total, and blocks until all that is done.  If N + n_samples >
+ * RM_PROGRESSIVE_MAX_SAMPLES nothing is launched, the outputs are the frame as it stands and the
+ * call returns RM_OK with *n_total = N: ticking a converged picture is not an error.  The checks
+ * are the device call's of params and lens; a refused call changes neither N nor the key.  rows == 0
+ * is RM_OK, does nothing and reports a total of 0.  timing->kernel_ms is the launch.  The call
+ * changes no frame any other entry point produces and leaves the launch and upload counters of
+ * renders alone, as the lens calls do.
+ */
+#define RM_PROGRESSIVE_MAX_SAMPLES 65536u
+
+rm_status rm_lens_sequence(uint32_t first, uint32_t count, double *table);
+rm_status rm_accumulate_lens_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                    uint32_t n_before, void *device_sum, void *device_mean /* optional */,
+                                    void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_render_progressive(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, int restart,
+                                double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                uint32_t *n_total /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

@@ -82,6 +82,9 @@ def _lens(aperture, focus, n_samples):
     return _lib.rm_lens(aperture, focus, int(n_samples), 0)
 
 
+PROGRESSIVE_MAX_SAMPLES = 65536            # RM_PROGRESSIVE_MAX_SAMPLES: samples a pixel a progressive frame can hold
+
+
 def _lens_rows(table, n_samples):
     """(n_samples, 4) float64 rows (dx, dy, u, v), C-contiguous, with the conditions rm_render_lens checks."""
     t = np.ascontiguousarray(table, dtype=np.float64)
@@ -507,6 +510,73 @@ class Context:
         _lib.check(self.L.rm_render_lens(self.ptr, C.byref(params), C.byref(lens), t.ctypes.data_as(C.POINTER(C.c_double)),
                                          host_array.ctypes.data_as(C.POINTER(C.c_double)), C.byref(timing)), self.ptr)
         return timing
+
+    # ---- progressive frames (include/rusty_marcher_amd.h, "progressive frames") ----
+    def lens_sequence(self, first, count):
+        """rm_lens_sequence: rows first .. first + count - 1 of the library's unbounded sample sequence, (count, 4) float64 rows
+        (dx, dy, u, v); every prefix is well spread.  Host arithmetic: needs neither a context nor a GPU."""
+        for name, v in (("first", first), ("count", count)):
+            if isinstance(v, bool) or int(v) != v or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        if first + count > PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+        t = np.zeros((int(count), 4), dtype=np.float64)
+        _lib.check(self.L.rm_lens_sequence(int(first), int(count), t.ctypes.data_as(C.POINTER(C.c_double))), None)
+        return t
+
+    def accumulate_lens_device(self, params, sum, aperture, focus, table, n_before, mean=None, rgb8=None, stream=None):
+        """rm_accumulate_lens_device: table.shape[0] more lens samples a pixel added to `sum`, which holds n_before a pixel
+        already (0: it is not read) -- a contiguous float64 tensor of shape (frame_height, frame_width, 3) on the context's
+        device.  mean: optionally a float64 tensor of that shape for sum / (n_before + n_samples); rgb8: optionally a uint8
+        tensor of that shape for the mean's display bytes.  Asynchronous on `stream` (torch's current one by default).
+        table: as render_lens_device's.  -> the table's tensor."""
+        torch = _torch()
+        h, w = params.frame_height, params.frame_width
+        for name, t, dtype in (("sum", sum, torch.float64), ("mean", mean, torch.float64), ("rgb8", rgb8, torch.uint8)):
+            if t is None and name != "sum":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (h, w, 3) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, (h, w, 3)))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
+        if mean is not None and mean.data_ptr() == sum.data_ptr():
+            raise ValueError("mean must not be the sum's own tensor")
+        if isinstance(n_before, bool) or int(n_before) != n_before or n_before < 0:
+            raise ValueError("n_before must be a non-negative integer, got %r" % (n_before,))
+        if isinstance(table, torch.Tensor):
+            if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+                raise ValueError("table must be a contiguous float64 torch tensor of shape (n_samples, 4)")
+            if table.device != sum.device:
+                raise ValueError("table must live on %s, not %s" % (sum.device, table.device))
+            lens = _lens(aperture, focus, table.shape[0])
+        else:
+            rows = np.asarray(table)
+            lens = _lens(aperture, focus, rows.shape[0] if rows.ndim == 2 else 0)
+            table = torch.from_numpy(_lens_rows(rows, lens.n_samples)).to(sum.device)
+        if n_before + lens.n_samples > PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("n_before + n_samples must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, n_before, lens.n_samples))
+        _lib.check(self.L.rm_accumulate_lens_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()), int(n_before),
+                                                    C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                    C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                    C.c_void_p(self._stream(stream))), self.ptr)
+        return table
+
+    def render_progressive(self, params, aperture, focus, n_samples, restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_progressive: n_samples more samples a pixel of the library's sequence into the frame the context keeps
+        for the standing view -- begun again when `restart` is set or the view, the lens or the scene changed --, its mean
+        copied into host_rgb (float64) and its display bytes into host_rgb8 (uint8) where given: C-contiguous arrays that hold
+        the frame's whole patch rows.  -> (rm_timing, samples a pixel in the frame now)."""
+        lens = _lens(aperture, focus, n_samples)
+        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
+        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
+                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        timing, total = _lib.rm_timing(), C.c_uint32(0)
+        _lib.check(self.L.rm_render_progressive(self.ptr, C.byref(params), C.byref(lens), 1 if restart else 0,
+                                                host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
+                                                host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
+                                                C.byref(total), C.byref(timing)), self.ptr)
+        return timing, total.value
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

@@ -1,0 +1,209 @@
+// rm_accum_host.inc -- host side of the progressive frames (include/rusty_marcher_amd.h, "progressive frames"); included at the
+// end of rm_device.hip, behind rm_lens_host.inc whose checks (check_lens), argument block (lens_args), grid (lens_grid, with
+// RM_LENS_MAX_BLOCKS) and occupancy cache it reuses.  The kernel is rm_accum.hip's.
+//
+// rm_accumulate_lens_device touches no render state and keeps none of its own: one launch on the caller's stream, nothing
+// waited for.  rm_render_progressive is that on the context's stream with a staged slice of rm_lens_sequence and three
+// buffers the context owns (sum, mean, bytes: not the resident frame, not the lens frame), the count of samples in the sum
+// and the key that says which view the sum belongs to.
+
+// phi_b(s): the digits of s in base b mirrored at the point, as the integer pair (r, q) -- r / q is the value
+static void digit_reversed(uint32_t s, uint32_t b, uint64_t *r, uint64_t *q) {
+    uint64_t rr = 0, qq = 1;
+    while (s > 0u) {
+        rr = rr * b + s % b;
+        qq *= b;
+        s /= b;
+    }
+    *r = rr;
+    *q = qq;
+}
+
+static double radical_inverse(uint32_t s, uint32_t b) {
+    uint64_t r, q;
+    digit_reversed(s, b, &r, &q);
+    return (double)r / (double)q;
+}
+
+// What both entry points check of params and lens (ctx is not NULL): check_lens with a table and a frame that are there.
+static rm_status check_accum(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens) {
+    const char present = 0;
+    return check_lens(ctx, who, p, lens, &present, &present);
+}
+
+// The launch on `stream`; everything was checked, rows > 0.
+static rm_status launch_accum(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, uint32_t n_before, void *sum,
+                              void *mean, void *rgb8, hipStream_t stream) {
+    AccumArgs a{};
+    a.L = lens_args(ctx, p, lens, table, nullptr);
+    a.n_before = n_before;
+    a.sum = static_cast<double *>(sum);
+    a.mean = static_cast<double *>(mean);
+    a.rgb8 = static_cast<uint8_t *>(rgb8);
+
+    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (launch_lens's rules)
+    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
+    const void *fn = rm_accum_kernel(bvh, pow_mode, a.L.max_depth <= 5u ? 4 : 32);
+    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "progressive: no such kernel");
+    uint32_t grid = 0;
+    if (rm_status gst = lens_grid(ctx, fn, a.L.rows * a.L.frame_width, a.L.n_samples, &grid)) return gst;
+    void *args[] = {(void *)&ctx->d_scene, (void *)&a};
+    RM_HIP(ctx, hipLaunchKernel(fn, dim3(grid), dim3(64), args, 0, stream));
+    return RM_OK;
+}
+
+static rm_status rm_accumulate_lens_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table,
+                                                uint32_t n_before, void *device_sum, void *device_mean, void *device_rgb8, void *hip_stream) {
+    const char *who = "rm_accumulate_lens_device";
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
+    if (!device_table) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL table");
+    if (!device_sum) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL sum");
+    if (device_mean == device_sum) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": the mean would overwrite the sum (device_mean == device_sum)");
+    if ((uint64_t)n_before + lens->n_samples > RM_PROGRESSIVE_MAX_SAMPLES) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "%s: n_before + n_samples = %u + %u is more than %u", who, n_before, lens->n_samples, RM_PROGRESSIVE_MAX_SAMPLES);
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+    }
+    if (refine_rows(p) == 0u) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_accum(ctx, p, lens, device_table, n_before, device_sum, device_mean, device_rgb8, (hipStream_t)hip_stream);
+}
+
+// The view a sum belongs to, byte for byte (no padding: doubles and pairs of words)
+struct rm_progressive_key {
+    double fov, half_fov, height, width, ratio;
+    uint32_t frame_width, frame_height, max_depth, oriented;
+    rm_vec3 background;
+    double aperture, focus;
+    rm_vec3 camera;
+    rm_camera_basis basis;
+    uint64_t copies;
+};
+
+// The progressive state of a context (rm_ctx::progressive; made on the first call, released by rm_destroy)
+struct rm_progressive {
+    void *d_table = nullptr;                 // RM_LENS_MAX_SAMPLES rows
+    void *d_sum = nullptr, *d_mean = nullptr, *d_rgb8 = nullptr;
+    size_t pixels = 0;                       // the three buffers have room for that many
+    double table[RM_LENS_MAX_SAMPLES * 4u];  // the slice as staged
+    bool have_key = false;                   // a call has succeeded, and nothing failed half-way since
+    rm_progressive_key key;
+    uint32_t n = 0;                          // samples a pixel in the sum
+};
+
+static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
+    rm_progressive *g = ctx->progressive;
+    if (!g) return;
+    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8})
+        if (b && device_ok) (void)hipFree(b);
+    delete g;
+    ctx->progressive = nullptr;
+}
+
+static rm_status rm_render_progressive_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, int restart, double *host_rgb,
+                                            uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
+    const char *who = "rm_render_progressive";
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
+    const uint32_t rows = refine_rows(p);
+    double kernel_ms = 0., d2h_ms = 0.;
+    uint32_t total = 0u;
+    if (rows > 0u) {
+        if (!ctx->progressive) ctx->progressive = new rm_progressive();
+        rm_progressive &g = *ctx->progressive;
+        rm_progressive_key key;
+        std::memset(&key, 0, sizeof key);
+        key.fov = p->fov; key.half_fov = p->half_fov; key.height = p->height; key.width = p->width; key.ratio = p->ratio;
+        key.frame_width = p->frame_width; key.frame_height = p->frame_height; key.max_depth = p->max_depth;
+        key.oriented = ctx->oriented ? 1u : 0u;
+        key.background = p->background;
+        key.aperture = lens->aperture; key.focus = lens->focus;
+        key.camera = ctx->camera;
+        key.basis = ctx->basis;
+        key.copies = ctx->upload_copies;
+        const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0;
+        const uint32_t n_before = same ? g.n : 0u;
+        const size_t pixels = (size_t)rows * p->frame_width;
+        const bool saturated = n_before + lens->n_samples > RM_PROGRESSIVE_MAX_SAMPLES;   // (then n_before > 0: the frame stands)
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        if (!saturated) {
+            g.have_key = false;                                            // (until this call is through)
+            if (!g.d_table) RM_HIP(ctx, hipMalloc(&g.d_table, sizeof g.table));
+            if (g.pixels < pixels) {
+                for (void **b : {&g.d_sum, &g.d_mean, &g.d_rgb8}) {
+                    if (*b) RM_HIP(ctx, hipFree(*b));
+                    *b = nullptr;
+                }
+                g.pixels = 0;
+                RM_HIP(ctx, hipMalloc(&g.d_sum, pixels * 3u * sizeof(double)));
+                RM_HIP(ctx, hipMalloc(&g.d_mean, pixels * 3u * sizeof(double)));
+                RM_HIP(ctx, hipMalloc(&g.d_rgb8, pixels * 3u));
+                g.pixels = pixels;
+            }
+            if (rm_status sst = rm_lens_sequence(n_before, lens->n_samples, g.table)) return sst;
+            RM_HIP(ctx, hipMemcpyAsync(g.d_table, g.table, (size_t)lens->n_samples * 4u * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            RM_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+            if (rm_status lst = launch_accum(ctx, p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream)) return lst;
+            RM_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+            RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            float ms = 0.f;
+            RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+            kernel_ms = ms;
+            g.key = key;
+            g.n = n_before + lens->n_samples;
+            g.have_key = true;
+        }
+        total = g.n;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (host_rgb) RM_HIP(ctx, hipMemcpy(host_rgb, g.d_mean, pixels * 3u * sizeof(double), hipMemcpyDeviceToHost));
+        if (host_rgb8) RM_HIP(ctx, hipMemcpy(host_rgb8, g.d_rgb8, pixels * 3u, hipMemcpyDeviceToHost));
+        d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (n_total) *n_total = total;
+    if (timing) {
+        timing->kernel_ms = kernel_ms;
+        timing->d2h_ms = d2h_ms;
+        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    return RM_OK;
+}
+
+extern "C" {
+
+rm_status rm_lens_sequence(uint32_t first, uint32_t count, double *table) {
+    if ((uint64_t)first + count > RM_PROGRESSIVE_MAX_SAMPLES) {
+        char buf[128];
+        std::snprintf(buf, sizeof buf, "rm_lens_sequence: first + count = %u + %u is more than %u", first, count, RM_PROGRESSIVE_MAX_SAMPLES);
+        return ctx_fail(nullptr, RM_ERR_INVALID_ARG, buf);
+    }
+    if (count == 0u) return RM_OK;
+    if (!table) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_lens_sequence: NULL table");
+    for (uint32_t k = 0; k < count; k++) {
+        const uint32_t s = first + k;
+        const double a = 2. * radical_inverse(s, 5u) - 1.;
+        const double b = 2. * radical_inverse(s, 7u) - 1.;
+        double *r = table + 4u * (size_t)k;
+        r[0] = radical_inverse(s, 2u);
+        r[1] = radical_inverse(s, 3u);
+        r[2] = a * std::sqrt(1. - b * b / 2.);
+        r[3] = b * std::sqrt(1. - a * a / 2.);
+    }
+    return RM_OK;
+}
+
+rm_status rm_accumulate_lens_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table, uint32_t n_before,
+                                    void *device_sum, void *device_mean, void *device_rgb8, void *hip_stream) {
+    return guarded(ctx, "rm_accumulate_lens_device", [&]() {
+        return rm_accumulate_lens_device_impl(ctx, params, lens, device_table, n_before, device_sum, device_mean, device_rgb8, hip_stream);
+    });
+}
+
+rm_status rm_render_progressive(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, int restart, double *host_rgb, uint8_t *host_rgb8,
+                                uint32_t *n_total, rm_timing *timing) {
+    return guarded(ctx, "rm_render_progressive",
+                   [&]() { return rm_render_progressive_impl(ctx, params, lens, restart, host_rgb, host_rgb8, n_total, timing); });
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 #include "rm_radiance.hpp"
 #include "rm_refine.hpp"
 #include "rm_lens.hpp"
+#include "rm_accum.hpp"
 
 using namespace rmdev;
 
@@ -115,6 +116,7 @@ struct rm_feedback {
 };
 
 struct rm_hostio;   // rm_hostio.inc: staging buffer, row-scatter threads, display frame
+struct rm_progressive;   // rm_accum_host.inc: staged table, sum, mean and bytes of rm_render_progressive, its count and key
 
 // The classification's output for the render launches on one stream: a mask per tile.  (Launches on a
 // stream are ordered: a render launch reads what the classification launch in front of it wrote, and the
@@ -216,6 +218,9 @@ struct rm_ctx {
     size_t lens_frame_bytes = 0;
     std::vector<std::pair<const void *, int>> lens_occupancy;
 
+    // progressive frames (rm_accum_host.inc): made by the first rm_render_progressive
+    rm_progressive *progressive = nullptr;
+
     // post-process scratch
     unsigned long long *d_max = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -224,6 +229,7 @@ struct rm_ctx {
 
 static void hostio_destroy(rm_ctx *ctx, bool device_ok);
 static bool hostio_packs(rm_ctx *ctx, size_t band_bytes);
+static void progressive_destroy(rm_ctx *ctx, bool device_ok);
 
 static rm_status ctx_fail(rm_ctx *ctx, rm_status st, const std::string &msg) {
     if (ctx) ctx->error = msg;
@@ -305,7 +311,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -361,6 +367,7 @@ void rm_destroy(rm_ctx *ctx) {
     // the process is about to exit (RM_ERR_TIMEOUT: "report and exit") and takes it along.
     const bool device_ok = !ctx->comm_stuck;
     hostio_destroy(ctx, device_ok);
+    progressive_destroy(ctx, device_ok);
     if (device_ok) {
         for (rm_frame_slot &s : ctx->slots) {
             // after a timed-out collective the slot's stream may never drain: leave it to process exit
@@ -1088,3 +1095,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_radiance_host.inc"
 #include "rm_refine_host.inc"
 #include "rm_lens_host.inc"
+#include "rm_accum_host.inc"

@@ -71,8 +71,8 @@ static rm_status lens_grid(rm_ctx *ctx, const void *fn, uint32_t total, uint32_t
     return RM_OK;
 }
 
-// The launch on `stream`; everything was checked, rows > 0.
-static rm_status launch_lens(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, void *frame, hipStream_t stream) {
+// The argument block of a launch (rm_accum_host.inc's launches carry one too); everything was checked.
+static LensArgs lens_args(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, void *frame) {
     LensArgs q{};
     q.H = ctx->image.H;
     q.H.off_occ = 0u;                                                      // (as launch_radiance)
@@ -93,7 +93,12 @@ static rm_status launch_lens(rm_ctx *ctx, const rm_params *p, const rm_lens *len
     q.cam_fx = cb.forward.x; q.cam_fy = cb.forward.y; q.cam_fz = cb.forward.z;
     q.table = static_cast<const double *>(table);
     q.frame = static_cast<double *>(frame);
+    return q;
+}
 
+// The launch on `stream`; everything was checked, rows > 0.
+static rm_status launch_lens(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, void *frame, hipStream_t stream) {
+    LensArgs q = lens_args(ctx, p, lens, table, frame);
     const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (the radiance kernels' rules: launch_radiance)
     const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
     const void *fn = rm_lens_kernel(bvh, pow_mode, q.max_depth <= 5u ? 4 : 32);

@@ -89,7 +89,7 @@ struct rm_knobs {
     // divisions throughout (the A/B switch, and what the bit-equality tests compare with)
     bool checked_numerics = true;
     uint32_t refine_max_blocks = 0;      // RM_REFINE_MAX_BLOCKS=n: at most n workgroups shade the pixels an anti-aliased frame refines, each then loops over more groups (unset / 0: what the device holds at once; results do not change)
-    uint32_t lens_max_blocks = 0;        // RM_LENS_MAX_BLOCKS=n: at most n workgroups shade a thin-lens frame, each then loops over more groups of pixels (unset / 0: what the device holds at once; results do not change)
+    uint32_t lens_max_blocks = 0;        // RM_LENS_MAX_BLOCKS=n: at most n workgroups shade a thin-lens frame or a pass of a progressive one (rm_accum.hip has the lens kernel's grid), each then loops over more groups of pixels (unset / 0: what the device holds at once; results do not change)
     bool debug_tail = false;             // RM_DEBUG_TAIL (set at all): every ordered launch is waited for and its order dumped to stderr; no launch is frozen
 };
 rm_knobs rm_knobs_from_env();

@@ -300,6 +300,7 @@ struct Renderer {
     uint32_t flags = RM_FLAG_NONE;
     rm_timing last_timing{};
     uint32_t last_refined = 0;     // render_antialiased: pixels it refined
+    uint32_t last_samples = 0;     // render_progressive: samples a pixel in its frame
 
     ~Renderer() { rm_destroy(ctx_); }
     Renderer(const Renderer &) = delete;
@@ -415,6 +416,26 @@ struct Renderer {
         const size_t rows = frame.height - frame.height % 32;
         std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
         check(rm_render_lens(ctx_, &p, &lens, table.data(), flat.data(), &last_timing), ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
+    // A tick of a standing view (rm_render_progressive): n_samples (1..64) more lens samples a pixel of the library's unbounded
+    // sequence are added on the device to the frame the context keeps, and `frame` gets the mean of all of them so far.  The
+    // frame begins again when `restart` is set or anything it depends on changed since the last tick (renderer, frame size, lens,
+    // camera, view direction, scene).  Fills the whole patch rows of `frame`; the samples a pixel in it are left in last_samples
+    // (at most RM_PROGRESSIVE_MAX_SAMPLES: further ticks change nothing).
+    std::string render_progressive(framebuffer::FrameBuffer &frame, const scene::Scene &sc, double aperture, double focus, uint32_t n_samples,
+                                   bool restart = false) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_progressive(ctx_, &p, &lens, restart ? 1 : 0, flat.data(), nullptr, &last_samples, &last_timing), ctx_);
         for (size_t y = 0; y < rows; y++)
             for (size_t x = 0; x < frame.width; x++) {
                 const double *c = &flat[(y * frame.width + x) * 3];

@@ -23,6 +23,7 @@ class Renderer:
         self.device = 0
         self.last_timing = None
         self.last_refined = None                                           # render_antialiased: pixels it refined
+        self.last_samples = None                                           # render_progressive: samples a pixel in its frame
 
     def render(self, frame, scene):
         t0 = time.perf_counter()
@@ -137,6 +138,36 @@ class Renderer:
         ctx.upload(scene.flatten())
         ctx.orient(getattr(scene, "basis", None))
         self.last_timing = ctx.render_lens(p, frame.buffer, aperture, focus, ctx.lens_table(n_samples))
+
+        ms = int((time.perf_counter() - t0) * 1000.)
+        buf = C.create_string_buffer(256)
+        _lib.lib().rm_format_status(buf, 256, ms, frame.width, frame.height)
+        message = buf.value.decode()
+        print(message)
+        info = ctx.device_info()
+        print("%d compute units used" % info["cus"])
+        return message
+
+    def render_progressive(self, frame, scene, aperture, focus, n_samples, restart=False):
+        """A tick of a standing view (rm_render_progressive): n_samples (1..64) more lens samples a pixel of the library's
+        unbounded sequence are added on the device to the frame the context keeps, and frame.buffer gets the mean of all of
+        them so far.  The frame begins again when `restart` is set or anything it depends on changed since the last tick: the
+        renderer, the frame's size, the lens, the camera, the view direction, the scene.  The whole patch rows of frame.buffer
+        are filled, rows from height - height % 32 on are left untouched.  Prints and returns what render() does; the
+        samples a pixel in the frame are left in self.last_samples (at most 65536: further ticks change nothing)."""
+        backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        t0 = time.perf_counter()
+        ctx = backend.default_context(self.device)
+        if frame.height % 32 != 0 or frame.width % 32 != 0:
+            print("Dimensions mismatch")                                   # renderer.rs:49-51
+        n_patches = (frame.height // 32) * (frame.width // 32)
+        print("Rendering using patches of size %d, using %d patches overall" % (32, n_patches))
+
+        p = backend.make_params(self.fov, self.height, self.width, self.max_depth)
+        p.frame_width, p.frame_height = frame.width, frame.height
+        ctx.upload(scene.flatten())
+        ctx.orient(getattr(scene, "basis", None))
+        self.last_timing, self.last_samples = ctx.render_progressive(p, aperture, focus, n_samples, restart, host_rgb=frame.buffer)
 
         ms = int((time.perf_counter() - t0) * 1000.)
         buf = C.create_string_buffer(256)

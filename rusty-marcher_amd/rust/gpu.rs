@@ -266,6 +266,9 @@ extern "C" {
     fn rm_lens_table(n_samples: u32, table: *mut f64) -> c_int;
     fn rm_render_lens_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_lens(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, table: *const f64, host_rgb: *mut f64, timing: *mut RmTiming) -> c_int;
+    fn rm_lens_sequence(first: u32, count: u32, table: *mut f64) -> c_int;
+    fn rm_accumulate_lens_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_progressive(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -485,6 +488,93 @@ impl Gpu {
             }
         }
         Gpu::status(now, frame.width, frame.height)
+    }
+
+    /// A tick of a standing view: `n_samples` (1..64) more lens samples a pixel of the library's unbounded sequence are added
+    /// on the GPU to the frame the context keeps, and `frame.buffer` gets the mean of all of them so far; `display`, where
+    /// given, gets its `to_vec` bytes (resized to width * height * 3).  The frame begins again when `restart` is set or
+    /// anything it depends on changed since the last tick: the renderer, the frame's size, the lens, the camera, the view
+    /// direction, the scene.  This is what the window's idle handler calls while no key is pressed.  Fills the
+    /// whole patch rows; returns the status string and the samples a pixel in the frame (at most 65536: further ticks
+    /// change nothing).
+    pub fn render_progressive(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let mut total: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe { rm_render_progressive(self.ctx, &p, &lens, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut total, &mut timing) },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), total)
+    }
+
+    /// The device call under `render_progressive` for a host that keeps its own device buffers (`rm_buffer_alloc`):
+    /// `n_samples` rows of `device_table` -- rows of `lens_sequence`, written there by the caller -- are cast for every pixel
+    /// and added to `device_sum`, which holds `n_before` samples a pixel already (0: it is not read); the mean goes to
+    /// `device_mean` and its display bytes to `device_rgb8` where these are not null.  Asynchronous on `hip_stream`; the
+    /// scene is the one the context holds.
+    pub fn accumulate_lens(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe { rm_accumulate_lens_device(self.ctx, &p, &lens, device_table, n_before, device_sum, device_mean, device_rgb8, hip_stream) },
+            self.ctx,
+        );
+    }
+
+    /// Rows `first .. first + count` of the library's unbounded sample sequence, four f64 (dx, dy, u, v) a row.
+    pub fn lens_sequence(first: u32, count: u32) -> Vec<f64> {
+        let mut table = vec![0f64; 4 * count as usize + 1]; // (+ 1: never a dangling pointer)
+        check(unsafe { rm_lens_sequence(first, count, table.as_mut_ptr()) }, ptr::null());
+        table.truncate(4 * count as usize);
+        table
     }
 
     /// `render` with a device-resident FrameBuffer: the f64 frame stays on the GPU and only
