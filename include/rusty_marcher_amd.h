@@ -899,6 +899,62 @@ rm_status rm_render_progressive(rm_ctx *ctx, const rm_params *params, const rm_l
                                 double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
                                 uint32_t *n_total /* optional */, rm_timing *timing /* optional */);
 
+/* ---- area lights: soft shadows in progressive frames -----------------------------------------
+ * Every light of a scene is a point, so every shadow edge is hard however many samples a frame
+ * holds.  These calls give each sample of a progressive frame light positions of its own: a light
+ * of radius r is sampled on the sphere of radius r about its position, and the mean converges to a
+ * picture with penumbrae.  Additive to ABI version 5; a host detects them by " soft" in
+ * rm_build_info().
+ *
+ * A light offset table is [n_samples][n_lights][3] doubles in world units.  For sample row s and
+ * light l the light stands at P'.c = P.c + off[s][l].c per component, P the resident scene's
+ * position: one addition, rounded once.  Everything direct_lighting does for that light takes P' in
+ * place of P -- light_dir = normalized(P' - point), the side test, the shadow ray's origin and
+ * direction, the diffuse and the specular term -- at every ray step of the sample: the primary hit
+ * and the reflected and refracted children.  Colour and intensity are the scene's; there is no
+ * fall-off with distance and shadow rays are unbounded, as rendered.  Everything else is steps 1-5
+ * of the thin-lens camera and the sum, mean and bytes of the progressive frames, word for word.
+ * With every offset +0. or -0. a frame is byte for byte what rm_accumulate_lens_device writes,
+ * for light coordinates that are not -0. (-0. + +0. is +0.).
+ *
+ * rm_light_sequence fills rows first .. first + count - 1 of one fixed offset sequence,
+ * count * n_lights * 3 doubles.  Host arithmetic only (no context, no GPU, no libm beyond sqrt and
+ * floor), every operation rounded once in this order.  With phi_b as in rm_lens_sequence, for index
+ * s and light l: x = phi_11(s) + (double)l * 0.6180339887498949, x = x - floor(x);
+ * y = phi_13(s) + (double)l * 0.6180339887498949, y = y - floor(y); a = 2.*x - 1., b = 2.*y - 1.;
+ * u = a * sqrt(1. - b*b/2.), v = b * sqrt(1. - a*a/2.); r2 = u*u + v*v,
+ * h = 2. * sqrt(fmax(1. - r2, 0.)); e = (u*h, v*h, 1. - 2.*r2) -- the disc of rm_lens_table lifted
+ * to the unit sphere -- and off[s][l] = (radii[l]*e.x, radii[l]*e.y, radii[l]*e.z).  A radius of 0
+ * gives zeros.  first + count > RM_PROGRESSIVE_MAX_SAMPLES, a radius that is not a finite number
+ * >= 0, and a NULL radii or offsets with something to write are RM_ERR_INVALID_ARG, nothing is
+ * written; count == 0 or n_lights == 0 is RM_OK, nothing is written.
+ *
+ * rm_accumulate_soft_device is rm_accumulate_lens_device with the offset table: asynchronous on
+ * hip_stream, neither reading nor writing render state, the same checks, and: n_lights must be the
+ * resident scene's (as rm_lights_visible requires); device_offsets must not be NULL when
+ * n_lights > 0 -- a scene without lights takes a NULL table.  lens->n_samples rows of
+ * device_offsets are read.  Their contents are a precondition: a non-finite offset gives
+ * unspecified pixels, never a fault.
+ *
+ * rm_render_progressive_soft is the viewer's tick with area lights: rm_render_progressive on the
+ * same context-owned sum, mean and bytes and the same count N, with the key extended by n_lights
+ * and the bytes of radii (rm_render_progressive counts as "no radii").  So the frame begins again
+ * when a radius changes, when a caller switches between the two calls in either direction, and on
+ * everything that begins it again in rm_render_progressive; it continues otherwise.  The call
+ * stages rows [N, N + n_samples) of rm_lens_sequence and of rm_light_sequence (buffers the context
+ * owns, grown on demand, freed by rm_destroy).  Checked before anything else happens: radii finite
+ * and >= 0 (NULL only when n_lights == 0), n_lights the resident scene's; a refused call changes
+ * neither N nor the key.  Saturation, rows == 0, timing and the counters are rm_render_progressive's.
+ */
+rm_status rm_light_sequence(uint32_t first, uint32_t count, const double *radii, uint32_t n_lights, double *offsets);
+rm_status rm_accumulate_soft_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                    const void *device_offsets, uint32_t n_lights, uint32_t n_before, void *device_sum,
+                                    void *device_mean /* optional */, void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_render_progressive_soft(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *radii,
+                                     uint32_t n_lights, int restart, double *host_rgb /* optional */,
+                                     uint8_t *host_rgb8 /* optional */, uint32_t *n_total /* optional */,
+                                     rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

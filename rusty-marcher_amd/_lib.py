@@ -203,6 +203,10 @@ SIGNATURES = {
     "rm_lens_sequence": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_double)]),
     "rm_accumulate_lens_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
     "rm_render_progressive": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), C.c_int, _P(C.c_double), _P(C.c_uint8), _P(C.c_uint32), _P(rm_timing)]),
+    "rm_light_sequence": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_double), C.c_uint32, _P(C.c_double)]),
+    "rm_accumulate_soft_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "rm_render_progressive_soft": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), C.c_uint32, C.c_int, _P(C.c_double),
+                                             _P(C.c_uint8), _P(C.c_uint32), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

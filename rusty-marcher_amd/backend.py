@@ -96,6 +96,52 @@ def _lens_rows(table, n_samples):
     return t
 
 
+def _radii(radii, n_lights=None):
+    """The radii of a scene's area lights as a C-contiguous float64 vector: one finite number >= 0 a light (n_lights of them
+    where that is known)."""
+    if isinstance(radii, (str, bytes)) or np.ndim(radii) != 1:
+        raise ValueError("light radii must be a sequence of numbers, one a light, got %r" % (radii,))
+    try:
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("light radii must be numbers, got %r" % (radii,))
+    if not (np.isfinite(r).all() and (r >= 0.).all()):
+        raise ValueError("every light radius must be a finite number >= 0, got %r" % (list(radii),))
+    if n_lights is not None and r.shape[0] != n_lights:
+        raise ValueError("one radius a light: the scene has %d lights, got %d radii" % (n_lights, r.shape[0]))
+    return r
+
+
+def _accumulate_args(device, params, sum, aperture, focus, table, n_before, mean, rgb8):
+    """What accumulate_lens_device and accumulate_soft_device check of their common arguments -> (rm_lens, the table's tensor)."""
+    torch = _torch()
+    h, w = params.frame_height, params.frame_width
+    for name, t, dtype in (("sum", sum, torch.float64), ("mean", mean, torch.float64), ("rgb8", rgb8, torch.uint8)):
+        if t is None and name != "sum":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (h, w, 3) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, (h, w, 3)))
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, device, t.device))
+    if mean is not None and mean.data_ptr() == sum.data_ptr():
+        raise ValueError("mean must not be the sum's own tensor")
+    if isinstance(n_before, bool) or int(n_before) != n_before or n_before < 0:
+        raise ValueError("n_before must be a non-negative integer, got %r" % (n_before,))
+    if isinstance(table, torch.Tensor):
+        if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+            raise ValueError("table must be a contiguous float64 torch tensor of shape (n_samples, 4)")
+        if table.device != sum.device:
+            raise ValueError("table must live on %s, not %s" % (sum.device, table.device))
+        lens = _lens(aperture, focus, table.shape[0])
+    else:
+        rows = np.asarray(table)
+        lens = _lens(aperture, focus, rows.shape[0] if rows.ndim == 2 else 0)
+        table = torch.from_numpy(_lens_rows(rows, lens.n_samples)).to(sum.device)
+    if n_before + lens.n_samples > PROGRESSIVE_MAX_SAMPLES:
+        raise ValueError("n_before + n_samples must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, n_before, lens.n_samples))
+    return lens, table
+
+
 def _device_hits(raw):
     """DeviceHits over a float64 tensor whose last dimension is one rm_hit (9 words)."""
     ints = raw.view(_torch().int32)                       # 18 int32 a record: shape, element, hit are 14, 15, 16
@@ -530,31 +576,7 @@ class Context:
         device.  mean: optionally a float64 tensor of that shape for sum / (n_before + n_samples); rgb8: optionally a uint8
         tensor of that shape for the mean's display bytes.  Asynchronous on `stream` (torch's current one by default).
         table: as render_lens_device's.  -> the table's tensor."""
-        torch = _torch()
-        h, w = params.frame_height, params.frame_width
-        for name, t, dtype in (("sum", sum, torch.float64), ("mean", mean, torch.float64), ("rgb8", rgb8, torch.uint8)):
-            if t is None and name != "sum":
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (h, w, 3) or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, (h, w, 3)))
-            if t.device.type != "cuda" or t.device.index != self.device:
-                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
-        if mean is not None and mean.data_ptr() == sum.data_ptr():
-            raise ValueError("mean must not be the sum's own tensor")
-        if isinstance(n_before, bool) or int(n_before) != n_before or n_before < 0:
-            raise ValueError("n_before must be a non-negative integer, got %r" % (n_before,))
-        if isinstance(table, torch.Tensor):
-            if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
-                raise ValueError("table must be a contiguous float64 torch tensor of shape (n_samples, 4)")
-            if table.device != sum.device:
-                raise ValueError("table must live on %s, not %s" % (sum.device, table.device))
-            lens = _lens(aperture, focus, table.shape[0])
-        else:
-            rows = np.asarray(table)
-            lens = _lens(aperture, focus, rows.shape[0] if rows.ndim == 2 else 0)
-            table = torch.from_numpy(_lens_rows(rows, lens.n_samples)).to(sum.device)
-        if n_before + lens.n_samples > PROGRESSIVE_MAX_SAMPLES:
-            raise ValueError("n_before + n_samples must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, n_before, lens.n_samples))
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
         _lib.check(self.L.rm_accumulate_lens_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()), int(n_before),
                                                     C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
                                                     C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
@@ -576,6 +598,67 @@ class Context:
                                                 host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
                                                 host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
                                                 C.byref(total), C.byref(timing)), self.ptr)
+        return timing, total.value
+
+    # ---- area lights (include/rusty_marcher_amd.h, "area lights") ----
+    def light_sequence(self, first, count, radii):
+        """rm_light_sequence: rows first .. first + count - 1 of the library's light offset sequence for lights of the radii
+        `radii`, (count, len(radii), 3) float64: row s moves light l to a point of the sphere of radius radii[l] about its
+        position.  Host arithmetic: needs neither a context nor a GPU."""
+        for name, v in (("first", first), ("count", count)):
+            if isinstance(v, bool) or int(v) != v or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        if first + count > PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+        r = _radii(radii)
+        off = np.zeros((int(count), r.shape[0], 3), dtype=np.float64)
+        _lib.check(self.L.rm_light_sequence(int(first), int(count), r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0],
+                                            off.ctypes.data_as(C.POINTER(C.c_double))), None)
+        return off
+
+    def accumulate_soft_device(self, params, sum, aperture, focus, table, offsets, n_before, mean=None, rgb8=None, stream=None):
+        """rm_accumulate_soft_device: accumulate_lens_device with a light offset table -- sample row s sees light l at its
+        position + offsets[s][l].  offsets: a contiguous float64 tensor (n_samples, n_lights, 3) on the context's device, or
+        an array, which is checked (finite) and copied over; n_lights must be the uploaded scene's.
+        -> (the table's tensor, the offsets' tensor)."""
+        torch = _torch()
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        if isinstance(offsets, torch.Tensor):
+            if offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != lens.n_samples or offsets.shape[2] != 3 \
+                    or not offsets.is_contiguous():
+                raise ValueError("offsets must be a contiguous float64 torch tensor of shape (%d, n_lights, 3)" % lens.n_samples)
+            if offsets.device != sum.device:
+                raise ValueError("offsets must live on %s, not %s" % (sum.device, offsets.device))
+        else:
+            off = np.ascontiguousarray(offsets, dtype=np.float64)
+            if off.ndim != 3 or off.shape[0] != lens.n_samples or off.shape[2] != 3 or not np.isfinite(off).all():
+                raise ValueError("offsets must be a finite float64 array of shape (%d, n_lights, 3), got %s" % (lens.n_samples, off.shape))
+            offsets = torch.from_numpy(off).to(sum.device)
+        n_lights = int(offsets.shape[1])
+        _lib.check(self.L.rm_accumulate_soft_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                    C.c_void_p(offsets.data_ptr()) if n_lights > 0 else None, n_lights, int(n_before),
+                                                    C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                    C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                    C.c_void_p(self._stream(stream))), self.ptr)
+        return table, offsets
+
+    def render_progressive_soft(self, params, radii, aperture, focus, n_samples, restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_progressive_soft: render_progressive with area lights -- light l is sampled on the sphere of radius radii[l]
+        about its position, one radius for every light of the uploaded scene.  The frame begins again when a radius changes or
+        the caller switches between this call and render_progressive, and on everything that begins it again there.
+        -> (rm_timing, samples a pixel in the frame now)."""
+        lens = _lens(aperture, focus, n_samples)
+        r = _radii(radii)
+        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
+        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
+                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        timing, total = _lib.rm_timing(), C.c_uint32(0)
+        _lib.check(self.L.rm_render_progressive_soft(self.ptr, C.byref(params), C.byref(lens), r.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     r.shape[0], 1 if restart else 0,
+                                                     host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
+                                                     host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
+                                                     C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
     def primary_hits_device(self, params, out=None, stream=None):

@@ -16,7 +16,8 @@
 // The bytes leave as three byte stores a pixel from the lane that holds the mean: see DESIGN.md section 6h for the
 // resource-usage lines that decided it.
 //
-// Strict flavour, scene in global memory, occluder masks off, contraction off: as rm_lens.hip.
+// Strict flavour, scene in global memory, occluder masks off, contraction off: as rm_lens.hip.  The body is
+// rm_accum_body.inc's, shared with the area lights' kernel (rm_soft.hip); here every light stands where the scene image says.
 #define RM_KERNEL_FAST 0
 #include "rm_render_kernel.hpp"
 #include "rm_accum.hpp"
@@ -26,90 +27,15 @@ using namespace rmdev_strict;
 
 #include "rm_radiance_step.inc"
 
+#include "rm_accum_body.inc"
+
 namespace rmaccum {
-
-using namespace rmradiance;
-
-__device__ __forceinline__ uint8_t to_byte(double v) {                   // framebuffer.rs:80-82, the render epilogue's rule
-    return (uint8_t)(255. * __builtin_fmin(__builtin_fmax(v, 0.), 1.));
-}
 
 template <bool BVH, int POW, int STACK>
 __global__ __launch_bounds__(64) void rm_accum_shade_t(const double *__restrict__ scene_blob, AccumArgs a) {
     __shared__ uint32_t bstack[64];
     __shared__ double sums[64 * 3];
-    const LensArgs &q = a.L;
-    SceneView sc;
-    sc.S = scene_blob;                // (as rm_lens_shade_t)
-    sc.G = scene_blob;
-    sc.cull_bounds = scene_blob + q.H.off_bounds;
-    sc.cull_planar = scene_blob + q.H.off_planar;
-    sc.bstack = bstack;
-    sc.cull_cos = 2.;
-    sc.H = q.H;
-
-    const uint32_t total = q.rows * q.frame_width;                       // (below 2^31: the host checked)
-    const uint32_t ns = q.n_samples, P = 64u / ns;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t slot = lane / ns, s = lane % ns;                      // the lane's pixel within the group, its table row
-    const double *row = q.table + 4u * s;                                // (s < n_samples in every lane)
-    const double dx = row[0], dy = row[1];
-    const double au = q.aperture * row[2], av = q.aperture * row[3];
-    const V3 bg = mk(q.bg_x, q.bg_y, q.bg_z);
-    const V3 cam = mk(q.cam_x, q.cam_y, q.cam_z);
-    const V3 lens = mk(q.cam_x + ((au * q.cam_rx) + (av * q.cam_ux)), q.cam_y + ((au * q.cam_ry) + (av * q.cam_uy)),
-                       q.cam_z + ((au * q.cam_rz) + (av * q.cam_uz)));
-    const bool pinhole = q.aperture == 0.;                               // wave-uniform
-    const bool resume = a.n_before > 0u;                                 // wave-uniform
-    const double div = (double)(a.n_before + ns);                        // (at most 65536: the host checked)
-
-    for (uint32_t g = blockIdx.x; (unsigned long long)g * P < total; g += gridDim.x) {
-        const uint32_t k = g * P + slot;                                 // (g P < total < 2^31, slot < 64)
-        const bool on = (slot < P) & (k < total);
-        const uint32_t pix = on ? k : 0u;
-        V3 orig = mk(0., 0., 0.), dir = mk(0., 0., -1.);                 // (a lane without a sample holds a harmless ray it never casts)
-        if (on) {
-            const double sx = (double)(pix % q.frame_width) + dx, sy = (double)(pix / q.frame_width) + dy;
-            const V3 D = sample_direction(q, q.oriented != 0u, sx, sy);
-            if (pinhole) {
-                orig = cam;
-                dir = normalized(D);
-            } else {
-                const V3 F = mk(q.cam_x + D.x * q.focus, q.cam_y + D.y * q.focus, q.cam_z + D.z * q.focus);
-                orig = lens;
-                dir = normalized(F - lens);
-            }
-        }
-        const V3 acc = q.max_depth == 0u ? bg : radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth);
-        sums[lane * 3u] = acc.x; sums[lane * 3u + 1u] = acc.y; sums[lane * 3u + 2u] = acc.z;
-        __syncthreads();
-        if (on & (s == 0u)) {
-            double *sum = a.sum + (size_t)pix * 3u;                      // (pix < rows x frame_width: inside the three buffers)
-            double rx, ry, rz;
-            uint32_t t;
-            if (resume) {
-                rx = sum[0]; ry = sum[1]; rz = sum[2];
-                t = 0u;
-            } else {
-                rx = sums[lane * 3u]; ry = sums[lane * 3u + 1u]; rz = sums[lane * 3u + 2u];
-                t = 1u;
-            }
-            for (; t < ns; t++) {                                        // table order (lane + t <= 63: lane = slot ns, slot < P)
-                rx = rx + sums[(lane + t) * 3u]; ry = ry + sums[(lane + t) * 3u + 1u]; rz = rz + sums[(lane + t) * 3u + 2u];
-            }
-            sum[0] = rx; sum[1] = ry; sum[2] = rz;
-            const double mx = rx / div, my = ry / div, mz = rz / div;
-            if (a.mean) {
-                double *out = a.mean + (size_t)pix * 3u;
-                out[0] = mx; out[1] = my; out[2] = mz;
-            }
-            if (a.rgb8) {
-                uint8_t *out = a.rgb8 + (size_t)pix * 3u;
-                out[0] = to_byte(mx); out[1] = to_byte(my); out[2] = to_byte(mz);
-            }
-        }
-        __syncthreads();                                                 // the next group's answers overwrite `sums`
-    }
+    accum_shade<BVH, POW, STACK>(scene_blob, a, bstack, sums, [](uint32_t) { return StoredLights(); });
 }
 
 }  // namespace rmaccum

@@ -52,10 +52,9 @@ static rm_status launch_accum(rm_ctx *ctx, const rm_params *p, const rm_lens *le
     return RM_OK;
 }
 
-static rm_status rm_accumulate_lens_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table,
-                                                uint32_t n_before, void *device_sum, void *device_mean, void *device_rgb8, void *hip_stream) {
-    const char *who = "rm_accumulate_lens_device";
-    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+// What the device calls (this one and rm_accumulate_soft_device) check of their own arguments (ctx is not NULL).
+static rm_status check_accum_device(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, const void *device_table,
+                                    uint32_t n_before, const void *device_sum, const void *device_mean) {
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
     if (!device_table) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL table");
     if (!device_sum) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL sum");
@@ -65,6 +64,14 @@ static rm_status rm_accumulate_lens_device_impl(rm_ctx *ctx, const rm_params *p,
         std::snprintf(buf, sizeof buf, "%s: n_before + n_samples = %u + %u is more than %u", who, n_before, lens->n_samples, RM_PROGRESSIVE_MAX_SAMPLES);
         return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
     }
+    return RM_OK;
+}
+
+static rm_status rm_accumulate_lens_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table,
+                                                uint32_t n_before, void *device_sum, void *device_mean, void *device_rgb8, void *hip_stream) {
+    const char *who = "rm_accumulate_lens_device";
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    if (rm_status cst = check_accum_device(ctx, who, p, lens, device_table, n_before, device_sum, device_mean)) return cst;
     if (refine_rows(p) == 0u) return RM_OK;
     RM_HIP(ctx, hipSetDevice(ctx->device));
     return launch_accum(ctx, p, lens, device_table, n_before, device_sum, device_mean, device_rgb8, (hipStream_t)hip_stream);
@@ -79,6 +86,7 @@ struct rm_progressive_key {
     rm_vec3 camera;
     rm_camera_basis basis;
     uint64_t copies;
+    uint32_t soft, n_lights;                 // rm_render_progressive_soft's frames: 1 and the radii's count (their bytes: rm_progressive::radii); else 0, 0
 };
 
 // The progressive state of a context (rm_ctx::progressive; made on the first call, released by rm_destroy)
@@ -90,23 +98,36 @@ struct rm_progressive {
     bool have_key = false;                   // a call has succeeded, and nothing failed half-way since
     rm_progressive_key key;
     uint32_t n = 0;                          // samples a pixel in the sum
+    // area lights (rm_soft_host.inc): the radii the sum belongs to, beside the key, and the staged slice of rm_light_sequence
+    std::vector<double> radii, offsets;
+    void *d_offsets = nullptr;
+    size_t offsets_room = 0;                 // doubles d_offsets has room for
 };
+
+// rm_soft_host.inc: the check of a soft tick's radii, and the launch with an offset table
+static rm_status check_soft_radii(rm_ctx *ctx, const char *who, const double *radii, uint32_t n_lights);
+static rm_status launch_soft(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, const void *offsets, uint32_t n_before,
+                             void *sum, void *mean, void *rgb8, hipStream_t stream);
 
 static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
     rm_progressive *g = ctx->progressive;
     if (!g) return;
-    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8})
+    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->d_offsets})
         if (b && device_ok) (void)hipFree(b);
     delete g;
     ctx->progressive = nullptr;
 }
 
-static rm_status rm_render_progressive_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, int restart, double *host_rgb,
-                                            uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
-    const char *who = "rm_render_progressive";
+// `soft`: rm_render_progressive_soft's tick -- n_lights radii (checked here), the slice of rm_light_sequence staged beside the
+// table's and the kernel of rm_soft.hip; else radii is NULL, n_lights 0 and everything as it was before there were area lights.
+static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, bool soft, const double *radii,
+                                            uint32_t n_lights, int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total,
+                                            rm_timing *timing) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
     const auto t_begin = std::chrono::steady_clock::now();
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
+    if (soft)
+        if (rm_status rst = check_soft_radii(ctx, who, radii, n_lights)) return rst;
     const uint32_t rows = refine_rows(p);
     double kernel_ms = 0., d2h_ms = 0.;
     uint32_t total = 0u;
@@ -123,7 +144,9 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const rm_params *p, con
         key.camera = ctx->camera;
         key.basis = ctx->basis;
         key.copies = ctx->upload_copies;
-        const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0;
+        key.soft = soft ? 1u : 0u; key.n_lights = n_lights;
+        const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0 && g.radii.size() == n_lights &&
+                          (n_lights == 0u || std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) == 0);
         const uint32_t n_before = same ? g.n : 0u;
         const size_t pixels = (size_t)rows * p->frame_width;
         const bool saturated = n_before + lens->n_samples > RM_PROGRESSIVE_MAX_SAMPLES;   // (then n_before > 0: the frame stands)
@@ -144,14 +167,34 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const rm_params *p, con
             }
             if (rm_status sst = rm_lens_sequence(n_before, lens->n_samples, g.table)) return sst;
             RM_HIP(ctx, hipMemcpyAsync(g.d_table, g.table, (size_t)lens->n_samples * 4u * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            const size_t n_offsets = (size_t)lens->n_samples * n_lights * 3u;
+            if (n_offsets > 0u) {                                          // (soft, and the scene has lights)
+                if (g.offsets_room < n_offsets) {
+                    if (g.d_offsets) RM_HIP(ctx, hipFree(g.d_offsets));
+                    g.d_offsets = nullptr;
+                    g.offsets_room = 0;
+                    RM_HIP(ctx, hipMalloc(&g.d_offsets, n_offsets * sizeof(double)));
+                    g.offsets_room = n_offsets;
+                }
+                g.offsets.resize(n_offsets);
+                if (rm_status sst = rm_light_sequence(n_before, lens->n_samples, radii, n_lights, g.offsets.data())) return sst;
+                RM_HIP(ctx, hipMemcpyAsync(g.d_offsets, g.offsets.data(), n_offsets * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            }
             RM_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-            if (rm_status lst = launch_accum(ctx, p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream)) return lst;
+            if (soft) {
+                if (rm_status lst = launch_soft(ctx, p, lens, g.d_table, n_offsets > 0u ? g.d_offsets : nullptr, n_before, g.d_sum, g.d_mean,
+                                                g.d_rgb8, ctx->stream))
+                    return lst;
+            } else if (rm_status lst = launch_accum(ctx, p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream)) {
+                return lst;
+            }
             RM_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
             RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
             float ms = 0.f;
             RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
             kernel_ms = ms;
             g.key = key;
+            g.radii.assign(radii, radii + n_lights);                       // (n_lights == 0: empty, radii may be NULL)
             g.n = n_before + lens->n_samples;
             g.have_key = true;
         }
@@ -203,7 +246,7 @@ rm_status rm_accumulate_lens_device(rm_ctx *ctx, const rm_params *params, const 
 rm_status rm_render_progressive(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, int restart, double *host_rgb, uint8_t *host_rgb8,
                                 uint32_t *n_total, rm_timing *timing) {
     return guarded(ctx, "rm_render_progressive",
-                   [&]() { return rm_render_progressive_impl(ctx, params, lens, restart, host_rgb, host_rgb8, n_total, timing); });
+                   [&]() { return rm_render_progressive_impl(ctx, "rm_render_progressive", params, lens, false, nullptr, 0u, restart, host_rgb, host_rgb8, n_total, timing); });
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include "rm_refine.hpp"
 #include "rm_lens.hpp"
 #include "rm_accum.hpp"
+#include "rm_soft.hpp"
 
 using namespace rmdev;
 
@@ -311,7 +312,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1096,3 +1097,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_refine_host.inc"
 #include "rm_lens_host.inc"
 #include "rm_accum_host.inc"
+#include "rm_soft_host.inc"

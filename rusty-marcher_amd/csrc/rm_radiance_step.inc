@@ -26,9 +26,11 @@ __device__ __forceinline__ V3 sample_direction(const A &q, bool oriented, double
 }
 
 // What comes back along the lane's ray (orig, dir), cast as a primary ray (n_recursion = 1) with the cap max_depth >= 1; zero
-// for a lane whose `on` is off.  Called by whole waves.
-template <bool BVH, int POW, int STACK>
-__device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 dir, bool on, const V3 bg, const uint32_t max_depth) {
+// for a lane whose `on` is off.  Called by whole waves.  `lights`: where the lane's lights stand at every step of its ray, the
+// children's included (rm_trace.inc, StoredLights: as the scene image says).
+template <bool BVH, int POW, int STACK, class LIGHTS = StoredLights>
+__device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 dir, bool on, const V3 bg, const uint32_t max_depth,
+                                             const LIGHTS &lights = LIGHTS()) {
     double weight = 1.;
     uint32_t depth = 1;                                                  // renderer.rs:83
     V3 acc = mk(0., 0., 0.);
@@ -49,7 +51,7 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
         bool next = false;                                               // the lane goes on with a child of its ray
         if (__any(got)) {
             const Surface s = surface_at<false>(sc, orig, dir, h, got);
-            L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, neg(normalized(dir)), s, got, h.pid), bg);
+            L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, neg(normalized(dir)), s, got, h.pid, lights), bg);
             const bool glass = got & (s.mat[8] != 0.);                   // is_glass_like, renderer.rs:277
             if (__any(glass)) {
                 const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];

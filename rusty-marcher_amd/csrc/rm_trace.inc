@@ -1173,11 +1173,20 @@ struct LightAt {
     bool dark;          // adds exactly zero whether or not it is shadowed
 };
 
-__device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, const Surface &s, V3 dir_to_viewer, double exponent, bool got RM_SUS_PARAM) {
+// Where light l stands, given its record `lt` of the scene image.  The default is the record's own position; a kernel whose
+// samples move their lights (rm_soft.hip) hands shade_direct another rule.  In shade_direct nothing else reads a light's position (the occluder masks are keyed on
+// the stored ones: such a kernel runs with them off).
+struct StoredLights {
+    __device__ __forceinline__ V3 operator()(const double *lt, uint32_t) const { return mk(lt[0], lt[1], lt[2]); }
+};
+
+template <class LIGHTS = StoredLights>
+__device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, const Surface &s, V3 dir_to_viewer, double exponent, bool got RM_SUS_PARAM,
+                                            const LIGHTS &lights = LIGHTS()) {
     (void)got;
     LightAt a;
     const double *lt = sc.G + sc.H.off_lights + RM_LIGHT_WORDS * l;
-    a.pos = mk(lt[0], lt[1], lt[2]);
+    a.pos = lights(lt, l);
     a.dir = RM_NORMALIZED(a.pos - s.point, got);                      // :166 (a ray direction: exact)
     a.ldn = dot(a.dir, s.normal);
     // :168-172 point -/+ normal * 1e-3: one expression, p - n k == p + n (-k) bit for bit
@@ -1195,8 +1204,10 @@ __device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, con
 }
 
 // `pid`: the primitive each lane's hit lies on.
-template <int POW, bool BVH, bool CULL, bool EDGES>
-__device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got, uint32_t pid RM_SUS_PARAM) {
+// `lights`: where each light stands (StoredLights: as the scene image says).
+template <int POW, bool BVH, bool CULL, bool EDGES, class LIGHTS = StoredLights>
+__device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got, uint32_t pid RM_SUS_PARAM,
+                                           const LIGHTS &lights = LIGHTS()) {
     const double *m = s.mat;
     const double exponent = m[5];
     // (colour and specular weight are fetched where a light is found unshadowed: held in
@@ -1225,13 +1236,13 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
     // plain-walk kernels: the occluder masks of the walks, where the scene has them
     const bool masks = !BVH && !CULL && sc.H.off_occ != 0u;
     for (uint32_t l = 0; l < sc.H.n_lights;) {
-        const LightAt a = light_at(sc, l, s, dir_to_viewer, exponent, got RM_SUS_ARG);
+        const LightAt a = light_at(sc, l, s, dir_to_viewer, exponent, got RM_SUS_ARG, lights);
         const bool dec_a = !got | a.dark;
         if (!BVH && !CULL && l + 1u < sc.H.n_lights) {
             // plain-walk kernels: lights two at a time -- where both lie on the same side of the
             // surface their shadow rays leave one point and share one walk (any_hit2); where some
             // lane has them on opposite sides (rare) the second light is taken up again alone
-            const LightAt b = light_at(sc, l + 1u, s, dir_to_viewer, exponent, got RM_SUS_ARG);
+            const LightAt b = light_at(sc, l + 1u, s, dir_to_viewer, exponent, got RM_SUS_ARG, lights);
             const bool dec_b = !got | b.dark;
             if (__all(dec_a | dec_b | ((a.ldn < 0.) == (b.ldn < 0.)))) {
                 bool occ_a, occ_b;

@@ -443,6 +443,26 @@ struct Renderer {
             }
         return status(t0, frame.width, frame.height);
     }
+    // render_progressive with area lights (rm_render_progressive_soft): light l of the scene is a sphere of radius radii[l] -- one
+    // radius a light, 0 for a point -- sampled at another point for every sample, so the frame converges to soft shadows.  Beyond
+    // what begins a frame again in render_progressive, a changed radius does, and so does a switch between the two calls.
+    std::string render_progressive_soft(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const std::vector<double> &radii, double aperture,
+                                        double focus, uint32_t n_samples, bool restart = false) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_progressive_soft(ctx_, &p, &lens, radii.data(), (uint32_t)radii.size(), restart ? 1 : 0, flat.data(), nullptr,
+                                         &last_samples, &last_timing),
+              ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
     void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }

@@ -156,6 +156,26 @@ class Renderer:
         are filled, rows from height - height % 32 on are left untouched.  Prints and returns what render() does; the
         samples a pixel in the frame are left in self.last_samples (at most 65536: further ticks change nothing)."""
         backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        return self._tick(frame, scene, lambda ctx, p: ctx.render_progressive(p, aperture, focus, n_samples, restart, host_rgb=frame.buffer))
+
+    def render_progressive_soft(self, frame, scene, light_radii, aperture, focus, n_samples, restart=False):
+        """render_progressive with area lights (rm_render_progressive_soft): light l of the scene is a sphere of radius
+        light_radii[l] -- one radius a light, 0 for a point -- sampled at another point for every sample, so the frame
+        converges to soft shadows.  Beyond what begins a frame again in render_progressive, a changed radius does, and so
+        does a switch between the two calls."""
+        backend._lens(aperture, focus, n_samples)
+        radii = backend._radii(light_radii, len(scene.lights))
+        return self._tick(frame, scene, lambda ctx, p: ctx.render_progressive_soft(p, radii, aperture, focus, n_samples, restart,
+                                                                                    host_rgb=frame.buffer))
+
+    def render_soft_shadows(self, frame, scene, light_radii, n_samples, aperture=0., focus=1.):
+        """One frame with soft shadows: a restarted tick of render_progressive_soft -- n_samples (1..64) samples a pixel, through
+        a pinhole unless an aperture is given."""
+        return self.render_progressive_soft(frame, scene, light_radii, aperture, focus, n_samples, restart=True)
+
+    def _tick(self, frame, scene, call):
+        """What the progressive renders share: the prints and the return value of render(); call(ctx, params) ->
+        (rm_timing, samples a pixel in the frame)."""
         t0 = time.perf_counter()
         ctx = backend.default_context(self.device)
         if frame.height % 32 != 0 or frame.width % 32 != 0:
@@ -167,7 +187,7 @@ class Renderer:
         p.frame_width, p.frame_height = frame.width, frame.height
         ctx.upload(scene.flatten())
         ctx.orient(getattr(scene, "basis", None))
-        self.last_timing, self.last_samples = ctx.render_progressive(p, aperture, focus, n_samples, restart, host_rgb=frame.buffer)
+        self.last_timing, self.last_samples = call(ctx, p)
 
         ms = int((time.perf_counter() - t0) * 1000.)
         buf = C.create_string_buffer(256)

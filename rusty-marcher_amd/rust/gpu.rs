@@ -269,6 +269,9 @@ extern "C" {
     fn rm_lens_sequence(first: u32, count: u32, table: *mut f64) -> c_int;
     fn rm_accumulate_lens_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_progressive(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_light_sequence(first: u32, count: u32, radii: *const f64, n_lights: u32, offsets: *mut f64) -> c_int;
+    fn rm_accumulate_soft_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_offsets: *const c_void, n_lights: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_progressive_soft(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -575,6 +578,96 @@ impl Gpu {
         check(unsafe { rm_lens_sequence(first, count, table.as_mut_ptr()) }, ptr::null());
         table.truncate(4 * count as usize);
         table
+    }
+
+    /// `render_progressive` with area lights: light l of the scene is a sphere of radius `radii[l]` -- one radius a light, 0 for
+    /// a point -- sampled at another point for every sample, so the frame converges to soft shadows.  Beyond what begins a
+    /// frame again in `render_progressive`, a changed radius does, and so does a switch between the two calls.
+    pub fn render_progressive_soft(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        radii: &[f64],
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let mut total: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_progressive_soft(self.ctx, &p, &lens, radii.as_ptr(), radii.len() as u32, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut total, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), total)
+    }
+
+    /// The device call under `render_progressive_soft`: `accumulate_lens` with `device_offsets`, `n_samples` x `n_lights` x 3
+    /// f64 -- rows of `light_sequence`, or any offsets of the caller's making -- that move light l of sample row s.
+    /// `n_lights` is the resident scene's.
+    pub fn accumulate_soft(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_offsets: *const c_void,
+        n_lights: u32,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_soft_device(self.ctx, &p, &lens, device_table, device_offsets, n_lights, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// Rows `first .. first + count` of the library's light offset sequence for lights of the radii `radii`: three f64 a light,
+    /// `radii.len()` lights a row.
+    pub fn light_sequence(first: u32, count: u32, radii: &[f64]) -> Vec<f64> {
+        let n = 3 * radii.len() * count as usize;
+        let mut offsets = vec![0f64; n + 1]; // (+ 1: never a dangling pointer)
+        check(unsafe { rm_light_sequence(first, count, radii.as_ptr(), radii.len() as u32, offsets.as_mut_ptr()) }, ptr::null());
+        offsets.truncate(n);
+        offsets
     }
 
     /// `render` with a device-resident FrameBuffer: the f64 frame stays on the GPU and only
