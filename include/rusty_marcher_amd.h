@@ -955,6 +955,112 @@ rm_status rm_render_progressive_soft(rm_ctx *ctx, const rm_params *params, const
                                      uint8_t *host_rgb8 /* optional */, uint32_t *n_total /* optional */,
                                      rm_timing *timing /* optional */);
 
+/* ---- converging frames: progressive frames that sample only the pixels still noisy ------------
+ * A pass of a progressive frame casts n_samples rays for every pixel, however long most of them
+ * have stopped changing.  These calls keep a sample count and an error estimate per pixel, list the
+ * pixels still noisy on the device, and shade the listed pixels alone -- each continuing the sample
+ * sequence where that pixel stopped.  A viewer learns when the picture is finished: nothing is
+ * listed.  Additive to ABI version 5; a host detects them by " converge" in rm_build_info().
+ *
+ * Let rows = frame_height - frame_height % 32 and ns = lens->n_samples.  The per-pixel state is
+ * three buffers in the plain layout: sum, [frame_height][frame_width][3] doubles as in the
+ * progressive frames; stats, [frame_height][frame_width][2] doubles (Y, Q): the sums of y and of
+ * y*y over the pixel's samples, y = (r + g) + b per sample; count, [frame_height][frame_width]
+ * uint32_t: the pixel's number of samples n.  With fresh != 0 every n counts as 0 and none of the
+ * three buffers is read.
+ *
+ *   Select.  Complete before any pixel is sampled.  Let nd = (double)n, m2 = Q - (Y*Y)/nd.
+ *            capped(p): n + ns > max_samples.  unsettled(p): tolerance < 0, or
+ *            n < max(min_samples, 2), or !(m2 <= (tolerance*tolerance) * (nd * (nd - 1.))) -- every
+ *            operation rounded once, no fused multiply-add, so a NaN leaves the pixel unsettled.
+ *            m2 / (nd (nd - 1)) is the squared standard error of the mean of y.
+ *            noisy(p) = !capped(p) && unsettled(p).  A pixel is listed iff it is not capped and it
+ *            or one of its up-to-four neighbours in [0, frame_width) x [0, rows) is noisy: the
+ *            neighbourhood of the adaptive anti-aliasing.  The widening keeps a silhouette's
+ *            neighbours sampling.  A pixel whose first samples all missed a thin feature is the
+ *            estimate's known weak spot; min_samples is the guard against it.
+ *            After the call the first uint32_t of the workspace holds the number of listed pixels
+ *            and their indices y * frame_width + x follow, in no particular order.  mask, where
+ *            given, gets 1 or 0 for every pixel of [0, rows).
+ *   Sample.  A listed pixel with count n casts rows n .. n + ns - 1 of device_table, a prefix of
+ *            rm_lens_sequence table_rows rows long, table_rows >= max_samples.  Where
+ *            device_offsets is given the pixel also takes the same rows of that prefix of
+ *            rm_light_sequence ([table_rows][n_lights][3]) and n_lights must be the resident
+ *            scene's; NULL: every light is the scene's point.  Rays and radiance are steps 1-5 of
+ *            the thin-lens camera, word for word, with the area lights' rule for the lights.
+ *   Fold.    S, Y and Q start as the first sample's values (r, g, b; y; y*y) when n == 0, else
+ *            from the buffers; the remaining samples are added in table order by plain additions;
+ *            count = n + ns.  The mean is S / (double)(n + ns) and the bytes follow the progressive
+ *            frames' rule; both are stored where those buffers are given.  A pixel that is not
+ *            listed keeps every byte of every buffer.  Rows from `rows` on are neither read nor
+ *            written.
+ *
+ * So the fold is a left fold in table order: a pixel with count c holds, byte for byte, the sum and
+ * the mean rm_accumulate_lens_device (with offsets: rm_accumulate_soft_device) leaves after c
+ * samples of the sequence, however the passes were sliced.  And with tolerance < 0 a run of passes
+ * is byte for byte the plain run in sum, mean and bytes, every count the plain run's total.
+ *
+ * rm_accumulate_converging_device is asynchronous on hip_stream, neither reads nor writes render
+ * state and keeps all of its state in the caller's buffers (a memset of the workspace's first word,
+ * the select launch, the shade launch).  The workspace has rm_converge_workspace bytes,
+ * rm_refine_workspace's size.  Checked before anything is launched, the offender named in
+ * rm_last_error, no buffer touched: everything rm_accumulate_soft_device checks of params, lens and
+ * the table (n_lights only where device_offsets is given); tolerance not NaN; ns <= max_samples <=
+ * min(table_rows, RM_PROGRESSIVE_MAX_SAMPLES); converge, buffers, sum, stats, count and workspace
+ * not NULL; mean != sum.  rows == 0 is RM_OK and does nothing.  The tables' contents and a count
+ * buffer that this call or zeros filled are preconditions; a count from elsewhere gives unspecified
+ * pixels, never a fault.
+ *
+ * rm_render_converging is the viewer's tick.  The context owns state of its own for it -- the six
+ * buffers, the resident prefix of both sequences (appended to as the frame grows, never staged
+ * again whole), the pass total N (a bound on every pixel's count: a pass that listed something sets
+ * N = max(N, min(N + ns, max_samples)), whatever ns and max_samples were tick by tick), the passes and samples so
+ * far, and the key of rm_render_progressive_soft: radii == NULL is "no radii" (point lights,
+ * n_lights ignored) -- and shares none of it with rm_render_progressive: neither call disturbs the
+ * other's frame.  The fields of rm_converge and n_samples are not part of the key: a viewer may
+ * tighten the tolerance and continue.  restart != 0, another key or no successful call before
+ * begin the frame again (fresh, N = 0).  The call runs one pass on the context's stream, copies the
+ * rows [0, rows) of the mean and the bytes where asked, fills *report and blocks.  If the previous
+ * tick of the same frame listed 0 pixels with the same rm_converge and n_samples, nothing is
+ * launched, the frame stands and report->listed is 0: ticking a finished picture is not an error.
+ * Checks: rm_render_progressive_soft's (radii only where given), tolerance not NaN, ns <=
+ * max_samples <= RM_PROGRESSIVE_MAX_SAMPLES; a refused call changes nothing of the state.
+ * rows == 0 is RM_OK with a report of zeros.  timing->kernel_ms covers the three steps.
+ */
+typedef struct rm_converge {
+    double   tolerance;    /* standard error of y = (r + g) + b a pixel may keep; < 0: no pixel ever settles; NaN refused */
+    uint32_t min_samples;  /* a pixel with fewer samples is never settled */
+    uint32_t max_samples;  /* a pixel is never sampled beyond this many; n_samples..RM_PROGRESSIVE_MAX_SAMPLES */
+} rm_converge;             /* 16 bytes */
+
+typedef struct rm_converge_frame {   /* device memory, the plain layout */
+    void *sum;         /* [frame_height][frame_width][3] doubles */
+    void *stats;       /* [frame_height][frame_width][2] doubles */
+    void *count;       /* [frame_height][frame_width] uint32_t */
+    void *workspace;   /* rm_converge_workspace bytes */
+    void *mean;        /* optional: the sum's shape */
+    void *rgb8;        /* optional: [frame_height][frame_width][3] bytes */
+    void *mask;        /* optional: [frame_height][frame_width] bytes */
+} rm_converge_frame;     /* 56 bytes */
+
+typedef struct rm_converge_report {
+    uint64_t samples_cast;   /* over the frame's life: the sum of listed * n_samples over its passes */
+    uint32_t listed;         /* pixels this call listed and sampled (0: the picture is finished) */
+    uint32_t passes;         /* passes the frame has run */
+    uint32_t max_count;      /* N: no pixel's count exceeds it */
+    uint32_t _pad;
+} rm_converge_report;      /* 24 bytes */
+
+/* bytes of device memory the list needs for `params`: rm_refine_workspace's */
+rm_status rm_converge_workspace(const rm_params *params, size_t *bytes);
+rm_status rm_accumulate_converging_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                                          const void *device_table, uint32_t table_rows, const void *device_offsets /* optional */,
+                                          uint32_t n_lights, int fresh, const rm_converge_frame *buffers, void *hip_stream);
+rm_status rm_render_converging(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                               const double *radii /* NULL: point lights */, uint32_t n_lights, int restart,
+                               double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                               rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

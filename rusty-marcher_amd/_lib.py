@@ -108,6 +108,23 @@ class rm_lens(C.Structure):
     _fields_ = [("aperture", C.c_double), ("focus", C.c_double), ("n_samples", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class rm_converge(C.Structure):
+    """When a pixel of a converging frame is settled: standard error it may keep, fewest and most samples (16 bytes)."""
+    _fields_ = [("tolerance", C.c_double), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32)]
+
+
+class rm_converge_frame(C.Structure):
+    """The device buffers of a converging frame: sum, stats, count, workspace; optional mean, rgb8, mask (56 bytes)."""
+    _fields_ = [("sum", C.c_void_p), ("stats", C.c_void_p), ("count", C.c_void_p), ("workspace", C.c_void_p),
+                ("mean", C.c_void_p), ("rgb8", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class rm_converge_report(C.Structure):
+    """What a tick of a converging frame reports (24 bytes)."""
+    _fields_ = [("samples_cast", C.c_uint64), ("listed", C.c_uint32), ("passes", C.c_uint32), ("max_count", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 class rm_camera_basis(C.Structure):
     """The oriented camera's view direction: three world-space unit vectors (72 bytes)."""
     _fields_ = [("right", rm_vec3), ("up", rm_vec3), ("forward", rm_vec3)]
@@ -207,6 +224,11 @@ SIGNATURES = {
     "rm_accumulate_soft_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP]),
     "rm_render_progressive_soft": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), C.c_uint32, C.c_int, _P(C.c_double),
                                              _P(C.c_uint8), _P(C.c_uint32), _P(rm_timing)]),
+    "rm_converge_workspace": (C.c_int, [_P(rm_params), _P(C.c_size_t)]),
+    "rm_accumulate_converging_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, C.c_uint32, C.c_int,
+                                                  _P(rm_converge_frame), _VP]),
+    "rm_render_converging": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, C.c_int,
+                                       _P(C.c_double), _P(C.c_uint8), _P(rm_converge_report), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

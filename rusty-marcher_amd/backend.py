@@ -112,6 +112,21 @@ def _radii(radii, n_lights=None):
     return r
 
 
+def _converge(tolerance, min_samples, max_samples, n_samples, table_rows=PROGRESSIVE_MAX_SAMPLES):
+    """rm_converge of a converging frame: tolerance any number but NaN, min_samples an integer >= 0, max_samples an integer in
+    n_samples..min(table_rows, RM_PROGRESSIVE_MAX_SAMPLES)."""
+    tolerance = float(tolerance)
+    if tolerance != tolerance:
+        raise ValueError("tolerance must not be NaN")
+    for name, v in (("min_samples", min_samples), ("max_samples", max_samples)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v < 2 ** 32:
+            raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+    most = min(int(table_rows), PROGRESSIVE_MAX_SAMPLES)
+    if not n_samples <= max_samples <= most:
+        raise ValueError("max_samples must lie in n_samples..min(table rows, %d) = %d..%d, got %r" % (PROGRESSIVE_MAX_SAMPLES, n_samples, most, max_samples))
+    return _lib.rm_converge(tolerance, int(min_samples), int(max_samples))
+
+
 def _accumulate_args(device, params, sum, aperture, focus, table, n_before, mean, rgb8):
     """What accumulate_lens_device and accumulate_soft_device check of their common arguments -> (rm_lens, the table's tensor)."""
     torch = _torch()
@@ -660,6 +675,96 @@ class Context:
                                                      host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
                                                      C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
+
+    # ---- converging frames (include/rusty_marcher_amd.h, "converging frames") ----
+    def converge_workspace(self, params):
+        """rm_converge_workspace: bytes of device memory the list of accumulate_converging_device needs for `params`."""
+        b = C.c_size_t(0)
+        _lib.check(self.L.rm_converge_workspace(C.byref(params), C.byref(b)), None)
+        return b.value
+
+    def accumulate_converging_device(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples, max_samples,
+                                     fresh, offsets=None, mean=None, rgb8=None, mask=None, workspace=None, stream=None):
+        """rm_accumulate_converging_device: one pass of a converging frame -- the pixels still noisy by (tolerance, min_samples,
+        max_samples), and their neighbours, are listed on the device and n_samples (1..64) more samples are cast for the listed
+        pixels alone, each from the row of `table` its own count says.  sum (h, w, 3) and stats (h, w, 2) are contiguous float64
+        tensors and count (h, w) an int32 one on the context's device; with `fresh` they are not read and every count is 0.
+        table: the first rows of lens_sequence, at least max_samples of them, a float64 tensor (rows, 4) there or an array,
+        which is checked and copied over; offsets: optionally as many rows of light_sequence, (rows, n_lights, 3).  mean, rgb8
+        (h, w, 3) and mask (h, w, uint8) are optional outputs.  Asynchronous on `stream` (torch's current one by default).
+        -> the workspace, an int32 tensor: ws[0] is the number of listed pixels, ws[1:1 + ws[0]] their indices y * w + x."""
+        torch = _torch()
+        h, w = params.frame_height, params.frame_width
+        for name, t, dtype, shape in (("sum", sum, torch.float64, (h, w, 3)), ("stats", stats, torch.float64, (h, w, 2)),
+                                      ("count", count, torch.int32, (h, w)), ("mean", mean, torch.float64, (h, w, 3)),
+                                      ("rgb8", rgb8, torch.uint8, (h, w, 3)), ("mask", mask, torch.uint8, (h, w))):
+            if t is None and name in ("mean", "rgb8", "mask"):
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, shape))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
+        if mean is not None and mean.data_ptr() == sum.data_ptr():
+            raise ValueError("mean must not be the sum's own tensor")
+        lens = _lens(aperture, focus, n_samples)
+        if isinstance(table, torch.Tensor):
+            if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+                raise ValueError("table must be a contiguous float64 torch tensor of shape (rows, 4)")
+            if table.device != sum.device:
+                raise ValueError("table must live on %s, not %s" % (sum.device, table.device))
+        else:
+            rows = np.asarray(table)
+            table = torch.from_numpy(_lens_rows(rows, rows.shape[0] if rows.ndim == 2 else 0)).to(sum.device)
+        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples, table.shape[0])
+        n_lights = 0
+        if offsets is not None:
+            if isinstance(offsets, torch.Tensor):
+                if offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != table.shape[0] or offsets.shape[2] != 3 \
+                        or not offsets.is_contiguous():
+                    raise ValueError("offsets must be a contiguous float64 torch tensor of shape (%d, n_lights, 3)" % table.shape[0])
+                if offsets.device != sum.device:
+                    raise ValueError("offsets must live on %s, not %s" % (sum.device, offsets.device))
+            else:
+                off = np.ascontiguousarray(offsets, dtype=np.float64)
+                if off.ndim != 3 or off.shape[0] != table.shape[0] or off.shape[2] != 3 or not np.isfinite(off).all():
+                    raise ValueError("offsets must be a finite float64 array of shape (%d, n_lights, 3), got %s" % (table.shape[0], off.shape))
+                offsets = torch.from_numpy(off).to(sum.device)
+            n_lights = int(offsets.shape[1])
+        need = self.converge_workspace(params) // 4
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.int32, device=sum.device)
+        elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.shape[0] < need \
+                or not workspace.is_contiguous() or workspace.device != sum.device:
+            raise ValueError("workspace must be a contiguous int32 torch tensor of at least %d words on %s" % (need, sum.device))
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        _lib.check(self.L.rm_accumulate_converging_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), int(table.shape[0]),
+                                                          vp(offsets) if n_lights > 0 else None, n_lights, 1 if fresh else 0, C.byref(frame),
+                                                          C.c_void_p(self._stream(stream))), self.ptr)
+        return workspace
+
+    def render_converging(self, params, aperture, focus, n_samples, tolerance, min_samples, max_samples, radii=None, restart=False,
+                          host_rgb=None, host_rgb8=None):
+        """rm_render_converging: a tick of a converging frame the context keeps for the standing view, apart from
+        render_progressive's -- n_samples more samples of the library's sequences for the pixels still noisy and their
+        neighbours; radii: one radius a light for area lights, None for point lights.  Begun again as render_progressive_soft's
+        frame is; tolerance, min_samples, max_samples and n_samples may change while it goes on.  Once a tick lists nothing the
+        picture is finished and further ticks launch nothing.  -> (rm_timing, rm_converge_report)."""
+        lens = _lens(aperture, focus, n_samples)
+        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
+        r = _radii(radii) if radii is not None else None
+        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
+        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
+                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        timing, report = _lib.rm_timing(), _lib.rm_converge_report()
+        _lib.check(self.L.rm_render_converging(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
+                                               r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                               r.shape[0] if r is not None else 0, 1 if restart else 0,
+                                               host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
+                                               host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
+                                               C.byref(report), C.byref(timing)), self.ptr)
+        return timing, report
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

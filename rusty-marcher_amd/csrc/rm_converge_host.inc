@@ -1,0 +1,286 @@
+// rm_converge_host.inc -- host side of the converging frames (include/rusty_marcher_amd.h, "converging frames"); included at the
+// end of rm_device.hip, behind rm_soft_host.inc whose checks (check_accum_device, check_soft_lights, check_soft_radii) and
+// rm_accum_host.inc whose key (rm_progressive_key) it shares, and rm_refine_host.inc whose workspace size.  The kernels are
+// rm_converge.hip's.
+//
+// rm_accumulate_converging_device touches no render state and keeps all of its own in the caller's buffers: a memset of the
+// list's length, the select launch, the shade launch, all on the caller's stream, nothing waited for.  rm_render_converging is
+// that on the context's stream with buffers, a resident prefix of both sequences, a pass total and a key of its own
+// (rm_ctx::converging) -- nothing of rm_render_progressive's.
+
+// What both entry points check of rm_converge (ctx is not NULL); table_rows: what the table holds
+static rm_status check_converge(rm_ctx *ctx, const char *who, const rm_lens *lens, const rm_converge *c, uint64_t table_rows) {
+    if (!c) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL converge");
+    if (std::isnan(c->tolerance)) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": converge.tolerance is NaN");
+    const uint64_t most = std::min<uint64_t>(table_rows, RM_PROGRESSIVE_MAX_SAMPLES);
+    if (c->max_samples < lens->n_samples || c->max_samples > most) {
+        char buf[192];
+        std::snprintf(buf, sizeof buf, "%s: converge.max_samples = %u is outside n_samples..min(table_rows, %u) = %u..%llu", who, c->max_samples,
+                      RM_PROGRESSIVE_MAX_SAMPLES, lens->n_samples, (unsigned long long)most);
+        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
+    }
+    return RM_OK;
+}
+
+// The three steps on `stream`; everything was checked, rows > 0, table_rows >= n_samples and no listed pixel's slice ends
+// behind table_rows.  offsets: NULL for the lights where the scene image says.
+static rm_status launch_converge(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                 uint32_t table_rows, const void *offsets, int fresh, const rm_converge_frame *b, hipStream_t stream) {
+    ConvergeArgs a{};
+    a.L = lens_args(ctx, p, lens, table, nullptr);
+    a.tolerance = c->tolerance;
+    a.min_samples = c->min_samples;
+    a.max_samples = c->max_samples;
+    a.fresh = fresh ? 1u : 0u;
+    a.last_first = table_rows - lens->n_samples;
+    a.sum = static_cast<double *>(b->sum);
+    a.stats = static_cast<double *>(b->stats);
+    a.count = static_cast<uint32_t *>(b->count);
+    a.ws = static_cast<uint32_t *>(b->workspace);
+    a.mean = static_cast<double *>(b->mean);
+    a.rgb8 = static_cast<uint8_t *>(b->rgb8);
+    a.mask = static_cast<uint8_t *>(b->mask);
+    a.offsets = static_cast<const double *>(offsets);
+
+    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (launch_accum's rules)
+    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
+    const void *shade = rm_converge_shade_kernel(bvh, pow_mode, a.L.max_depth <= 5u ? 4 : 32, offsets != nullptr);
+    if (!shade) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "converging: no such kernel");
+    const uint32_t total = a.L.rows * a.L.frame_width;
+    uint32_t grid = 0;
+    if (rm_status gst = lens_grid(ctx, shade, total, a.L.n_samples, &grid)) return gst;
+
+    RM_HIP(ctx, hipMemsetAsync(b->workspace, 0, sizeof(uint32_t), stream));
+    void *select_args[] = {(void *)&a};
+    RM_HIP(ctx, hipLaunchKernel(rm_converge_select_kernel(), dim3((total + RM_CONVERGE_SELECT_LANES - 1u) / RM_CONVERGE_SELECT_LANES),
+                                dim3(RM_CONVERGE_SELECT_LANES), select_args, 0, stream));
+    void *shade_args[] = {(void *)&ctx->d_scene, (void *)&a};
+    RM_HIP(ctx, hipLaunchKernel(shade, dim3(grid), dim3(64), shade_args, 0, stream));
+    return RM_OK;
+}
+
+static rm_status rm_accumulate_converging_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c,
+                                                      const void *device_table, uint32_t table_rows, const void *device_offsets,
+                                                      uint32_t n_lights, int fresh, const rm_converge_frame *b, void *hip_stream) {
+    const char *who = "rm_accumulate_converging_device";
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    if (!b) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL buffers");
+    if (rm_status cst = check_accum_device(ctx, who, p, lens, device_table, 0u, b->sum, b->mean)) return cst;
+    if (device_offsets)
+        if (rm_status lst = check_soft_lights(ctx, who, n_lights)) return lst;
+    if (rm_status vst = check_converge(ctx, who, lens, c, table_rows)) return vst;
+    if (!b->stats) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL stats");
+    if (!b->count) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL count");
+    if (!b->workspace) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL workspace");
+    if (refine_rows(p) == 0u) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // (a scene without lights never fetches an offset: the kernel with stored lights)
+    return launch_converge(ctx, p, lens, c, device_table, table_rows, ctx->image.H.n_lights > 0u ? device_offsets : nullptr, fresh, b,
+                           (hipStream_t)hip_stream);
+}
+
+// The converging state of a context (rm_ctx::converging; made on the first call, released by rm_destroy)
+struct rm_converging {
+    void *d_table = nullptr, *d_offsets = nullptr;   // the resident prefix of rm_lens_sequence and of rm_light_sequence
+    uint32_t table_room = 0, table_rows = 0;         // rows d_table has room for / holds
+    uint32_t offsets_room = 0, offsets_rows = 0;     // the same of d_offsets, in rows of offsets_lights x 3 doubles
+    uint32_t offsets_lights = 0;
+    void *d_sum = nullptr, *d_stats = nullptr, *d_count = nullptr, *d_ws = nullptr, *d_mean = nullptr, *d_rgb8 = nullptr;
+    size_t pixels = 0;                               // the six buffers have room for that many
+    bool have_key = false;                           // a call has succeeded, and nothing failed half-way since
+    rm_progressive_key key;
+    std::vector<double> radii;                       // beside the key; empty: point lights
+    std::vector<double> staging;                     // the rows a call appends, host side
+    uint32_t n = 0;                                  // the pass total N: no pixel's count exceeds it (a bound, reached by the pixels sampled in every pass)
+    uint32_t passes = 0, listed = 0;                 // passes launched; pixels the last of them listed
+    uint64_t cast = 0;                               // samples cast over the frame's life
+    rm_converge last{};                              // what the last pass ran with
+    uint32_t last_ns = 0;
+};
+
+static void converging_destroy(rm_ctx *ctx, bool device_ok) {
+    rm_converging *g = ctx->converging;
+    if (!g) return;
+    for (void *b : {g->d_table, g->d_offsets, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8})
+        if (b && device_ok) (void)hipFree(b);
+    delete g;
+    ctx->converging = nullptr;
+}
+
+// Makes *d hold rows [0, need) of a sequence of `row_doubles` doubles a row: what it holds stays (copied on the device where the
+// buffer has to grow), rows [*have, need) are computed by fill(first, count, out) and appended on the context's stream.
+template <class FILL>
+static rm_status converging_extend(rm_ctx *ctx, rm_converging &g, void **d, uint32_t *room, uint32_t *have, uint32_t need, size_t row_doubles,
+                                   FILL fill) {
+    if (need <= *have) return RM_OK;
+    const size_t row_bytes = row_doubles * sizeof(double);
+    if (need > *room) {
+        const uint32_t grown = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 2ull * *room), RM_PROGRESSIVE_MAX_SAMPLES);
+        void *fresh = nullptr;
+        RM_HIP(ctx, hipMalloc(&fresh, (size_t)grown * row_bytes));
+        if (*d) {
+            hipError_t e = *have > 0u ? hipMemcpyAsync(fresh, *d, (size_t)*have * row_bytes, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // (the old buffer is freed below)
+            if (e != hipSuccess) {
+                (void)hipFree(fresh);
+                return ctx_fail(ctx, RM_ERR_HIP, std::string("converging: growing a sequence: ") + hipGetErrorString(e));
+            }
+            RM_HIP(ctx, hipFree(*d));
+        }
+        *d = fresh;
+        *room = grown;
+    }
+    const uint32_t first = *have, count = need - first;
+    g.staging.resize((size_t)count * row_doubles);
+    if (rm_status sst = fill(first, count, g.staging.data())) return sst;
+    RM_HIP(ctx, hipMemcpyAsync(static_cast<char *>(*d) + (size_t)first * row_bytes, g.staging.data(), (size_t)count * row_bytes,
+                               hipMemcpyHostToDevice, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));                        // (staging is reused by the next append)
+    *have = need;
+    return RM_OK;
+}
+
+static rm_status rm_render_converging_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const double *radii,
+                                           uint32_t n_lights, int restart, double *host_rgb, uint8_t *host_rgb8, rm_converge_report *report,
+                                           rm_timing *timing) {
+    const char *who = "rm_render_converging";
+    if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
+    const bool soft = radii != nullptr;
+    if (!soft) n_lights = 0u;                                              // point lights: no radii, whatever the count says
+    if (soft)
+        if (rm_status rst = check_soft_radii(ctx, who, radii, n_lights)) return rst;
+    if (rm_status vst = check_converge(ctx, who, lens, c, RM_PROGRESSIVE_MAX_SAMPLES)) return vst;
+    const uint32_t rows = refine_rows(p), ns = lens->n_samples;
+    double kernel_ms = 0., d2h_ms = 0.;
+    rm_converge_report rep{};
+    if (rows > 0u) {
+        if (!ctx->converging) ctx->converging = new rm_converging();
+        rm_converging &g = *ctx->converging;
+        rm_progressive_key key;
+        std::memset(&key, 0, sizeof key);
+        key.fov = p->fov; key.half_fov = p->half_fov; key.height = p->height; key.width = p->width; key.ratio = p->ratio;
+        key.frame_width = p->frame_width; key.frame_height = p->frame_height; key.max_depth = p->max_depth;
+        key.oriented = ctx->oriented ? 1u : 0u;
+        key.background = p->background;
+        key.aperture = lens->aperture; key.focus = lens->focus;
+        key.camera = ctx->camera;
+        key.basis = ctx->basis;
+        key.copies = ctx->upload_copies;
+        key.soft = soft ? 1u : 0u; key.n_lights = n_lights;
+        const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0 && g.radii.size() == n_lights &&
+                          (n_lights == 0u || std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) == 0);
+        // a finished picture: the pass before this one, with the same rule, listed nothing -- so would this one
+        const bool finished = same && g.passes > 0u && g.listed == 0u && g.last_ns == ns && std::memcmp(&g.last, c, sizeof *c) == 0;
+        const size_t pixels = (size_t)rows * p->frame_width;
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        if (!finished) {
+            g.have_key = false;                                            // (until this call is through)
+            if (!same) {
+                g.n = 0u; g.passes = 0u; g.listed = 0u; g.cast = 0u;
+                if (g.offsets_lights != n_lights || g.radii.size() != n_lights ||
+                    (n_lights > 0u && std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) != 0))
+                    g.offsets_rows = 0u;                                   // another sequence (the lens sequence is the same for every frame)
+                if (g.offsets_lights != n_lights) {
+                    if (g.d_offsets) RM_HIP(ctx, hipFree(g.d_offsets));
+                    g.d_offsets = nullptr;
+                    g.offsets_room = 0u;
+                    g.offsets_lights = n_lights;
+                }
+                g.radii.assign(radii, radii + n_lights);                   // (n_lights == 0: empty, radii is NULL)
+            }
+            if (g.pixels < pixels) {
+                for (void **b : {&g.d_sum, &g.d_stats, &g.d_count, &g.d_ws, &g.d_mean, &g.d_rgb8}) {
+                    if (*b) RM_HIP(ctx, hipFree(*b));
+                    *b = nullptr;
+                }
+                g.pixels = 0;
+                RM_HIP(ctx, hipMalloc(&g.d_sum, pixels * 3u * sizeof(double)));
+                RM_HIP(ctx, hipMalloc(&g.d_stats, pixels * 2u * sizeof(double)));
+                RM_HIP(ctx, hipMalloc(&g.d_count, pixels * sizeof(uint32_t)));
+                RM_HIP(ctx, hipMalloc(&g.d_ws, (4u * (1u + pixels) + 255u) & ~(size_t)255u));
+                RM_HIP(ctx, hipMalloc(&g.d_mean, pixels * 3u * sizeof(double)));
+                RM_HIP(ctx, hipMalloc(&g.d_rgb8, pixels * 3u));
+                g.pixels = pixels;
+            }
+            // no count exceeds N and no slice ends behind max_samples: rows [0, min(N + ns, max_samples)) serve this pass
+            const uint32_t need = (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)g.n + ns, c->max_samples), ns);
+            if (rm_status est = converging_extend(ctx, g, &g.d_table, &g.table_room, &g.table_rows, need, 4u, rm_lens_sequence)) return est;
+            const bool offsets = soft && n_lights > 0u;
+            if (offsets) {
+                const double *rr = g.radii.data();
+                auto fill = [=](uint32_t first, uint32_t count, double *out) { return rm_light_sequence(first, count, rr, n_lights, out); };
+                if (rm_status est = converging_extend(ctx, g, &g.d_offsets, &g.offsets_room, &g.offsets_rows, need, (size_t)n_lights * 3u, fill))
+                    return est;
+            }
+            const rm_converge_frame b{g.d_sum, g.d_stats, g.d_count, g.d_ws, g.d_mean, g.d_rgb8, nullptr};
+            RM_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+            // (the kernel is told what is resident -- at least `need` rows of either sequence -- so its clamp guards the buffers' end)
+            const uint32_t resident = offsets ? std::min(g.table_rows, g.offsets_rows) : g.table_rows;
+            if (rm_status lst = launch_converge(ctx, p, lens, c, g.d_table, resident, offsets ? g.d_offsets : nullptr, g.n == 0u, &b, ctx->stream))
+                return lst;
+            RM_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+            RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            uint32_t listed = 0;
+            RM_HIP(ctx, hipMemcpy(&listed, g.d_ws, sizeof listed, hipMemcpyDeviceToHost));
+            float ms = 0.f;
+            RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+            kernel_ms = ms;
+            g.key = key;
+            g.listed = listed;
+            g.passes += 1u;
+            g.cast += (uint64_t)listed * ns;
+            // N stays a bound on every count whatever n_samples and the cap were from tick to tick: a sampled pixel had c <= N and
+            // c + ns <= max_samples, so it holds at most min(N + ns, max_samples); a pass that sampled nothing raised no count
+            if (listed > 0u) g.n = std::max<uint32_t>(g.n, (uint32_t)std::min<uint64_t>((uint64_t)g.n + ns, c->max_samples));
+            g.last = *c;
+            g.last_ns = ns;
+            g.have_key = true;
+        }
+        rep.listed = finished ? 0u : g.listed;
+        rep.passes = g.passes;
+        rep.max_count = g.n;
+        rep.samples_cast = g.cast;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (host_rgb) RM_HIP(ctx, hipMemcpy(host_rgb, g.d_mean, pixels * 3u * sizeof(double), hipMemcpyDeviceToHost));
+        if (host_rgb8) RM_HIP(ctx, hipMemcpy(host_rgb8, g.d_rgb8, pixels * 3u, hipMemcpyDeviceToHost));
+        d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (report) *report = rep;
+    if (timing) {
+        timing->kernel_ms = kernel_ms;
+        timing->d2h_ms = d2h_ms;
+        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    return RM_OK;
+}
+
+extern "C" {
+
+rm_status rm_converge_workspace(const rm_params *params, size_t *bytes) {
+    if (!params || !bytes) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, "rm_converge_workspace: NULL argument");
+    if (params->frame_width % RM_PATCH_SIZE != 0)
+        return ctx_fail(nullptr, RM_ERR_DIMENSIONS, "rm_converge_workspace: frame width is not a multiple of 32");
+    *bytes = refine_workspace_bytes(params);
+    return RM_OK;
+}
+
+rm_status rm_accumulate_converging_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                                          const void *device_table, uint32_t table_rows, const void *device_offsets, uint32_t n_lights,
+                                          int fresh, const rm_converge_frame *buffers, void *hip_stream) {
+    return guarded(ctx, "rm_accumulate_converging_device", [&]() {
+        return rm_accumulate_converging_device_impl(ctx, params, lens, converge, device_table, table_rows, device_offsets, n_lights, fresh,
+                                                    buffers, hip_stream);
+    });
+}
+
+rm_status rm_render_converging(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge, const double *radii,
+                               uint32_t n_lights, int restart, double *host_rgb, uint8_t *host_rgb8, rm_converge_report *report,
+                               rm_timing *timing) {
+    return guarded(ctx, "rm_render_converging", [&]() {
+        return rm_render_converging_impl(ctx, params, lens, converge, radii, n_lights, restart, host_rgb, host_rgb8, report, timing);
+    });
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 #include "rm_lens.hpp"
 #include "rm_accum.hpp"
 #include "rm_soft.hpp"
+#include "rm_converge.hpp"
 
 using namespace rmdev;
 
@@ -118,6 +119,7 @@ struct rm_feedback {
 
 struct rm_hostio;   // rm_hostio.inc: staging buffer, row-scatter threads, display frame
 struct rm_progressive;   // rm_accum_host.inc: staged table, sum, mean and bytes of rm_render_progressive, its count and key
+struct rm_converging;    // rm_converge_host.inc: the buffers, resident sequences, pass total and key of rm_render_converging
 
 // The classification's output for the render launches on one stream: a mask per tile.  (Launches on a
 // stream are ordered: a render launch reads what the classification launch in front of it wrote, and the
@@ -222,6 +224,9 @@ struct rm_ctx {
     // progressive frames (rm_accum_host.inc): made by the first rm_render_progressive
     rm_progressive *progressive = nullptr;
 
+    // converging frames (rm_converge_host.inc): made by the first rm_render_converging; shares nothing with `progressive`
+    rm_converging *converging = nullptr;
+
     // post-process scratch
     unsigned long long *d_max = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -231,6 +236,7 @@ struct rm_ctx {
 static void hostio_destroy(rm_ctx *ctx, bool device_ok);
 static bool hostio_packs(rm_ctx *ctx, size_t band_bytes);
 static void progressive_destroy(rm_ctx *ctx, bool device_ok);
+static void converging_destroy(rm_ctx *ctx, bool device_ok);
 
 static rm_status ctx_fail(rm_ctx *ctx, rm_status st, const std::string &msg) {
     if (ctx) ctx->error = msg;
@@ -312,7 +318,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -369,6 +375,7 @@ void rm_destroy(rm_ctx *ctx) {
     const bool device_ok = !ctx->comm_stuck;
     hostio_destroy(ctx, device_ok);
     progressive_destroy(ctx, device_ok);
+    converging_destroy(ctx, device_ok);
     if (device_ok) {
         for (rm_frame_slot &s : ctx->slots) {
             // after a timed-out collective the slot's stream may never drain: leave it to process exit
@@ -1098,3 +1105,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_lens_host.inc"
 #include "rm_accum_host.inc"
 #include "rm_soft_host.inc"
+#include "rm_converge_host.inc"

@@ -301,6 +301,7 @@ struct Renderer {
     rm_timing last_timing{};
     uint32_t last_refined = 0;     // render_antialiased: pixels it refined
     uint32_t last_samples = 0;     // render_progressive: samples a pixel in its frame
+    rm_converge_report last_report{};   // render_converging: the last tick's report
 
     ~Renderer() { rm_destroy(ctx_); }
     Renderer(const Renderer &) = delete;
@@ -462,6 +463,29 @@ struct Renderer {
                 frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
             }
         return status(t0, frame.width, frame.height);
+    }
+    // A tick of a converging frame (rm_render_converging): render_progressive -- with area lights where `radii` holds one radius a
+    // light; empty: point lights -- that casts its n_samples more samples only for the pixels still noisy and their neighbours.  A
+    // pixel is settled once it has converge.min_samples samples and the standard error of the mean of r + g + b is at most
+    // converge.tolerance; none gets more than converge.max_samples.  The frame is the context's own for this call
+    // (render_progressive's is left alone) and begins again as render_progressive_soft's does.  Returns the tick's report, also left
+    // in last_report: listed == 0 says the picture is finished, and further ticks change nothing.
+    rm_converge_report render_converging(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const rm_converge &converge, uint32_t n_samples,
+                                         const std::vector<double> &radii = {}, double aperture = 0., double focus = 1., bool restart = false) {
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_converging(ctx_, &p, &lens, &converge, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), restart ? 1 : 0,
+                                   flat.data(), nullptr, &last_report, &last_timing),
+              ctx_);
+        last_samples = last_report.max_count;
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return last_report;
     }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.

@@ -24,6 +24,7 @@ class Renderer:
         self.last_timing = None
         self.last_refined = None                                           # render_antialiased: pixels it refined
         self.last_samples = None                                           # render_progressive: samples a pixel in its frame
+        self.last_report = None                                            # render_converging: the last tick's rm_converge_report
 
     def render(self, frame, scene):
         t0 = time.perf_counter()
@@ -172,6 +173,37 @@ class Renderer:
         """One frame with soft shadows: a restarted tick of render_progressive_soft -- n_samples (1..64) samples a pixel, through
         a pinhole unless an aperture is given."""
         return self.render_progressive_soft(frame, scene, light_radii, aperture, focus, n_samples, restart=True)
+
+    def render_converging(self, frame, scene, tolerance, n_samples, min_samples=16, max_samples=1024, light_radii=None, aperture=0., focus=1.,
+                          restart=False):
+        """A tick of a converging frame (rm_render_converging): render_progressive -- with area lights where light_radii is
+        given, one radius a light -- that casts its n_samples (1..64) more samples only for the pixels still noisy and their
+        neighbours.  A pixel is settled once it has min_samples samples and the standard error of the mean of r + g + b is at
+        most `tolerance`; none gets more than max_samples.  The frame is the context's own for this call -- render_progressive's
+        is left alone -- and begins again as render_progressive_soft's does; the tolerance and the sample numbers may change
+        while it goes on.  Prints what render() does and returns the tick's report: .listed pixels sampled by this tick (0: the
+        picture is finished, further ticks change nothing), .passes so far, .samples_cast over the frame's life, .max_count the
+        most samples a pixel can hold (also left in self.last_samples)."""
+        backend._converge(tolerance, min_samples, max_samples, backend._lens(aperture, focus, n_samples).n_samples)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        got = []
+
+        def call(ctx, p):
+            timing, report = ctx.render_converging(p, aperture, focus, n_samples, tolerance, min_samples, max_samples, radii, restart,
+                                                   host_rgb=frame.buffer)
+            got.append(report)
+            return timing, report.max_count
+
+        self._tick(frame, scene, call)
+        self.last_report = got[0]
+        return got[0]
+
+    def render_converged(self, frame, scene, tolerance, n_samples, min_samples=16, max_samples=1024, light_radii=None, aperture=0., focus=1.):
+        """A finished picture: a restarted render_converging ticked until a tick lists nothing.  -> the last tick's report."""
+        report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus, restart=True)
+        while report.listed > 0:
+            report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus)
+        return report
 
     def _tick(self, frame, scene, call):
         """What the progressive renders share: the prints and the return value of render(); call(ctx, params) ->

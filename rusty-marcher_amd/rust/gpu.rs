@@ -160,6 +160,41 @@ pub struct RmLens {
     pub _pad: u32,
 }
 
+/// `rm_converge`: when a pixel of a converging frame is settled -- the standard error of the mean of r + g + b it may keep
+/// (< 0: no pixel ever settles), the fewest samples a settled pixel has, the most any pixel gets (16 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmConverge {
+    pub tolerance: f64,
+    pub min_samples: u32,
+    pub max_samples: u32,
+}
+
+/// `rm_converge_frame`: the device buffers of a converging frame -- sum, stats, count, workspace; mean, rgb8 and mask may be
+/// null (56 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmConvergeFrame {
+    pub sum: *mut c_void,
+    pub stats: *mut c_void,
+    pub count: *mut c_void,
+    pub workspace: *mut c_void,
+    pub mean: *mut c_void,
+    pub rgb8: *mut c_void,
+    pub mask: *mut c_void,
+}
+
+/// `rm_converge_report`: what a tick of a converging frame reports; `listed == 0` says the picture is finished (24 bytes).
+#[repr(C)]
+#[derive(Copy, Clone, Default)]
+pub struct RmConvergeReport {
+    pub samples_cast: u64,
+    pub listed: u32,
+    pub passes: u32,
+    pub max_count: u32,
+    pub _pad: u32,
+}
+
 /// `rm_lights_visible`'s modes: the decision direct_lighting takes / the shadow ray ended at the light.
 pub const RM_LIGHTS_AS_RENDERED: u32 = 0;
 pub const RM_LIGHTS_CLIPPED: u32 = 1;
@@ -272,6 +307,9 @@ extern "C" {
     fn rm_light_sequence(first: u32, count: u32, radii: *const f64, n_lights: u32, offsets: *mut f64) -> c_int;
     fn rm_accumulate_soft_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_offsets: *const c_void, n_lights: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_progressive_soft(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_converge_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
+    fn rm_accumulate_converging_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_offsets: *const c_void, n_lights: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_converging(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -668,6 +706,105 @@ impl Gpu {
         check(unsafe { rm_light_sequence(first, count, radii.as_ptr(), radii.len() as u32, offsets.as_mut_ptr()) }, ptr::null());
         offsets.truncate(n);
         offsets
+    }
+
+    /// A tick of a converging frame: `render_progressive` -- with area lights where `radii` is given, one radius a light; `None`:
+    /// point lights -- that casts its `n_samples` more samples only for the pixels still noisy and their neighbours.  A pixel is
+    /// settled once it has `converge.min_samples` samples and the standard error of the mean of r + g + b is at most
+    /// `converge.tolerance`; none gets more than `converge.max_samples`.  The frame is the context's own for this call --
+    /// `render_progressive`'s is left alone -- and begins again as `render_progressive_soft`'s does; `converge` and `n_samples`
+    /// may change while it goes on.  Returns the status string and the tick's report: `listed == 0` says the picture is
+    /// finished, and further ticks launch nothing.
+    pub fn render_converging(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        converge: RmConverge,
+        radii: Option<&[f64]>,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, RmConvergeReport) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut report = RmConvergeReport::default();
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_converging(self.ctx, &p, &lens, &converge, radii_ptr, n_lights, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut report, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), report)
+    }
+
+    /// The device call under `render_converging` for a host that keeps its own device buffers (`rm_buffer_alloc`): one pass
+    /// over `buffers` -- the pixels still noisy and their neighbours are listed in `buffers.workspace`
+    /// (`converge_workspace` bytes) and sampled, each from the row of `device_table` its own count says.  `device_table`
+    /// holds the first `table_rows >= converge.max_samples` rows of `lens_sequence`, `device_offsets` as many of
+    /// `light_sequence` or null for point lights.  With `fresh` the buffers are not read.  Asynchronous on `hip_stream`.
+    pub fn accumulate_converging(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_offsets: *const c_void,
+        n_lights: u32,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_offsets, n_lights, if fresh { 1 } else { 0 }, &buffers, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// Bytes of device memory the list of `accumulate_converging` needs for a frame of that size.
+    pub fn converge_workspace(fov: f64, height: f64, width: f64, frame_width: usize, frame_height: usize) -> usize {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let mut bytes: usize = 0;
+        check(unsafe { rm_converge_workspace(&p, &mut bytes) }, ptr::null());
+        bytes
     }
 
     /// `render` with a device-resident FrameBuffer: the f64 frame stays on the GPU and only
