@@ -235,6 +235,13 @@ SIGNATURES = {
     "rm_kernel_name": (C.c_int, [_VP, _P(rm_params), C.c_char_p, C.c_size_t]),
 }
 
+# ... and the one internal hook with a prototype here (not part of the ABI; rm_plan.cpp): header[19], integer_exponents,
+# max_depth -> variant[3] = bvh, pow_mode, stack; total, rays_per_pixel, n_cus, per_cu, max_blocks -> *grid
+INTERNAL_SIGNATURES = {
+    "rmi_shading_launch": (C.c_int, [_P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                     C.c_uint32, _P(C.c_uint32)]),
+}
+
 _lib = None
 
 
@@ -261,7 +268,7 @@ def lib():
         # process would hold two runtimes and the second finds no device.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -43,11 +43,6 @@ __global__ __launch_bounds__(64) void rm_accum_shade_t(const double *__restrict_
 using namespace rmaccum;
 
 const void *rm_accum_kernel(bool bvh, int pow_mode, int stack) {
-#define RM_ROW(B, S)                                                                                   \
-    if (bvh == B && stack == S)                                                                        \
-        return pow_mode == POW_INTEGER ? (const void *)rm_accum_shade_t<B, POW_INTEGER, S>             \
-                                       : (const void *)rm_accum_shade_t<B, POW_GENERIC, S>;
-    RM_ROW(false, 4) RM_ROW(false, 32) RM_ROW(true, 4) RM_ROW(true, 32)
-#undef RM_ROW
+    RM_SHADING_TABLE(RM_SHADING_KERNEL, rm_accum_shade_t)
     return nullptr;
 }

@@ -8,22 +8,11 @@ namespace rmaccum {
 
 using namespace rmradiance;
 
-__device__ __forceinline__ uint8_t to_byte(double v) {                   // framebuffer.rs:80-82, the render epilogue's rule
-    return (uint8_t)(255. * __builtin_fmin(__builtin_fmax(v, 0.), 1.));
-}
-
 template <bool BVH, int POW, int STACK, class LIGHTS_OF>
 __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blob, const AccumArgs &a, uint32_t *bstack, double *sums,
                                             LIGHTS_OF lights_of) {
     const LensArgs &q = a.L;
-    SceneView sc;
-    sc.S = scene_blob;                // (as rm_lens_shade_t)
-    sc.G = scene_blob;
-    sc.cull_bounds = scene_blob + q.H.off_bounds;
-    sc.cull_planar = scene_blob + q.H.off_planar;
-    sc.bstack = bstack;
-    sc.cull_cos = 2.;
-    sc.H = q.H;
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
 
     const uint32_t total = q.rows * q.frame_width;                       // (below 2^31: the host checked)
     const uint32_t ns = q.n_samples, P = 64u / ns;

@@ -1,6 +1,6 @@
 // rm_accum_host.inc -- host side of the progressive frames (include/rusty_marcher_amd.h, "progressive frames"); included at the
-// end of rm_device.hip, behind rm_lens_host.inc whose checks (check_lens), argument block (lens_args), grid (lens_grid, with
-// RM_LENS_MAX_BLOCKS) and occupancy cache it reuses.  The kernel is rm_accum.hip's.
+// end of rm_device.hip, behind rm_lens_host.inc whose checks (check_lens), argument block (lens_args) and grid (lens_extent, with
+// RM_LENS_MAX_BLOCKS) it reuses.  The kernel is rm_accum.hip's.
 //
 // rm_accumulate_lens_device touches no render state and keeps none of its own: one launch on the caller's stream, nothing
 // waited for.  rm_render_progressive is that on the context's stream with a staged slice of rm_lens_sequence and three
@@ -40,16 +40,7 @@ static rm_status launch_accum(rm_ctx *ctx, const rm_params *p, const rm_lens *le
     a.sum = static_cast<double *>(sum);
     a.mean = static_cast<double *>(mean);
     a.rgb8 = static_cast<uint8_t *>(rgb8);
-
-    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (launch_lens's rules)
-    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
-    const void *fn = rm_accum_kernel(bvh, pow_mode, a.L.max_depth <= 5u ? 4 : 32);
-    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "progressive: no such kernel");
-    uint32_t grid = 0;
-    if (rm_status gst = lens_grid(ctx, fn, a.L.rows * a.L.frame_width, a.L.n_samples, &grid)) return gst;
-    void *args[] = {(void *)&ctx->d_scene, (void *)&a};
-    RM_HIP(ctx, hipLaunchKernel(fn, dim3(grid), dim3(64), args, 0, stream));
-    return RM_OK;
+    return launch_shading(ctx, shade_family{"progressive", rm_accum_kernel}, a.L.max_depth, lens_extent(ctx, a.L), a, stream);
 }
 
 // What the device calls (this one and rm_accumulate_soft_device) check of their own arguments (ctx is not NULL).
@@ -89,6 +80,21 @@ struct rm_progressive_key {
     uint32_t soft, n_lights;                 // rm_render_progressive_soft's frames: 1 and the radii's count (their bytes: rm_progressive::radii); else 0, 0
 };
 
+static rm_progressive_key progressive_key_of(const rm_ctx *ctx, const rm_params *p, const rm_lens *lens, bool soft, uint32_t n_lights) {
+    rm_progressive_key key;
+    std::memset(&key, 0, sizeof key);
+    key.fov = p->fov; key.half_fov = p->half_fov; key.height = p->height; key.width = p->width; key.ratio = p->ratio;
+    key.frame_width = p->frame_width; key.frame_height = p->frame_height; key.max_depth = p->max_depth;
+    key.oriented = ctx->oriented ? 1u : 0u;
+    key.background = p->background;
+    key.aperture = lens->aperture; key.focus = lens->focus;
+    key.camera = ctx->camera;
+    key.basis = ctx->basis;
+    key.copies = ctx->upload_copies;
+    key.soft = soft ? 1u : 0u; key.n_lights = n_lights;
+    return key;
+}
+
 // The progressive state of a context (rm_ctx::progressive; made on the first call, released by rm_destroy)
 struct rm_progressive {
     void *d_table = nullptr;                 // RM_LENS_MAX_SAMPLES rows
@@ -101,7 +107,7 @@ struct rm_progressive {
     // area lights (rm_soft_host.inc): the radii the sum belongs to, beside the key, and the staged slice of rm_light_sequence
     std::vector<double> radii, offsets;
     void *d_offsets = nullptr;
-    size_t offsets_room = 0;                 // doubles d_offsets has room for
+    size_t offsets_bytes = 0;                // d_offsets has room for that many
 };
 
 // rm_soft_host.inc: the check of a soft tick's radii, and the launch with an offset table
@@ -134,17 +140,7 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
     if (rows > 0u) {
         if (!ctx->progressive) ctx->progressive = new rm_progressive();
         rm_progressive &g = *ctx->progressive;
-        rm_progressive_key key;
-        std::memset(&key, 0, sizeof key);
-        key.fov = p->fov; key.half_fov = p->half_fov; key.height = p->height; key.width = p->width; key.ratio = p->ratio;
-        key.frame_width = p->frame_width; key.frame_height = p->frame_height; key.max_depth = p->max_depth;
-        key.oriented = ctx->oriented ? 1u : 0u;
-        key.background = p->background;
-        key.aperture = lens->aperture; key.focus = lens->focus;
-        key.camera = ctx->camera;
-        key.basis = ctx->basis;
-        key.copies = ctx->upload_copies;
-        key.soft = soft ? 1u : 0u; key.n_lights = n_lights;
+        const rm_progressive_key key = progressive_key_of(ctx, p, lens, soft, n_lights);
         const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0 && g.radii.size() == n_lights &&
                           (n_lights == 0u || std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) == 0);
         const uint32_t n_before = same ? g.n : 0u;
@@ -155,44 +151,30 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
             g.have_key = false;                                            // (until this call is through)
             if (!g.d_table) RM_HIP(ctx, hipMalloc(&g.d_table, sizeof g.table));
             if (g.pixels < pixels) {
-                for (void **b : {&g.d_sum, &g.d_mean, &g.d_rgb8}) {
-                    if (*b) RM_HIP(ctx, hipFree(*b));
-                    *b = nullptr;
-                }
                 g.pixels = 0;
-                RM_HIP(ctx, hipMalloc(&g.d_sum, pixels * 3u * sizeof(double)));
-                RM_HIP(ctx, hipMalloc(&g.d_mean, pixels * 3u * sizeof(double)));
-                RM_HIP(ctx, hipMalloc(&g.d_rgb8, pixels * 3u));
+                const std::pair<void **, size_t> buffers[] = {{&g.d_sum, pixels * 3u * sizeof(double)}, {&g.d_mean, pixels * 3u * sizeof(double)},
+                                                              {&g.d_rgb8, pixels * 3u}};
+                for (const auto &b : buffers) {
+                    size_t none = 0;                                       // (every one is replaced: they share one size)
+                    if (rm_status gst = grow_device_buffer(ctx, b.first, &none, b.second)) return gst;
+                }
                 g.pixels = pixels;
             }
             if (rm_status sst = rm_lens_sequence(n_before, lens->n_samples, g.table)) return sst;
             RM_HIP(ctx, hipMemcpyAsync(g.d_table, g.table, (size_t)lens->n_samples * 4u * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             const size_t n_offsets = (size_t)lens->n_samples * n_lights * 3u;
             if (n_offsets > 0u) {                                          // (soft, and the scene has lights)
-                if (g.offsets_room < n_offsets) {
-                    if (g.d_offsets) RM_HIP(ctx, hipFree(g.d_offsets));
-                    g.d_offsets = nullptr;
-                    g.offsets_room = 0;
-                    RM_HIP(ctx, hipMalloc(&g.d_offsets, n_offsets * sizeof(double)));
-                    g.offsets_room = n_offsets;
-                }
+                if (rm_status gst = grow_device_buffer(ctx, &g.d_offsets, &g.offsets_bytes, n_offsets * sizeof(double))) return gst;
                 g.offsets.resize(n_offsets);
                 if (rm_status sst = rm_light_sequence(n_before, lens->n_samples, radii, n_lights, g.offsets.data())) return sst;
                 RM_HIP(ctx, hipMemcpyAsync(g.d_offsets, g.offsets.data(), n_offsets * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             }
-            RM_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-            if (soft) {
-                if (rm_status lst = launch_soft(ctx, p, lens, g.d_table, n_offsets > 0u ? g.d_offsets : nullptr, n_before, g.d_sum, g.d_mean,
-                                                g.d_rgb8, ctx->stream))
-                    return lst;
-            } else if (rm_status lst = launch_accum(ctx, p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream)) {
-                return lst;
-            }
-            RM_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-            RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            float ms = 0.f;
-            RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-            kernel_ms = ms;
+            auto launch = [&]() {
+                return soft ? launch_soft(ctx, p, lens, g.d_table, n_offsets > 0u ? g.d_offsets : nullptr, n_before, g.d_sum, g.d_mean, g.d_rgb8,
+                                          ctx->stream)
+                            : launch_accum(ctx, p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream);
+            };
+            if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
             g.key = key;
             g.radii.assign(radii, radii + n_lights);                       // (n_lights == 0: empty, radii may be NULL)
             g.n = n_before + lens->n_samples;
@@ -205,11 +187,7 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
         d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     if (n_total) *n_total = total;
-    if (timing) {
-        timing->kernel_ms = kernel_ms;
-        timing->d2h_ms = d2h_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
+    fill_timing(timing, kernel_ms, d2h_ms, t_begin);
     return RM_OK;
 }
 

@@ -47,19 +47,6 @@ namespace rmconverge {
 
 using namespace rmradiance;
 
-__device__ __forceinline__ uint8_t to_byte(double v) {                   // framebuffer.rs:80-82, the render epilogue's rule
-    return (uint8_t)(255. * __builtin_fmin(__builtin_fmax(v, 0.), 1.));
-}
-
-// Light i of the lane's sample: the scene's position plus the sample's row of the offset table (rm_soft.hip's rule)
-struct OffsetLights {
-    const double *row;                                                   // n_lights x 3 doubles
-    __device__ __forceinline__ V3 operator()(const double *lt, uint32_t i) const {
-        const double *o = row + 3u * i;
-        return mk(lt[0] + o[0], lt[1] + o[1], lt[2] + o[2]);
-    }
-};
-
 // The pixel's count as the pass sees it
 __device__ __forceinline__ uint32_t count_of(const ConvergeArgs &a, uint32_t pix) { return a.fresh ? 0u : a.count[pix]; }
 
@@ -107,14 +94,7 @@ __global__ __launch_bounds__(64) void rm_converge_shade_t(const double *__restri
     __shared__ uint32_t bstack[64];
     __shared__ double sums[64 * 3];
     const LensArgs &q = a.L;
-    SceneView sc;
-    sc.S = scene_blob;                // (as rm_lens_shade_t)
-    sc.G = scene_blob;
-    sc.cull_bounds = scene_blob + q.H.off_bounds;
-    sc.cull_planar = scene_blob + q.H.off_planar;
-    sc.bstack = bstack;
-    sc.cull_cos = 2.;
-    sc.H = q.H;
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
 
     const uint32_t total = q.rows * q.frame_width;                       // (below 2^31: the host checked)
     const uint32_t listed = min(uniform_u32(a.ws[0]), total);            // read once; held to the frame (the head of the file: a workspace damaged between the launches)
@@ -207,15 +187,8 @@ using namespace rmconverge;
 const void *rm_converge_select_kernel() { return (const void *)rm_converge_select; }
 
 const void *rm_converge_shade_kernel(bool bvh, int pow_mode, int stack, bool offset) {
-#define RM_ROW(B, S)                                                                                                     \
-    if (bvh == B && stack == S) {                                                                                        \
-        if (offset)                                                                                                      \
-            return pow_mode == POW_INTEGER ? (const void *)rm_converge_shade_t<B, POW_INTEGER, S, true>                  \
-                                           : (const void *)rm_converge_shade_t<B, POW_GENERIC, S, true>;                 \
-        return pow_mode == POW_INTEGER ? (const void *)rm_converge_shade_t<B, POW_INTEGER, S, false>                     \
-                                       : (const void *)rm_converge_shade_t<B, POW_GENERIC, S, false>;                    \
-    }
-    RM_ROW(false, 4) RM_ROW(false, 32) RM_ROW(true, 4) RM_ROW(true, 32)
-#undef RM_ROW
+#define RM_CONVERGE_KERNEL(K, B, S) (offset ? RM_SHADING_KERNEL(K, B, S, true) : RM_SHADING_KERNEL(K, B, S, false))
+    RM_SHADING_TABLE(RM_CONVERGE_KERNEL, rm_converge_shade_t)
+#undef RM_CONVERGE_KERNEL
     return nullptr;
 }

@@ -42,21 +42,18 @@ static rm_status launch_converge(rm_ctx *ctx, const rm_params *p, const rm_lens 
     a.mask = static_cast<uint8_t *>(b->mask);
     a.offsets = static_cast<const double *>(offsets);
 
-    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (launch_accum's rules)
-    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
-    const void *shade = rm_converge_shade_kernel(bvh, pow_mode, a.L.max_depth <= 5u ? 4 : 32, offsets != nullptr);
-    if (!shade) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "converging: no such kernel");
-    const uint32_t total = a.L.rows * a.L.frame_width;
-    uint32_t grid = 0;
-    if (rm_status gst = lens_grid(ctx, shade, total, a.L.n_samples, &grid)) return gst;
-
-    RM_HIP(ctx, hipMemsetAsync(b->workspace, 0, sizeof(uint32_t), stream));
-    void *select_args[] = {(void *)&a};
-    RM_HIP(ctx, hipLaunchKernel(rm_converge_select_kernel(), dim3((total + RM_CONVERGE_SELECT_LANES - 1u) / RM_CONVERGE_SELECT_LANES),
-                                dim3(RM_CONVERGE_SELECT_LANES), select_args, 0, stream));
-    void *shade_args[] = {(void *)&ctx->d_scene, (void *)&a};
-    RM_HIP(ctx, hipLaunchKernel(shade, dim3(grid), dim3(64), shade_args, 0, stream));
-    return RM_OK;
+    // the two families: lights where the scene image says, and lights moved by the sample's row of `offsets`
+    const shade_family stored{"converging", [](bool bvh, int pow_mode, int stack) { return rm_converge_shade_kernel(bvh, pow_mode, stack, false); }};
+    const shade_family moved{"converging", [](bool bvh, int pow_mode, int stack) { return rm_converge_shade_kernel(bvh, pow_mode, stack, true); }};
+    auto select = [&]() -> rm_status {
+        const uint32_t total = a.L.rows * a.L.frame_width;
+        RM_HIP(ctx, hipMemsetAsync(b->workspace, 0, sizeof(uint32_t), stream));
+        void *select_args[] = {(void *)&a};
+        RM_HIP(ctx, hipLaunchKernel(rm_converge_select_kernel(), dim3((total + RM_CONVERGE_SELECT_LANES - 1u) / RM_CONVERGE_SELECT_LANES),
+                                    dim3(RM_CONVERGE_SELECT_LANES), select_args, 0, stream));
+        return RM_OK;
+    };
+    return launch_shading(ctx, offsets ? moved : stored, a.L.max_depth, lens_extent(ctx, a.L), a, stream, select);
 }
 
 static rm_status rm_accumulate_converging_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c,
@@ -158,17 +155,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const rm_params *p, cons
     if (rows > 0u) {
         if (!ctx->converging) ctx->converging = new rm_converging();
         rm_converging &g = *ctx->converging;
-        rm_progressive_key key;
-        std::memset(&key, 0, sizeof key);
-        key.fov = p->fov; key.half_fov = p->half_fov; key.height = p->height; key.width = p->width; key.ratio = p->ratio;
-        key.frame_width = p->frame_width; key.frame_height = p->frame_height; key.max_depth = p->max_depth;
-        key.oriented = ctx->oriented ? 1u : 0u;
-        key.background = p->background;
-        key.aperture = lens->aperture; key.focus = lens->focus;
-        key.camera = ctx->camera;
-        key.basis = ctx->basis;
-        key.copies = ctx->upload_copies;
-        key.soft = soft ? 1u : 0u; key.n_lights = n_lights;
+        const rm_progressive_key key = progressive_key_of(ctx, p, lens, soft, n_lights);
         const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0 && g.radii.size() == n_lights &&
                           (n_lights == 0u || std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) == 0);
         // a finished picture: the pass before this one, with the same rule, listed nothing -- so would this one
@@ -191,17 +178,14 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const rm_params *p, cons
                 g.radii.assign(radii, radii + n_lights);                   // (n_lights == 0: empty, radii is NULL)
             }
             if (g.pixels < pixels) {
-                for (void **b : {&g.d_sum, &g.d_stats, &g.d_count, &g.d_ws, &g.d_mean, &g.d_rgb8}) {
-                    if (*b) RM_HIP(ctx, hipFree(*b));
-                    *b = nullptr;
-                }
                 g.pixels = 0;
-                RM_HIP(ctx, hipMalloc(&g.d_sum, pixels * 3u * sizeof(double)));
-                RM_HIP(ctx, hipMalloc(&g.d_stats, pixels * 2u * sizeof(double)));
-                RM_HIP(ctx, hipMalloc(&g.d_count, pixels * sizeof(uint32_t)));
-                RM_HIP(ctx, hipMalloc(&g.d_ws, (4u * (1u + pixels) + 255u) & ~(size_t)255u));
-                RM_HIP(ctx, hipMalloc(&g.d_mean, pixels * 3u * sizeof(double)));
-                RM_HIP(ctx, hipMalloc(&g.d_rgb8, pixels * 3u));
+                const std::pair<void **, size_t> buffers[] = {
+                    {&g.d_sum, pixels * 3u * sizeof(double)}, {&g.d_stats, pixels * 2u * sizeof(double)}, {&g.d_count, pixels * sizeof(uint32_t)},
+                    {&g.d_ws, (4u * (1u + pixels) + 255u) & ~(size_t)255u}, {&g.d_mean, pixels * 3u * sizeof(double)}, {&g.d_rgb8, pixels * 3u}};
+                for (const auto &b : buffers) {
+                    size_t none = 0;                                       // (every one is replaced: they share one size)
+                    if (rm_status gst = grow_device_buffer(ctx, b.first, &none, b.second)) return gst;
+                }
                 g.pixels = pixels;
             }
             // no count exceeds N and no slice ends behind max_samples: rows [0, min(N + ns, max_samples)) serve this pass
@@ -215,18 +199,14 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const rm_params *p, cons
                     return est;
             }
             const rm_converge_frame b{g.d_sum, g.d_stats, g.d_count, g.d_ws, g.d_mean, g.d_rgb8, nullptr};
-            RM_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
             // (the kernel is told what is resident -- at least `need` rows of either sequence -- so its clamp guards the buffers' end)
             const uint32_t resident = offsets ? std::min(g.table_rows, g.offsets_rows) : g.table_rows;
-            if (rm_status lst = launch_converge(ctx, p, lens, c, g.d_table, resident, offsets ? g.d_offsets : nullptr, g.n == 0u, &b, ctx->stream))
-                return lst;
-            RM_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-            RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            auto launch = [&]() {
+                return launch_converge(ctx, p, lens, c, g.d_table, resident, offsets ? g.d_offsets : nullptr, g.n == 0u, &b, ctx->stream);
+            };
+            if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
             uint32_t listed = 0;
             RM_HIP(ctx, hipMemcpy(&listed, g.d_ws, sizeof listed, hipMemcpyDeviceToHost));
-            float ms = 0.f;
-            RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-            kernel_ms = ms;
             g.key = key;
             g.listed = listed;
             g.passes += 1u;
@@ -248,11 +228,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const rm_params *p, cons
         d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     if (report) *report = rep;
-    if (timing) {
-        timing->kernel_ms = kernel_ms;
-        timing->d2h_ms = d2h_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
+    fill_timing(timing, kernel_ms, d2h_ms, t_begin);
     return RM_OK;
 }
 

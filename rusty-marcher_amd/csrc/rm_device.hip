@@ -208,18 +208,18 @@ struct rm_ctx {
     void *d_query = nullptr;
     size_t query_bytes = 0;
 
-    // adaptive anti-aliasing (rm_refine_host.inc): the workspace of rm_render_antialiased (grown on demand), and what
-    // hipOccupancyMaxActiveBlocksPerMultiprocessor said of the shade kernels launched so far
+    // the shading launches (rm_shade_host.inc): the workgroups a compute unit holds of every shading kernel launched so far,
+    // by kernel address, asked once a kernel and context
+    std::vector<std::pair<const void *, int>> shade_occupancy;
+
+    // adaptive anti-aliasing (rm_refine_host.inc): the workspace of rm_render_antialiased (grown on demand)
     void *d_refine_ws = nullptr;
     size_t refine_ws_bytes = 0;
-    std::vector<std::pair<const void *, int>> refine_occupancy;
 
-    // the thin-lens camera (rm_lens_host.inc): the table and the frame rm_render_lens renders with (the frame grown on demand),
-    // and what hipOccupancyMaxActiveBlocksPerMultiprocessor said of the lens kernels launched so far
+    // the thin-lens camera (rm_lens_host.inc): the table and the frame rm_render_lens renders with (the frame grown on demand)
     void *d_lens_table = nullptr;
     void *d_lens_frame = nullptr;
     size_t lens_frame_bytes = 0;
-    std::vector<std::pair<const void *, int>> lens_occupancy;
 
     // progressive frames (rm_accum_host.inc): made by the first rm_render_progressive
     rm_progressive *progressive = nullptr;
@@ -275,6 +275,17 @@ static T *entry_of(std::vector<T> &v, hipStream_t stream) {
             return ctx_fail(ctx, RM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
+// Makes the context-owned device buffer *d hold `need` bytes (*have: what it holds): a larger one stays, a smaller one is
+// freed and replaced, nothing is kept.  A failed allocation leaves *d NULL and *have 0.
+static rm_status grow_device_buffer(rm_ctx *ctx, void **d, size_t *have, size_t need) {
+    if (*have >= need) return RM_OK;
+    if (*d) RM_HIP(ctx, hipFree(*d));
+    *d = nullptr;
+    *have = 0;
+    RM_HIP(ctx, hipMalloc(d, need));
+    *have = need;
+    return RM_OK;
+}
 
 // The kernel instantiations live in rm_kernels.hip, one object per numeric flavour and kernel
 // group (STAGED: LDS copy of the scene for the per-lane gathers; BVH: hierarchy walk for wide
@@ -1100,6 +1111,7 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_exchange.inc"
 #include "rm_hostio.inc"
 #include "rm_query_host.inc"
+#include "rm_shade_host.inc"
 #include "rm_radiance_host.inc"
 #include "rm_refine_host.inc"
 #include "rm_lens_host.inc"

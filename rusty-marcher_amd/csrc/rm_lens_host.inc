@@ -1,6 +1,5 @@
 // rm_lens_host.inc -- host side of the thin-lens camera (include/rusty_marcher_amd.h, "thin-lens camera"); included at the end
-// of rm_device.hip, behind rm_refine_host.inc whose row count it shares and rm_radiance_host.inc whose checks.  The kernel is
-// rm_lens.hip's.
+// of rm_device.hip, behind rm_shade_host.inc whose checks and launch path it shares.  The kernel is rm_lens.hip's.
 //
 // rm_render_lens_device touches no render state and keeps none of its own: one launch on the caller's stream, nothing waited
 // for.  rm_render_lens is that on the context's stream with a table buffer and a frame buffer the context owns, and the copy;
@@ -10,12 +9,7 @@
 
 // What both entry points check before anything is launched (ctx is not NULL).
 static rm_status check_lens(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, const void *table, const void *frame) {
-    if (rm_status pst = check_query_params(ctx, p, who)) return pst;
-    if (p->frame_width % RM_PATCH_SIZE != 0)
-        return ctx_fail(ctx, RM_ERR_DIMENSIONS, std::string(who) + ": frame width is not a multiple of 32 (no render writes such a frame)");
-    if ((uint64_t)refine_rows(p) * p->frame_width > 0x7fffffffull)
-        return ctx_fail(ctx, RM_ERR_DIMENSIONS, std::string(who) + ": more than 2^31 - 1 pixels");
-    if (rm_status cst = check_shading(ctx, who, p->background, p->max_depth)) return cst;
+    if (rm_status fst = check_sample_frame(ctx, who, p)) return fst;
     if (!lens) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL lens");
     char buf[160];
     if (!std::isfinite(lens->aperture) || !(lens->aperture >= 0.)) {
@@ -52,30 +46,10 @@ static rm_status check_lens_table(rm_ctx *ctx, const char *who, const double *t,
     return RM_OK;
 }
 
-// Workgroups of the launch: what the device holds at once (CUs x the kernel's occupancy, asked once per kernel and context), at
-// most what the frame needs, at most RM_LENS_MAX_BLOCKS where that is set.
-static rm_status lens_grid(rm_ctx *ctx, const void *fn, uint32_t total, uint32_t n_samples, uint32_t *grid) {
-    int per_cu = 0;
-    for (const auto &e : ctx->lens_occupancy)
-        if (e.first == fn) per_cu = e.second;
-    if (per_cu == 0) {
-        RM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0));
-        per_cu = std::max(1, per_cu);
-        ctx->lens_occupancy.emplace_back(fn, per_cu);
-    }
-    const uint32_t P = 64u / n_samples;
-    const uint64_t need = ((uint64_t)total + P - 1u) / P;
-    uint64_t g = std::min<uint64_t>(need, (uint64_t)std::max(1, ctx->prop.multiProcessorCount) * (uint64_t)per_cu);
-    if (ctx->knobs.lens_max_blocks > 0u) g = std::min<uint64_t>(g, ctx->knobs.lens_max_blocks);
-    *grid = (uint32_t)std::max<uint64_t>(g, 1u);
-    return RM_OK;
-}
-
-// The argument block of a launch (rm_accum_host.inc's launches carry one too); everything was checked.
+// The argument block of a launch (the progressive, soft and converging launches carry one too); everything was checked.
 static LensArgs lens_args(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, void *frame) {
     LensArgs q{};
-    q.H = ctx->image.H;
-    q.H.off_occ = 0u;                                                      // (as launch_radiance)
+    q.H = shading_header(ctx);
     q.frame_width = p->frame_width;
     q.rows = refine_rows(p);
     q.n_samples = lens->n_samples;
@@ -83,31 +57,22 @@ static LensArgs lens_args(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, 
     q.oriented = ctx->oriented ? 1u : 0u;
     q.aperture = lens->aperture;
     q.focus = lens->focus;
-    q.bg_x = p->background.x; q.bg_y = p->background.y; q.bg_z = p->background.z;
-    q.width = p->width; q.height = p->height; q.half_fov = p->half_fov; q.ratio = p->ratio;
-    q.cam_x = ctx->camera.x; q.cam_y = ctx->camera.y; q.cam_z = ctx->camera.z;
     const rm_camera_basis fixed{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
-    const rm_camera_basis &cb = ctx->oriented ? ctx->basis : fixed;
-    q.cam_rx = cb.right.x; q.cam_ry = cb.right.y; q.cam_rz = cb.right.z;
-    q.cam_ux = cb.up.x; q.cam_uy = cb.up.y; q.cam_uz = cb.up.z;
-    q.cam_fx = cb.forward.x; q.cam_fy = cb.forward.y; q.cam_fz = cb.forward.z;
+    fill_view(q, ctx, p, ctx->oriented ? ctx->basis : fixed);               // (the lens point is formed from the basis in either view)
     q.table = static_cast<const double *>(table);
     q.frame = static_cast<double *>(frame);
     return q;
 }
 
+// The workgroups of a launch over the pixels of `q`, n_samples rays each: what the frame needs, capped by RM_LENS_MAX_BLOCKS
+static shade_extent lens_extent(const rm_ctx *ctx, const LensArgs &q) {
+    return shade_extent{0u, q.rows * q.frame_width, q.n_samples, ctx->knobs.lens_max_blocks};
+}
+
 // The launch on `stream`; everything was checked, rows > 0.
 static rm_status launch_lens(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, void *frame, hipStream_t stream) {
     LensArgs q = lens_args(ctx, p, lens, table, frame);
-    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (the radiance kernels' rules: launch_radiance)
-    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
-    const void *fn = rm_lens_kernel(bvh, pow_mode, q.max_depth <= 5u ? 4 : 32);
-    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "lens: no such kernel");
-    uint32_t grid = 0;
-    if (rm_status gst = lens_grid(ctx, fn, q.rows * q.frame_width, q.n_samples, &grid)) return gst;
-    void *args[] = {(void *)&ctx->d_scene, (void *)&q};
-    RM_HIP(ctx, hipLaunchKernel(fn, dim3(grid), dim3(64), args, 0, stream));
-    return RM_OK;
+    return launch_shading(ctx, shade_family{"lens", rm_lens_kernel}, q.max_depth, lens_extent(ctx, q), q, stream);
 }
 
 static rm_status rm_render_lens_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table, void *device_rgb,
@@ -133,30 +98,15 @@ static rm_status rm_render_lens_impl(rm_ctx *ctx, const rm_params *p, const rm_l
         RM_HIP(ctx, hipSetDevice(ctx->device));
         if (!ctx->d_lens_table) RM_HIP(ctx, hipMalloc(&ctx->d_lens_table, RM_LENS_MAX_SAMPLES * 4u * sizeof(double)));
         const size_t need = (size_t)rows * p->frame_width * 3u * sizeof(double);
-        if (ctx->lens_frame_bytes < need) {
-            if (ctx->d_lens_frame) RM_HIP(ctx, hipFree(ctx->d_lens_frame));
-            ctx->d_lens_frame = nullptr;
-            ctx->lens_frame_bytes = 0;
-            RM_HIP(ctx, hipMalloc(&ctx->d_lens_frame, need));
-            ctx->lens_frame_bytes = need;
-        }
+        if (rm_status gst = grow_device_buffer(ctx, &ctx->d_lens_frame, &ctx->lens_frame_bytes, need)) return gst;
         RM_HIP(ctx, hipMemcpyAsync(ctx->d_lens_table, table, (size_t)lens->n_samples * 4u * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        if (rm_status lst = launch_lens(ctx, p, lens, ctx->d_lens_table, ctx->d_lens_frame, ctx->stream)) return lst;
-        RM_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (rm_status lst = timed_launch(ctx, &kernel_ms, [&]() { return launch_lens(ctx, p, lens, ctx->d_lens_table, ctx->d_lens_frame, ctx->stream); }))
+            return lst;
         const auto t0 = std::chrono::steady_clock::now();
         RM_HIP(ctx, hipMemcpy(host_rgb, ctx->d_lens_frame, need, hipMemcpyDeviceToHost));
         d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        float ms = 0.f;
-        RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        kernel_ms = ms;
     }
-    if (timing) {
-        timing->kernel_ms = kernel_ms;
-        timing->d2h_ms = d2h_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
+    fill_timing(timing, kernel_ms, d2h_ms, t_begin);
     return RM_OK;
 }
 

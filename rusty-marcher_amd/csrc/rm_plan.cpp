@@ -205,6 +205,24 @@ bool choose_kernel(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params 
     return k->fn != nullptr;
 }
 
+// The shading kernels' variant (rm_plan.hpp): the rules above for the hierarchy and the power, two stacks for the four -- and
+// no look at RM_FORCE_STACK, which choose_kernel alone obeys.
+rm_shading_variant rm_shading_variant_of(const rm_knobs &kn, const rm_dev_header &H, bool integer_exponents, uint32_t max_depth) {
+    rm_shading_variant v;
+    v.bvh = H.off_bvh_spheres != 0 || H.off_bvh_triangles != 0;
+    v.pow_mode = (integer_exponents && !kn.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
+    v.stack = max_depth <= 5u ? 4 : 32;
+    return v;
+}
+
+uint32_t rm_shading_grid(uint32_t total, uint32_t rays_per_pixel, int n_cus, int per_cu, uint32_t max_blocks) {
+    const uint32_t P = 64u / rays_per_pixel;
+    const uint64_t need = ((uint64_t)total + P - 1u) / P;
+    uint64_t g = std::min<uint64_t>(need, (uint64_t)std::max(1, n_cus) * (uint64_t)per_cu);
+    if (max_blocks > 0u) g = std::min<uint64_t>(g, max_blocks);
+    return (uint32_t)std::max<uint64_t>(g, 1u);
+}
+
 // ---------------------------------------------------------------------------
 // The launch
 // ---------------------------------------------------------------------------
@@ -674,5 +692,26 @@ extern "C" rm_status rmi_plan_exact_only(const rm_vec3 *camera, const rm_camera_
         return RM_ERR_INVALID_ARG;
     }
     *out = (P.exact_only ? 1u : 0u) | (P.args.exact_only ? 2u : 0u);
+    return RM_OK;
+}
+
+// Test hook, not part of the ABI (tests/test_launch_plan.py, tests/test_variant_matrix.py): the two decisions of a shading
+// launch, with the knobs as the environment has them now.  header (rmi_scene_image's: rm_dev_header's 19 integer fields in their
+// order) with the image's integer_exponents verdict and a depth cap -> variant[3] = bvh, pow_mode, stack; and, where `grid` is
+// given, *grid = rm_shading_grid of the five numbers.  Either half may be left out (header / grid NULL).  No device is needed.
+extern "C" rm_status rmi_shading_launch(const uint32_t *header, uint32_t integer_exponents, uint32_t max_depth, uint32_t *variant,
+                                        uint32_t total, uint32_t rays_per_pixel, int32_t n_cus, int32_t per_cu, uint32_t max_blocks,
+                                        uint32_t *grid) {
+    if (header) {
+        if (!variant) { rm_set_host_error("rmi_shading_launch: NULL variant"); return RM_ERR_INVALID_ARG; }
+        rm_dev_header H{};
+        std::memcpy(&H, header, 19u * sizeof(uint32_t));
+        const rm_shading_variant v = rm_shading_variant_of(rm_knobs_from_env(), H, integer_exponents != 0, max_depth);
+        variant[0] = v.bvh ? 1u : 0u; variant[1] = (uint32_t)v.pow_mode; variant[2] = (uint32_t)v.stack;
+    }
+    if (grid) {
+        if (rays_per_pixel < 1u || rays_per_pixel > 64u) { rm_set_host_error("rmi_shading_launch: rays_per_pixel is outside 1..64"); return RM_ERR_INVALID_ARG; }
+        *grid = rm_shading_grid(total, rays_per_pixel, n_cus, per_cu, max_blocks);
+    }
     return RM_OK;
 }

@@ -158,6 +158,24 @@ struct rm_kernel_choice {
 // false: no kernel for this scene / depth combination
 bool choose_kernel(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p, uint32_t tiles, rm_kernel_choice *k);
 
+// Which instantiation of radiance_steps<BVH, POW, STACK> (rm_radiance_step.inc) a launch of the shading kernels takes -- the
+// radiance queries, adaptive anti-aliasing, the thin-lens camera, progressive, soft and converging frames alike.  choose_kernel's
+// rules for the hierarchy and the power, with a reduced set of stacks: a lane parks at most max_depth - 1 rays, 4 serves a cap
+// of up to 5, 32 every other.  Unlike choose_kernel this rule does not look at RM_FORCE_STACK: these kernels are instantiated
+// for 4 and 32 only, and the knob's deeper stack is the render kernels' A/B switch.
+struct rm_shading_variant {
+    bool bvh;
+    int pow_mode;
+    int stack;
+};
+rm_shading_variant rm_shading_variant_of(const rm_knobs &kn, const rm_dev_header &H, bool integer_exponents, uint32_t max_depth);
+
+// Workgroups of a launch that shades `total` pixels with `rays_per_pixel` (1..64) rays each, 64 / rays_per_pixel pixels a
+// workgroup at a time: what the frame needs, at most what the device holds at once (max(1, n_cus) x per_cu, the kernel's
+// occupancy), at most `max_blocks` where that is not 0 (RM_REFINE_MAX_BLOCKS / RM_LENS_MAX_BLOCKS), at least 1.  The
+// workgroups loop over what is left.
+uint32_t rm_shading_grid(uint32_t total, uint32_t rays_per_pixel, int n_cus, int per_cu, uint32_t max_blocks);
+
 // The bookkeeping of the render launches on one stream (rm_tile_lists holds it next to the stream's buffers).  A plan is
 // made from it as it stands and carries what it is after the launch; the launcher stores that once the launch is out.
 struct rm_stream_state {

@@ -29,19 +29,11 @@
 using namespace rmdev;
 using namespace rmdev_strict;
 
+#include "rm_radiance_step.inc"   // global_scene_view: the scene in global memory, no LDS copy (the per-lane gathers of a query are few)
+
 namespace rmquery {
 
-__device__ __forceinline__ SceneView query_view(const double *__restrict__ blob, const rm_dev_header &H, uint32_t *bstack) {
-    SceneView sc;
-    sc.S = blob;                      // no LDS copy: the per-lane gathers of a query are few
-    sc.G = blob;
-    sc.cull_bounds = blob + H.off_bounds;
-    sc.cull_planar = blob + H.off_planar;
-    sc.bstack = bstack;
-    sc.cull_cos = 2.;                 // (never narrow: the kernels below are compiled without the cull anyway)
-    sc.H = H;
-    return sc;
-}
+using rmradiance::global_scene_view;
 
 // One rm_hit: the point and normal of surface_at (sphere.rs:58, polygon.rs:95, triangle.rs:80), the
 // pid mapped back to Scene.shapes.  Every field of a miss is 0.
@@ -63,7 +55,7 @@ __device__ __forceinline__ void store_hit(const Args &q, const SceneView &sc, rm
 template <bool BVH, bool OCCLUSION>
 __global__ __launch_bounds__(64) void rm_query_rays_kernel(const double *__restrict__ scene_blob, QueryArgs q) {
     __shared__ uint32_t bstack[64];
-    const SceneView sc = query_view(scene_blob, q.H, bstack);
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
     const size_t i = (size_t)blockIdx.x * 64u + (threadIdx.x & 63u);     // (64-bit: 60 M rays x 72 B is past 4 GB)
     const bool on = i < (size_t)q.n_rays;
     V3 o = mk(0., 0., 0.), d = mk(0., 0., -1.);                          // (a tail lane holds a harmless ray it never reports)
@@ -86,7 +78,7 @@ __global__ __launch_bounds__(64) void rm_query_rays_kernel(const double *__restr
 template <bool BVH, bool ORIENTED>
 __global__ __launch_bounds__(64) void rm_query_pixels_kernel(const double *__restrict__ scene_blob, QueryArgs q) {
     __shared__ uint32_t bstack[64];
-    const SceneView sc = query_view(scene_blob, q.H, bstack);
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t x, y;
     bool on;
@@ -342,7 +334,7 @@ __device__ __forceinline__ V3 normalized_norm(V3 a, double &norm) {
 template <bool BVH, int KIND>
 __global__ __launch_bounds__(64) void rm_ranged_kernel_t(const double *__restrict__ scene_blob, RangedArgs q) {
     __shared__ uint32_t bstack[64];
-    const SceneView sc = query_view(scene_blob, q.H, bstack);
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
     const size_t i = (size_t)blockIdx.x * 64u + (threadIdx.x & 63u);
     const bool on = i < (size_t)q.n;
     V3 o = mk(0., 0., 0.), d = mk(0., 0., -1.);

@@ -64,13 +64,7 @@ static rm_status query_rays(rm_ctx *ctx, bool occlusion, const void *origins, co
 
 // The host variants' staging buffer: rays in, answers out (grown as needed; only synchronous calls use it).
 static rm_status query_staging(rm_ctx *ctx, size_t bytes, char **out) {
-    if (ctx->query_bytes < bytes) {
-        if (ctx->d_query) RM_HIP(ctx, hipFree(ctx->d_query));
-        ctx->d_query = nullptr;
-        ctx->query_bytes = 0;
-        RM_HIP(ctx, hipMalloc(&ctx->d_query, bytes));
-        ctx->query_bytes = bytes;
-    }
+    if (rm_status gst = grow_device_buffer(ctx, &ctx->d_query, &ctx->query_bytes, bytes)) return gst;
     *out = static_cast<char *>(ctx->d_query);
     return RM_OK;
 }

@@ -38,14 +38,7 @@ namespace rmradiance {
 template <bool BVH, int POW, int STACK>
 __global__ __launch_bounds__(64) void rm_radiance_kernel_t(const double *__restrict__ scene_blob, RadianceArgs q) {
     __shared__ uint32_t bstack[64];
-    SceneView sc;
-    sc.S = scene_blob;                // no LDS copy: the rays of a wave gather from all over the scene anyway
-    sc.G = scene_blob;
-    sc.cull_bounds = scene_blob + q.H.off_bounds;
-    sc.cull_planar = scene_blob + q.H.off_planar;
-    sc.bstack = bstack;
-    sc.cull_cos = 2.;                 // (never narrow: compiled without the cull)
-    sc.H = q.H;
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
 
     const size_t i = (size_t)blockIdx.x * 64u + (threadIdx.x & 63u);     // (64-bit: 2^32 answers x 24 B)
     bool on = i < (size_t)q.n;
@@ -83,11 +76,6 @@ __global__ __launch_bounds__(64) void rm_radiance_kernel_t(const double *__restr
 using namespace rmradiance;
 
 const void *rm_radiance_kernel(bool bvh, int pow_mode, int stack) {
-#define RM_ROW(B, S)                                                                                         \
-    if (bvh == B && stack == S)                                                                              \
-        return pow_mode == POW_INTEGER ? (const void *)rm_radiance_kernel_t<B, POW_INTEGER, S>               \
-                                       : (const void *)rm_radiance_kernel_t<B, POW_GENERIC, S>;
-    RM_ROW(false, 4) RM_ROW(false, 32) RM_ROW(true, 4) RM_ROW(true, 32)
-#undef RM_ROW
+    RM_SHADING_TABLE(RM_SHADING_KERNEL, rm_radiance_kernel_t)
     return nullptr;
 }

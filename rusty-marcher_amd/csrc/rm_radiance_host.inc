@@ -1,33 +1,15 @@
 // rm_radiance_host.inc -- host side of the radiance queries (include/rusty_marcher_amd.h, "radiance queries"); included at
-// the end of rm_device.hip, behind rm_query_host.inc whose checks and staging buffer it shares.  The kernels are
-// rm_radiance.hip's.
+// the end of rm_device.hip, behind rm_query_host.inc whose checks and staging buffer it shares and rm_shade_host.inc whose
+// launch path.  The kernels are rm_radiance.hip's.
 //
 // Nothing here touches render state: the calls read the resident scene blob and -- the sample calls -- the context's camera
 // and basis.  The sample rays are formed in the kernel, so the backproject tables are neither read nor rebuilt.
 
+// One lane an answer (n > 0): the grid is the list's, no occupancy is asked
 static rm_status launch_radiance(rm_ctx *ctx, RadianceArgs &q, hipStream_t stream) {
-    q.H = ctx->image.H;
-    q.H.off_occ = 0u;                                                      // the occluder masks hold near the scene only: never here
-    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (as launch_query)
-    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;   // (as choose_kernel)
-    // a lane parks at most max_depth - 1 rays (rm_plan.cpp choose_kernel), from a reduced set of stacks
-    const void *fn = rm_radiance_kernel(bvh, pow_mode, q.max_depth <= 5u ? 4 : 32);
-    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "radiance: no such kernel");
-    const uint32_t blocks = (uint32_t)((q.n + 63u) / 64u);
-    void *args[] = {(void *)&ctx->d_scene, (void *)&q};
-    RM_HIP(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(64), args, 0, stream));
-    return RM_OK;
-}
-
-// max_depth and background of a call: what a host can get wrong without touching an element
-static rm_status check_shading(rm_ctx *ctx, const char *who, const rm_vec3 &bg, uint32_t max_depth) {
-    if (max_depth > RM_MAX_DEPTH) return ctx_fail(ctx, RM_ERR_DEPTH, std::string(who) + ": max_depth above RM_MAX_DEPTH");
-    if (!finite3(bg)) {
-        char buf[192];
-        std::snprintf(buf, sizeof buf, "%s: background (%g, %g, %g) is not finite", who, bg.x, bg.y, bg.z);
-        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
-    }
-    return RM_OK;
+    q.H = shading_header(ctx);
+    return launch_shading(ctx, shade_family{"radiance", rm_radiance_kernel}, q.max_depth, shade_extent{(uint32_t)((q.n + 63u) / 64u), 0u, 0u, 0u}, q,
+                          stream);
 }
 
 static rm_status check_samples(rm_ctx *ctx, const char *who, const rm_params *p, const double *xy, uint32_t n) {
@@ -90,13 +72,7 @@ static rm_status radiance_samples_impl(rm_ctx *ctx, const char *who, bool device
     q.n = n;
     q.mode = ctx->oriented ? RM_RADIANCE_SAMPLES_ORIENTED : RM_RADIANCE_SAMPLES;
     q.max_depth = p->max_depth;
-    q.bg_x = p->background.x; q.bg_y = p->background.y; q.bg_z = p->background.z;
-    q.width = p->width; q.height = p->height; q.half_fov = p->half_fov; q.ratio = p->ratio;
-    q.cam_x = ctx->camera.x; q.cam_y = ctx->camera.y; q.cam_z = ctx->camera.z;
-    const rm_camera_basis &cb = ctx->basis;                               // (read in the oriented mode only)
-    q.cam_rx = cb.right.x; q.cam_ry = cb.right.y; q.cam_rz = cb.right.z;
-    q.cam_ux = cb.up.x; q.cam_uy = cb.up.y; q.cam_uz = cb.up.z;
-    q.cam_fx = cb.forward.x; q.cam_fy = cb.forward.y; q.cam_fz = cb.forward.z;
+    fill_view(q, ctx, p, ctx->basis);                                      // (the basis: read in the oriented mode only)
     if (device) {
         RM_HIP(ctx, hipSetDevice(ctx->device));
         q.xy = static_cast<const double *>(xy);

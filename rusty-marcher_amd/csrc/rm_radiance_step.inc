@@ -10,8 +10,39 @@
 // The loop is wave-uniform: it ends when no lane holds a ray, every block is entered on a vote and predicated inside
 // (where<false> of rm_trace.inc), and a lane without a ray walks along with its `on` off -- see rm_radiance.hip, "Divergence".
 // How a lane comes by its ray is the including kernel's business; sample_direction below is the one way to form a sample's.
+//
+// Also here, once, what the including kernels share beside the step: their view of the scene (global_scene_view, rm_query.hip's
+// too), the display byte of a mean (to_byte) and the rule of the moved lights (OffsetLights).
 
 namespace rmradiance {
+
+// The scene as the kernels outside the render see it: read from global memory (no LDS copy: the rays of a wave gather from all
+// over the scene anyway), never narrow (they are compiled without the cull).  `bstack`: the workgroup's 64 words of LDS.
+__device__ __forceinline__ SceneView global_scene_view(const double *__restrict__ scene_blob, const rm_dev_header &H, uint32_t *bstack) {
+    SceneView sc;
+    sc.S = scene_blob;
+    sc.G = scene_blob;
+    sc.cull_bounds = scene_blob + H.off_bounds;
+    sc.cull_planar = scene_blob + H.off_planar;
+    sc.bstack = bstack;
+    sc.cull_cos = 2.;
+    sc.H = H;
+    return sc;
+}
+
+__device__ __forceinline__ uint8_t to_byte(double v) {                   // framebuffer.rs:80-82, the render epilogue's rule
+    return (uint8_t)(255. * __builtin_fmin(__builtin_fmax(v, 0.), 1.));
+}
+
+// Light i of a sample whose lights are moved: the scene's position plus the sample's row of an offset table, rounded once a
+// component (the area lights, rm_soft.hip; StoredLights of rm_trace.inc is the rule without).
+struct OffsetLights {
+    const double *row;                                                   // n_lights x 3 doubles
+    __device__ __forceinline__ V3 operator()(const double *lt, uint32_t i) const {
+        const double *o = row + 3u * i;
+        return mk(lt[0] + o[0], lt[1] + o[1], lt[2] + o[2]);
+    }
+};
 
 // The un-normalised direction of the sample (sx, sy): renderer.rs:128-135 at a real-valued position, the host's
 // backproject_tables operation for operation.  A: an argument block with the params' Renderer (width, height, half_fov,
@@ -97,3 +128,16 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
 }
 
 }  // namespace rmradiance
+
+// The instantiations every family of these kernels carries, written once: without and with a hierarchy, 4 or 32 parked rays a
+// lane (rm_plan.cpp rm_shading_variant_of never asks for another), each with both powers.  In a picker of (bool bvh, int
+// pow_mode, int stack), RM_SHADING_TABLE(RM_SHADING_KERNEL, K) returns the K<BVH, POW, STACK> that matches and falls through
+// where none does.  A family with a template argument more hands the table a macro of its own that forms a row's kernel from
+// RM_SHADING_KERNEL(K, B, S, the argument): the kernels of a row then stay together in the object, as they always have.
+#define RM_SHADING_KERNEL(K, B, S, ...)                                                                   \
+    (pow_mode == POW_INTEGER ? (const void *)K<B, POW_INTEGER, S, ##__VA_ARGS__> : (const void *)K<B, POW_GENERIC, S, ##__VA_ARGS__>)
+#define RM_SHADING_TABLE(ROW, K)                                                                          \
+    if (!bvh && stack == 4) return ROW(K, false, 4);                                                      \
+    if (!bvh && stack == 32) return ROW(K, false, 32);                                                    \
+    if (bvh && stack == 4) return ROW(K, true, 4);                                                        \
+    if (bvh && stack == 32) return ROW(K, true, 32);

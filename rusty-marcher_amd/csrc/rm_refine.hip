@@ -71,14 +71,7 @@ template <bool BVH, int POW, int STACK>
 __global__ __launch_bounds__(64) void rm_refine_shade_t(const double *__restrict__ scene_blob, RefineArgs q) {
     __shared__ uint32_t bstack[64];
     __shared__ double sums[64 * 3];
-    SceneView sc;
-    sc.S = scene_blob;                // (as rm_radiance_kernel_t: no LDS copy, never narrow)
-    sc.G = scene_blob;
-    sc.cull_bounds = scene_blob + q.H.off_bounds;
-    sc.cull_planar = scene_blob + q.H.off_planar;
-    sc.bstack = bstack;
-    sc.cull_cos = 2.;
-    sc.H = q.H;
+    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
 
     const uint32_t total = q.rows * q.frame_width;
     const uint32_t count = min(uniform_u32(q.ws[0]), total);             // clamped: a damaged workspace lists nothing outside the frame
@@ -125,11 +118,6 @@ using namespace rmrefine;
 const void *rm_refine_mark_kernel() { return (const void *)rm_refine_mark; }
 
 const void *rm_refine_shade_kernel(bool bvh, int pow_mode, int stack) {
-#define RM_ROW(B, S)                                                                                   \
-    if (bvh == B && stack == S)                                                                        \
-        return pow_mode == POW_INTEGER ? (const void *)rm_refine_shade_t<B, POW_INTEGER, S>            \
-                                       : (const void *)rm_refine_shade_t<B, POW_GENERIC, S>;
-    RM_ROW(false, 4) RM_ROW(false, 32) RM_ROW(true, 4) RM_ROW(true, 32)
-#undef RM_ROW
+    RM_SHADING_TABLE(RM_SHADING_KERNEL, rm_refine_shade_t)
     return nullptr;
 }

@@ -30,15 +30,6 @@ namespace rmsoft {
 
 using namespace rmaccum;
 
-// Light i of the lane's sample: the scene's position plus the lane's row of the offset table, rounded once a component.
-struct OffsetLights {
-    const double *row;                                                   // n_lights x 3 doubles
-    __device__ __forceinline__ V3 operator()(const double *lt, uint32_t i) const {
-        const double *o = row + 3u * i;
-        return mk(lt[0] + o[0], lt[1] + o[1], lt[2] + o[2]);
-    }
-};
-
 template <bool BVH, int POW, int STACK>
 __global__ __launch_bounds__(64) void rm_soft_shade_t(const double *__restrict__ scene_blob, SoftArgs a) {
     __shared__ uint32_t bstack[64];
@@ -53,11 +44,6 @@ __global__ __launch_bounds__(64) void rm_soft_shade_t(const double *__restrict__
 using namespace rmsoft;
 
 const void *rm_soft_kernel(bool bvh, int pow_mode, int stack) {
-#define RM_ROW(B, S)                                                                                   \
-    if (bvh == B && stack == S)                                                                        \
-        return pow_mode == POW_INTEGER ? (const void *)rm_soft_shade_t<B, POW_INTEGER, S>              \
-                                       : (const void *)rm_soft_shade_t<B, POW_GENERIC, S>;
-    RM_ROW(false, 4) RM_ROW(false, 32) RM_ROW(true, 4) RM_ROW(true, 32)
-#undef RM_ROW
+    RM_SHADING_TABLE(RM_SHADING_KERNEL, rm_soft_shade_t)
     return nullptr;
 }

@@ -42,16 +42,7 @@ static rm_status launch_soft(rm_ctx *ctx, const rm_params *p, const rm_lens *len
     a.A.mean = static_cast<double *>(mean);
     a.A.rgb8 = static_cast<uint8_t *>(rgb8);
     a.offsets = static_cast<const double *>(offsets);
-
-    const bool bvh = ctx->image.H.off_bvh_spheres != 0 || ctx->image.H.off_bvh_triangles != 0;   // (launch_accum's rules)
-    const int pow_mode = (ctx->image.integer_exponents && !ctx->knobs.force_generic_pow) ? POW_INTEGER : POW_GENERIC;
-    const void *fn = rm_soft_kernel(bvh, pow_mode, a.A.L.max_depth <= 5u ? 4 : 32);
-    if (!fn) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "area lights: no such kernel");
-    uint32_t grid = 0;
-    if (rm_status gst = lens_grid(ctx, fn, a.A.L.rows * a.A.L.frame_width, a.A.L.n_samples, &grid)) return gst;
-    void *args[] = {(void *)&ctx->d_scene, (void *)&a};
-    RM_HIP(ctx, hipLaunchKernel(fn, dim3(grid), dim3(64), args, 0, stream));
-    return RM_OK;
+    return launch_shading(ctx, shade_family{"area lights", rm_soft_kernel}, a.A.L.max_depth, lens_extent(ctx, a.A.L), a, stream);
 }
 
 static rm_status rm_accumulate_soft_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table,

@@ -1,7 +1,9 @@
 // AddressSanitizer / UBSan exercise of the host half of the C ABI (csrc/rm_scene.cpp):
 // scene builder, OBJ ingest (good and malformed files), status formatting, the hierarchy
 // builder (csrc/rm_bvh.hpp) and the device image the upload builds from a description, good
-// and bad ones (csrc/rm_image.cpp).  CPU only.
+// and bad ones (csrc/rm_image.cpp); and the two decisions of a shading launch (csrc/rm_plan.cpp rm_shading_variant_of,
+// rm_shading_grid) over the cases of tests/test_launch_plan.py.  CPU only.
+#include <algorithm>
 #include <cassert>
 #include <cstdio>
 #include <cstring>
@@ -12,10 +14,16 @@
 #include "rm_internal.h"
 #include "rm_bvh.hpp"
 #include "rm_image.hpp"
+#include "rm_plan.hpp"
 
 // the device half (rm_device.hip) is not part of this CPU-only build: its one symbol the
 // host half's callers need is the error accessor
 extern "C" const char *rm_last_error(const rm_ctx *) { return rm_get_host_error(); }
+// ... and the kernel tables the render launch's plan hands out (rm_plan.cpp links against them; no plan is made here)
+const void *rm_pick_kernel(bool, bool, bool, bool, bool, int, bool, int, int) { return nullptr; }
+const void *rm_pick_kernel_oriented(bool, bool, bool, bool, bool, int, int) { return nullptr; }
+const void *rmdev::rm_classify_kernel(bool) { return nullptr; }
+const void *rmdev::rm_classify_kernel_oriented(bool) { return nullptr; }
 
 // rm_build_bvh invariants the kernel's walk relies on: `order` is a permutation; every leaf
 // holds 1..leaf_size consecutive primitives and every primitive sits in exactly one leaf;
@@ -131,6 +139,39 @@ static void check_refusals(const rm_scene_desc &good) {
     d.lights = nullptr; refused(d, "rm_scene_upload: NULL array with non-zero count");
 }
 
+// The shading launches' variant and grid: every outcome of the rule, the grid against the formula in 64-bit integers
+static void check_shading_plan() {
+    rm_knobs plain, generic, deep;
+    generic.force_generic_pow = true;
+    deep.force_stack = 32;
+    for (uint32_t spheres : {0u, 512u})
+        for (uint32_t triangles : {0u, 768u})
+            for (bool integer : {false, true})
+                for (uint32_t depth : {0u, 5u, 6u, (uint32_t)RM_MAX_DEPTH}) {
+                    rm_dev_header H{};
+                    H.off_bvh_spheres = spheres;
+                    H.off_bvh_triangles = triangles;
+                    const rm_shading_variant v = rm_shading_variant_of(plain, H, integer, depth);
+                    assert(v.bvh == (spheres != 0u || triangles != 0u));
+                    assert(v.pow_mode == (integer ? rmdev::POW_INTEGER : rmdev::POW_GENERIC));
+                    assert(v.stack == (depth <= 5u ? 4 : 32));
+                    const rm_shading_variant g = rm_shading_variant_of(generic, H, integer, depth), d = rm_shading_variant_of(deep, H, integer, depth);
+                    assert(g.bvh == v.bvh && g.pow_mode == rmdev::POW_GENERIC && g.stack == v.stack);
+                    assert(d.bvh == v.bvh && d.pow_mode == v.pow_mode && d.stack == v.stack);   // RM_FORCE_STACK changes nothing
+                }
+    for (uint32_t rays : {1u, 4u, 9u, 49u, 64u})
+        for (uint32_t total : {1u, 63u, 64u, 65u, 0x7fffffffu})
+            for (uint32_t cap : {0u, 1u, 3u})
+                for (int n_cus : {0, 1, 256})
+                    for (int per_cu : {1, 8}) {
+                        const uint64_t group = 64u / rays;
+                        uint64_t g = std::min<uint64_t>((total + group - 1u) / group, (uint64_t)std::max(1, n_cus) * (uint64_t)per_cu);
+                        if (cap) g = std::min<uint64_t>(g, cap);
+                        assert(rm_shading_grid(total, rays, n_cus, per_cu, cap) == std::max<uint64_t>(g, 1u));
+                    }
+    assert(rm_shading_grid(0x7fffffffu, 64u, 1 << 20, 1 << 11, 0u) == 0x7fffffffu);
+}
+
 int main(int argc, char **argv) {
     assert(argc >= 3);
     const std::string cornell = argv[1], tmpdir = argv[2];
@@ -218,6 +259,7 @@ int main(int argc, char **argv) {
     check_hierarchy(257, 4);
     check_hierarchy(1000, 2);
     check_hierarchy(64, 1);
+    check_shading_plan();
     char buf[8];
     assert(rm_format_status(buf, sizeof buf, 92, 1280, 800) > 7);   // truncated, NUL-terminated
     assert(buf[7] == '\0');

@@ -4,7 +4,10 @@ ordered by, when the tags wrap and what is cleared then, how the sky tail follow
 benchmark's configurations.  The planner touches no device: rmi_plan_launches (an internal export, not part of the ABI) plans
 a sequence of launches on one imaginary stream and commits each plan's "state after" itself.  Expected values are the rules
 the planner's comments state, worked out here by hand; the shapes of C2 / C3 / C5 were read off the launches of the commit
-before the planner existed, on a device of 256 compute units."""
+before the planner existed, on a device of 256 compute units.
+
+Behind them the two decisions of a shading launch (rmi_shading_launch): which instantiation of the shading kernels a scene and a
+depth cap take, and how many workgroups a frame gets."""
 import ctypes as C
 
 import pytest
@@ -259,3 +262,89 @@ def test_benchmark_launch_shapes(pkg, config, scene, kernel, grid, lds):
     r = plan(pkg, [launch(scene=scene, w=cfg["width"], h=cfg["height"], depth=cfg["max_depth"])])[0]
     assert (r.fast, r.stack, r.pow_mode, r.waves, r.per_wave, r.staged, r.bvh, r.cull, r.edges, r.order, r.feedback) == kernel
     assert (r.grid, r.block, r.lds_bytes) == (grid, 64, lds)
+
+
+# ---------------------------------------------------------------- the shading launches (rm_plan.cpp rm_shading_variant_of, rm_shading_grid)
+POW_GENERIC, POW_INTEGER = 0, 1
+RM_MAX_DEPTH = 32
+HEADER_WORDS = 19                                  # rm_dev_header's integer fields (tests/test_scene_image.py HEADER_FIELDS)
+OFF_BVH_SPHERES, OFF_BVH_TRIANGLES = 13, 14
+
+
+def shading_hook(pkg):
+    return pkg.lib().rmi_shading_launch            # (an internal export like rmi_plan_launches; its prototype is _lib.py's)
+
+
+def shading_variant(pkg, header, integer_exponents, max_depth):
+    """-> (bvh, pow_mode, stack) of a shading launch: header = rm_dev_header's 19 integer fields in their order."""
+    assert len(header) == HEADER_WORDS
+    out = (C.c_uint32 * 3)()
+    assert shading_hook(pkg)((C.c_uint32 * HEADER_WORDS)(*header), int(integer_exponents), max_depth, out, 0, 0, 0, 0, 0, None) == 0
+    return bool(out[0]), int(out[1]), int(out[2])
+
+
+def shading_grid(pkg, total, rays_per_pixel, n_cus, per_cu, max_blocks):
+    out = C.c_uint32(0xFFFFFFFF)
+    assert shading_hook(pkg)(None, 0, 0, None, total, rays_per_pixel, n_cus, per_cu, max_blocks, C.byref(out)) == 0
+    return out.value
+
+
+def header_with(spheres=0, triangles=0):
+    h = [0] * HEADER_WORDS
+    h[OFF_BVH_SPHERES], h[OFF_BVH_TRIANGLES] = spheres, triangles
+    return h
+
+
+def test_shading_variant_outcomes(pkg, monkeypatch):
+    for k in ("RM_FORCE_GENERIC_POW", "RM_FORCE_STACK"):
+        monkeypatch.delenv(k, raising=False)
+    # the eight (bvh, pow, stack) outcomes, both sides of the depth rule at 5 and 6
+    for spheres in (0, 1024):
+        for integer in (False, True):
+            for depth in (5, 6):
+                assert shading_variant(pkg, header_with(spheres), integer, depth) == \
+                    (spheres != 0, POW_INTEGER if integer else POW_GENERIC, 4 if depth <= 5 else 32)
+    # ... and its ends
+    assert shading_variant(pkg, header_with(), True, 0) == (False, POW_INTEGER, 4)
+    assert shading_variant(pkg, header_with(), True, RM_MAX_DEPTH) == (False, POW_INTEGER, 32)
+    # each hierarchy alone and both together
+    assert [shading_variant(pkg, header_with(s, t), True, 5)[0] for s, t in ((0, 0), (512, 0), (0, 768), (512, 768))] == [False, True, True, True]
+    # no other field of the header is looked at
+    others = [7 if i not in (OFF_BVH_SPHERES, OFF_BVH_TRIANGLES) else 0 for i in range(HEADER_WORDS)]
+    assert shading_variant(pkg, others, True, 5) == (False, POW_INTEGER, 4)
+
+
+def test_shading_variant_knobs(pkg, monkeypatch):
+    monkeypatch.delenv("RM_FORCE_STACK", raising=False)
+    for forced, expect in (("1", POW_GENERIC), ("0", POW_INTEGER)):
+        monkeypatch.setenv("RM_FORCE_GENERIC_POW", forced)
+        assert shading_variant(pkg, header_with(), True, 5)[1] == expect
+        assert shading_variant(pkg, header_with(), False, 5)[1] == POW_GENERIC
+    monkeypatch.delenv("RM_FORCE_GENERIC_POW")
+    # RM_FORCE_STACK is the render kernels' alone: the shading kernels come with 4 and 32 parked rays only
+    before = [shading_variant(pkg, header_with(s), i, d) for s in (0, 64) for i in (False, True) for d in (0, 5, 6, RM_MAX_DEPTH)]
+    monkeypatch.setenv("RM_FORCE_STACK", "32")
+    assert [shading_variant(pkg, header_with(s), i, d) for s in (0, 64) for i in (False, True) for d in (0, 5, 6, RM_MAX_DEPTH)] == before
+    assert shading_variant(pkg, header_with(), True, 5)[2] == 4
+
+
+def test_shading_grid(pkg):
+    """min(ceil(total / (64 / rays_per_pixel)), max(1, n_cus) * per_cu), then the cap where it is not 0, then at least 1 -- worked
+    out here, in Python's integers."""
+    for rays in (1, 4, 9, 49, 64):
+        for total in (1, 63, 64, 65, 2 ** 31 - 1):
+            for cap in (0, 1, 3):
+                for n_cus, per_cu in ((256, 8), (256, 1), (0, 5), (1, 1), (304, 3)):
+                    pixels_a_group = 64 // rays
+                    g = min(-(-total // pixels_a_group), max(1, n_cus) * per_cu)
+                    if cap:
+                        g = min(g, cap)
+                    g = max(g, 1)
+                    assert shading_grid(pkg, total, rays, n_cus, per_cu, cap) == g, (total, rays, n_cus, per_cu, cap)
+    # a frame smaller than the device, a device smaller than the frame, and the largest frame one ray a pixel
+    assert shading_grid(pkg, 32 * 32, 4, 256, 8, 0) == 64
+    assert shading_grid(pkg, 1920 * 1056, 8, 256, 8, 0) == 2048
+    assert shading_grid(pkg, 2 ** 31 - 1, 64, 2 ** 20, 2 ** 11, 0) == 2 ** 31 - 1
+    # what the hook refuses: a group of no pixels
+    assert shading_hook(pkg)(None, 0, 0, None, 64, 0, 256, 8, 0, C.byref(C.c_uint32())) == 1
+    assert shading_hook(pkg)(None, 0, 0, None, 64, 65, 256, 8, 0, C.byref(C.c_uint32())) == 1

@@ -2,7 +2,8 @@
 tests/test_gpu_structured_rays.py, by the host-only scene image and the oracle alone:
 
 1. every cell's scene image carries the hierarchies and the integer_exponents verdict the cell claims, and its depth lies on
-   the side of the stack rule it claims: a recipe that drifts into another kernel fails here;
+   the side of the stack rule it claims -- by the rule as written here and by the library's own (rmi_shading_launch, asked
+   with the image's header, verdict and the depth): a recipe that drifts into another kernel fails here;
 2. the oracle tells the variants apart: with 12.5 replaced by 12, and one level less deep, more than 1e-6 changes in some
    channel on at least 5 % of the rays and of the pixels (the shares are printed);
 3. some ray of the list holds exactly max_depth - 1 live siblings at once (cast_ray's tree replayed for 64 rays);
@@ -20,6 +21,7 @@ import converge_reference as CR
 import radiance_reference as RR
 import ranged_reference
 import test_gpu_query as GQ
+import test_launch_plan as LP
 import test_scene_image as SI
 import variant_matrix as VM
 
@@ -55,6 +57,9 @@ def test_a_cell_takes_the_kernel_it_claims(pkg, matrix, cell):
     assert (img["H"]["off_bvh_spheres"] != 0) == spheres and (img["H"]["off_bvh_triangles"] != 0) == triangles, img["H"]
     assert bool(img["verdicts"][1]) == integer
     assert (depth <= 5) == shallow and depth in (5, 6)                 # the two sides of `max_depth <= 5u ? 4 : 32`
+    # ... and the library says so itself: the variant its launchers take for this header, verdict and depth
+    header = [img["H"][name] for name in SI.HEADER_FIELDS]
+    assert LP.shading_variant(pkg, header, bool(img["verdicts"][1]), depth) == (spheres or triangles, 1 if integer else 0, 4 if shallow else 32)
     assert img["H"]["n_lights"] == len(VM.LIGHTS) == len(VM.RADII)
     # the exponents the integer cells keep at the ends of the binary powering
     exponents = {m["specular_exponent"] for m in VM.materials(generic).values()}
