@@ -190,8 +190,13 @@ def test_depth_caps(pkg, O, ctx, depth):
 
 def test_deep_recursion_needs_the_stack(pkg, O, ctx):
     """A stack of 13 glass panes in front of a glass sphere: every pane adds a level
-    (refraction) and, at oblique incidence, a sibling (reflection), so the ray trees
-    really reach the caps being tested and the per-lane stack is exercised."""
+    (refraction), so the ray trees really reach the caps being tested.  It does not fill
+    the per-lane stack: the panes are nearly square to the view and have ri 1.5, and a
+    glass hit has both children only beyond asin(1 / ri) off the normal.  cast_ray's tree
+    replayed on the CPU under every pixel of the 256x224 frame (variant_matrix.parked_at_once)
+    holds at most 1 live sibling at once at depths 5 and 10 (21,011 of the 57,344 pixels; the
+    others none) and at most 2 at depths 16 and 32 (8,790 pixels).  The stacks are filled to
+    the brim, in every instantiation of the render kernels, by tests/test_gpu_render_matrix.py."""
     glass = dict(diffusion=0.3, diffuse_color=(0.9, 0.8, 0.7), specular=0.9, specular_exponent=20.,
                  is_glass_like=True, reflection=0.4, refractive_index=1.5)
     panes = []

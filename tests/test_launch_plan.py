@@ -51,8 +51,9 @@ def launch(scene=DEMO, cam=(0., 0., 0.), w=640, h=352, depth=5, band=None, basis
     return dict(scene=scene, cam=cam, w=w, h=h, depth=depth, band=band, basis=basis, epoch=epoch, hint=hint)
 
 
-def plan(pkg, launches, n_cus=256):
-    """-> one Row per launch of the sequence, planned on one stream with the knobs of the environment as it is now."""
+def plan(pkg, launches, n_cus=256, integer_exponents=1):
+    """-> one Row per launch of the sequence, planned on one stream with the knobs of the environment as it is now.
+    integer_exponents: the scene image's verdict (0: the launches take POW_GENERIC); a launch may carry rm_params' "flags"."""
     L = pkg.lib()
 
     class Case(C.Structure):
@@ -64,9 +65,10 @@ def plan(pkg, launches, n_cus=256):
     for c, l in zip(cases, launches):
         for k, v in l["scene"].items():
             setattr(c, k, v)
-        c.integer_exponents, c.n_cus, c.scene_epoch, c.hint = 1, n_cus, l["epoch"], l["hint"]
+        c.integer_exponents, c.n_cus, c.scene_epoch, c.hint = integer_exponents, n_cus, l["epoch"], l["hint"]
         c.oriented = 0 if l["basis"] is None else 1
         c.params = pkg.backend.make_params(workloads.FOV, float(l["h"]), float(l["w"]), l["depth"], l["band"])
+        c.params.flags = l.get("flags", c.params.flags)
         c.camera = pkg._lib.vec3(l["cam"])
         c.basis = pkg._lib.camera_basis(FIXED if l["basis"] is None else l["basis"])
     rows = (Row * len(launches))()
