@@ -955,6 +955,74 @@ rm_status rm_render_progressive_soft(rm_ctx *ctx, const rm_params *params, const
                                      uint8_t *host_rgb8 /* optional */, uint32_t *n_total /* optional */,
                                      rm_timing *timing /* optional */);
 
+/* ---- moving spheres: motion blur in progressive frames ----------------------------------------
+ * A scene whose spheres move renders as one frozen instant, however many samples a frame holds.
+ * These calls give each sample of a progressive frame sphere positions of its own -- a sphere of
+ * velocity v is seen where it stands at the sample's own time within the shutter -- and the mean
+ * converges to a picture blurred along the motion.  Additive to ABI version 5; a host detects them
+ * by " motion" in rm_build_info().
+ *
+ * Spheres only.  The reference has no offset for spheres, so one addition per component defines a
+ * moved sphere; polygon and triangle records are projected at upload, and moving them would not
+ * reproduce the reference's hit / miss decisions bit for bit.
+ *
+ * A shape offset table is [n_samples][n_shapes][3] doubles in world units, indexed by the shape's
+ * index in the scene's shape list: the index rm_scene_offset_shape takes and rm_hit.shape reports.
+ * For sample row s and a shape k that is a sphere the centre is C'.c = C.c + off[s][k].c per
+ * component, C the resident scene's: one addition, rounded once.  C' takes C's place in everything
+ * the sample does with that sphere, at every ray step: the closest-hit test, every shadow test and
+ * the normal normalized(point - C'), for the primary hit and for the reflected and refracted
+ * children.  radius_square and the material are the scene's.  Rows of shapes that are not spheres
+ * are never read.  Everything else is the area lights' frame word for word: steps 1-5 of the
+ * thin-lens camera, the light offset table, and the sum, mean and bytes of the progressive frames.
+ * With every shape offset +0. or -0. a frame is byte for byte what rm_accumulate_soft_device writes
+ * for the same tables, for centre coordinates that are not -0. (-0. + +0. is +0.).
+ *
+ * Cost: the kernels of these calls test every primitive against every ray (the flat walk, what
+ * RM_DISABLE_BVH=1 selects elsewhere), whatever hierarchies the scene image holds: a hierarchy's
+ * boxes hold for the uploaded centres only.  A scene of hundreds of spheres or a mesh pays for it.
+ *
+ * rm_motion_sequence fills rows first .. first + count - 1 of one fixed offset sequence,
+ * count * n_shapes * 3 doubles.  Host arithmetic only (no context, no GPU, no libm), every
+ * operation rounded once.  With phi_b as in rm_lens_sequence -- bases 2, 3, 5, 7, 11 and 13 are the
+ * lens' and the lights' -- for index s: t = shutter * phi_17(s), and off[s][k].c =
+ * velocities[k].c * t.  Row 0 is the scene as uploaded, at shutter open.  first + count >
+ * RM_PROGRESSIVE_MAX_SAMPLES, a velocity component or a shutter that is not finite, shutter < 0,
+ * and a NULL velocities or offsets with something to write are RM_ERR_INVALID_ARG, nothing is
+ * written; count == 0 or n_shapes == 0 is RM_OK, nothing is written.
+ *
+ * rm_accumulate_motion_device is rm_accumulate_soft_device with one more pair of arguments:
+ * asynchronous on hip_stream, neither reading nor writing render state, the same checks, and:
+ * n_shapes must be the resident scene's shape count; device_shape_offsets must not be NULL when the
+ * scene holds a sphere.  Both tables are required where their count is not zero -- a caller with
+ * point lights passes zeros -- and lens->n_samples rows of each are read.  Their contents are a
+ * precondition: a non-finite offset gives unspecified pixels, never a fault.
+ *
+ * rm_render_progressive_motion is the viewer's tick: rm_render_progressive_soft on the same
+ * context-owned sum, mean and bytes and the same count N, with the key extended by n_shapes, the
+ * bytes of velocities and of shutter.  radii == NULL is "no radii" (point lights, n_lights is not
+ * looked at) and stages zeros.  So the frame begins again when a velocity or the shutter changes,
+ * when a caller switches between the three calls, and on everything that begins it again in
+ * rm_render_progressive_soft; it continues otherwise.  The call stages rows [N, N + n_samples) of
+ * rm_lens_sequence, rm_light_sequence and rm_motion_sequence (buffers the context owns).  Checked
+ * before anything else happens: rm_render_progressive_soft's checks (the radii only where given),
+ * n_shapes the resident scene's, velocities and shutter as rm_motion_sequence demands, and a
+ * velocity that is not zero for a shape that is not a sphere -- RM_ERR_INVALID_ARG, the shape named
+ * in rm_last_error; a refused call changes neither N nor the key.  Saturation, rows == 0, timing
+ * and the counters are rm_render_progressive's.
+ */
+rm_status rm_motion_sequence(uint32_t first, uint32_t count, const rm_vec3 *velocities, uint32_t n_shapes, double shutter,
+                             double *offsets);
+rm_status rm_accumulate_motion_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                      const void *device_light_offsets, uint32_t n_lights, const void *device_shape_offsets,
+                                      uint32_t n_shapes, uint32_t n_before, void *device_sum, void *device_mean /* optional */,
+                                      void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_render_progressive_motion(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                       const double *radii /* NULL: point lights */, uint32_t n_lights,
+                                       const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart,
+                                       double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                       uint32_t *n_total /* optional */, rm_timing *timing /* optional */);
+
 /* ---- converging frames: progressive frames that sample only the pixels still noisy ------------
  * A pass of a progressive frame casts n_samples rays for every pixel, however long most of them
  * have stopped changing.  These calls keep a sample count and an error estimate per pixel, list the

@@ -112,6 +112,50 @@ def _radii(radii, n_lights=None):
     return r
 
 
+def _velocities(velocities, n_shapes=None):
+    """The velocities of a scene's shapes as a C-contiguous float64 array (n_shapes, 3): one finite vector a shape, None for a
+    shape that stands still (n_shapes of them where that is known)."""
+    if isinstance(velocities, (str, bytes)) or not hasattr(velocities, "__len__"):
+        raise ValueError("velocities must be a sequence of vectors, one a shape, got %r" % (velocities,))
+    v = np.zeros((len(velocities), 3), dtype=np.float64)
+    for k, e in enumerate(velocities):
+        if e is None:
+            continue
+        try:
+            v[k] = (e.x, e.y, e.z) if hasattr(e, "x") else tuple(float(c) for c in e)
+        except (TypeError, ValueError):
+            raise ValueError("velocities[%d] must be a vector of three numbers or None, got %r" % (k, e))
+    if not np.isfinite(v).all():
+        raise ValueError("every velocity must be finite, got %r" % (v.tolist(),))
+    if n_shapes is not None and v.shape[0] != n_shapes:
+        raise ValueError("one velocity a shape: the scene has %d shapes, got %d velocities" % (n_shapes, v.shape[0]))
+    return v
+
+
+def _shutter(shutter):
+    """The time the shutter stands open: a finite number >= 0."""
+    if isinstance(shutter, bool) or not isinstance(shutter, (int, float, np.floating, np.integer)) or not np.isfinite(shutter) or shutter < 0.:
+        raise ValueError("shutter must be a finite number >= 0, got %r" % (shutter,))
+    return float(shutter)
+
+
+def _offset_tensor(offsets, name, what, n_samples, device):
+    """A light or shape offset table as a contiguous float64 tensor (n_samples, n, 3) on `device`: a tensor is checked, an array is
+    checked (finite) and copied over."""
+    torch = _torch()
+    if isinstance(offsets, torch.Tensor):
+        if offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != n_samples or offsets.shape[2] != 3 \
+                or not offsets.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 torch tensor of shape (%d, %s, 3)" % (name, n_samples, what))
+        if offsets.device != device:
+            raise ValueError("%s must live on %s, not %s" % (name, device, offsets.device))
+        return offsets
+    off = np.ascontiguousarray(offsets, dtype=np.float64)
+    if off.ndim != 3 or off.shape[0] != n_samples or off.shape[2] != 3 or not np.isfinite(off).all():
+        raise ValueError("%s must be a finite float64 array of shape (%d, %s, 3), got %s" % (name, n_samples, what, off.shape))
+    return torch.from_numpy(off).to(device)
+
+
 def _converge(tolerance, min_samples, max_samples, n_samples, table_rows=PROGRESSIVE_MAX_SAMPLES):
     """rm_converge of a converging frame: tolerance any number but NaN, min_samples an integer >= 0, max_samples an integer in
     n_samples..min(table_rows, RM_PROGRESSIVE_MAX_SAMPLES)."""
@@ -674,6 +718,66 @@ class Context:
                                                      host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
                                                      host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
                                                      C.byref(total), C.byref(timing)), self.ptr)
+        return timing, total.value
+
+    # ---- moving spheres (include/rusty_marcher_amd.h, "moving spheres") ----
+    def motion_sequence(self, first, count, velocities, shutter):
+        """rm_motion_sequence: rows first .. first + count - 1 of the library's shape offset sequence for shapes of the velocities
+        `velocities` and a shutter open for `shutter`, (count, len(velocities), 3) float64: row s moves shape k by velocities[k]
+        times the row's time within the shutter.  Host arithmetic: needs neither a context nor a GPU."""
+        for name, v in (("first", first), ("count", count)):
+            if isinstance(v, bool) or int(v) != v or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        if first + count > PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+        v, shutter = _velocities(velocities), _shutter(shutter)
+        off = np.zeros((int(count), v.shape[0], 3), dtype=np.float64)
+        _lib.check(self.L.rm_motion_sequence(int(first), int(count), v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter,
+                                             off.ctypes.data_as(C.POINTER(C.c_double))), None)
+        return off
+
+    def accumulate_motion_device(self, params, sum, aperture, focus, table, light_offsets, shape_offsets, n_before, mean=None, rgb8=None,
+                                 stream=None):
+        """rm_accumulate_motion_device: accumulate_soft_device with a shape offset table as well -- sample row s sees the sphere
+        that is shape k of the scene at its centre + shape_offsets[s][k], in every hit test, shadow test and normal.
+        light_offsets: (n_samples, n_lights, 3), zeros for point lights; shape_offsets: (n_samples, n_shapes, 3), rows of shapes
+        that are not spheres are not read.  Each a contiguous float64 tensor on the context's device, or an array, which is
+        checked (finite) and copied over; n_lights and n_shapes must be the uploaded scene's.
+        -> (the table's tensor, the light offsets' tensor, the shape offsets' tensor)."""
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", lens.n_samples, sum.device)
+        shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", lens.n_samples, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), int(shape_offsets.shape[1])
+        _lib.check(self.L.rm_accumulate_motion_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                      C.c_void_p(light_offsets.data_ptr()) if n_lights > 0 else None, n_lights,
+                                                      C.c_void_p(shape_offsets.data_ptr()) if n_shapes > 0 else None, n_shapes, int(n_before),
+                                                      C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                      C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                      C.c_void_p(self._stream(stream))), self.ptr)
+        return table, light_offsets, shape_offsets
+
+    def render_progressive_motion(self, params, velocities, shutter, aperture, focus, n_samples, radii=None, restart=False, host_rgb=None,
+                                  host_rgb8=None):
+        """rm_render_progressive_motion: render_progressive_soft with moving spheres -- the sphere that is shape k of the uploaded
+        scene moves by velocities[k] while the shutter stands open, and every sample sees it at a time of its own.  velocities:
+        one vector (or None) for every shape, zero for what is not a sphere; radii: one radius a light, None for point lights.
+        The frame begins again when a velocity or the shutter changes or the caller switches between this call and the other two
+        ticks, and on everything that begins it again there.  -> (rm_timing, samples a pixel in the frame now)."""
+        lens = _lens(aperture, focus, n_samples)
+        v, shutter = _velocities(velocities), _shutter(shutter)
+        r = _radii(radii) if radii is not None else None
+        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
+        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
+                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        timing, total = _lib.rm_timing(), C.c_uint32(0)
+        _lib.check(self.L.rm_render_progressive_motion(self.ptr, C.byref(params), C.byref(lens),
+                                                       r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                       r.shape[0] if r is not None else 0,
+                                                       v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, 1 if restart else 0,
+                                                       host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
+                                                       host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
+                                                       C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
     # ---- converging frames (include/rusty_marcher_amd.h, "converging frames") ----

@@ -1,16 +1,21 @@
-// rm_accum_body.inc -- the body the kernels of the progressive frames share: rm_accum.hip's (lights where the scene image says)
-// and rm_soft.hip's (lights moved by the lane's row of an offset table).  Included behind rm_radiance_step.inc.
+// rm_accum_body.inc -- the body the kernels of the progressive frames share: rm_accum.hip's (lights where the scene image says),
+// rm_soft.hip's (lights moved by the lane's row of an offset table) and rm_motion.hip's (spheres moved as well).  Included
+// behind rm_radiance_step.inc.
 //
 // `lights_of(s)`: the rule that says where the lights of table row s stand (rm_trace.inc, StoredLights), asked once a lane
-// before the loop over the groups.  `bstack` (64 words) and `sums` (64 x 3 doubles) are the workgroup's LDS.
+// before the loop over the groups; `spheres_of(s)`: the same for the spheres (StoredSpheres where none is given).  `bstack` (64 words) and `sums` (64 x 3 doubles) are the workgroup's LDS.
 
 namespace rmaccum {
 
 using namespace rmradiance;
 
-template <bool BVH, int POW, int STACK, class LIGHTS_OF>
+struct stored_spheres_of {
+    __device__ __forceinline__ StoredSpheres operator()(uint32_t) const { return StoredSpheres(); }
+};
+
+template <bool BVH, int POW, int STACK, class LIGHTS_OF, class SPHERES_OF = stored_spheres_of>
 __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blob, const AccumArgs &a, uint32_t *bstack, double *sums,
-                                            LIGHTS_OF lights_of) {
+                                            LIGHTS_OF lights_of, SPHERES_OF spheres_of = SPHERES_OF()) {
     const LensArgs &q = a.L;
     const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
 
@@ -22,6 +27,7 @@ __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blo
     const double dx = row[0], dy = row[1];
     const double au = q.aperture * row[2], av = q.aperture * row[3];
     const auto lights = lights_of(s);
+    const auto spheres = spheres_of(s);
     const V3 bg = mk(q.bg_x, q.bg_y, q.bg_z);
     const V3 cam = mk(q.cam_x, q.cam_y, q.cam_z);
     const V3 lens = mk(q.cam_x + ((au * q.cam_rx) + (av * q.cam_ux)), q.cam_y + ((au * q.cam_ry) + (av * q.cam_uy)),
@@ -47,7 +53,7 @@ __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blo
                 dir = normalized(F - lens);
             }
         }
-        const V3 acc = q.max_depth == 0u ? bg : radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights);
+        const V3 acc = q.max_depth == 0u ? bg : radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights, spheres);
         sums[lane * 3u] = acc.x; sums[lane * 3u + 1u] = acc.y; sums[lane * 3u + 2u] = acc.z;
         __syncthreads();
         if (on & (s == 0u)) {

@@ -77,10 +77,20 @@ struct rm_progressive_key {
     rm_vec3 camera;
     rm_camera_basis basis;
     uint64_t copies;
-    uint32_t soft, n_lights;                 // rm_render_progressive_soft's frames: 1 and the radii's count (their bytes: rm_progressive::radii); else 0, 0
+    uint32_t soft, n_lights;                 // frames with radii: 1 and the radii's count (their bytes: rm_progressive::radii); else 0, 0
+    uint32_t motion, n_shapes;               // rm_render_progressive_motion's frames: 1 and the velocities' count (their bytes:
+    double shutter;                          // rm_progressive::velocities) and the shutter; else 0, 0, 0
 };
 
-static rm_progressive_key progressive_key_of(const rm_ctx *ctx, const rm_params *p, const rm_lens *lens, bool soft, uint32_t n_lights) {
+// A tick's moving spheres (rm_motion_host.inc): rm_render_progressive_motion's arguments; the other ticks pass none
+struct rm_motion_tick {
+    const rm_vec3 *velocities;
+    uint32_t n_shapes;
+    double shutter;
+};
+
+static rm_progressive_key progressive_key_of(const rm_ctx *ctx, const rm_params *p, const rm_lens *lens, bool soft, uint32_t n_lights,
+                                             const rm_motion_tick *motion = nullptr) {
     rm_progressive_key key;
     std::memset(&key, 0, sizeof key);
     key.fov = p->fov; key.half_fov = p->half_fov; key.height = p->height; key.width = p->width; key.ratio = p->ratio;
@@ -92,6 +102,7 @@ static rm_progressive_key progressive_key_of(const rm_ctx *ctx, const rm_params 
     key.basis = ctx->basis;
     key.copies = ctx->upload_copies;
     key.soft = soft ? 1u : 0u; key.n_lights = n_lights;
+    if (motion) { key.motion = 1u; key.n_shapes = motion->n_shapes; key.shutter = motion->shutter; }
     return key;
 }
 
@@ -108,6 +119,11 @@ struct rm_progressive {
     std::vector<double> radii, offsets;
     void *d_offsets = nullptr;
     size_t offsets_bytes = 0;                // d_offsets has room for that many
+    // moving spheres (rm_motion_host.inc): the velocities the sum belongs to, and the staged slice of rm_motion_sequence
+    std::vector<rm_vec3> velocities;
+    std::vector<double> shape_offsets;
+    void *d_shape_offsets = nullptr;
+    size_t shape_offsets_bytes = 0;          // d_shape_offsets has room for that many
 };
 
 // rm_soft_host.inc: the check of a soft tick's radii, and the launch with an offset table
@@ -115,10 +131,15 @@ static rm_status check_soft_radii(rm_ctx *ctx, const char *who, const double *ra
 static rm_status launch_soft(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, const void *offsets, uint32_t n_before,
                              void *sum, void *mean, void *rgb8, hipStream_t stream);
 
+// rm_motion_host.inc: the check of a motion tick's velocities and shutter, and the launch with both offset tables
+static rm_status check_motion_tick(rm_ctx *ctx, const char *who, const rm_motion_tick &m);
+static rm_status launch_motion(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, const void *offsets,
+                               const void *shape_offsets, uint32_t n_before, void *sum, void *mean, void *rgb8, hipStream_t stream);
+
 static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
     rm_progressive *g = ctx->progressive;
     if (!g) return;
-    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->d_offsets})
+    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->d_offsets, g->d_shape_offsets})
         if (b && device_ok) (void)hipFree(b);
     delete g;
     ctx->progressive = nullptr;
@@ -126,23 +147,30 @@ static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
 
 // `soft`: rm_render_progressive_soft's tick -- n_lights radii (checked here), the slice of rm_light_sequence staged beside the
 // table's and the kernel of rm_soft.hip; else radii is NULL, n_lights 0 and everything as it was before there were area lights.
+// `motion`: rm_render_progressive_motion's tick -- the velocities and the shutter (checked here), the slice of rm_motion_sequence
+// staged as well, light offsets for every light of the scene (zeros where `soft` is off) and the kernel of rm_motion.hip; else NULL.
 static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, bool soft, const double *radii,
                                             uint32_t n_lights, int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total,
-                                            rm_timing *timing) {
+                                            rm_timing *timing, const rm_motion_tick *motion = nullptr) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
     const auto t_begin = std::chrono::steady_clock::now();
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
     if (soft)
         if (rm_status rst = check_soft_radii(ctx, who, radii, n_lights)) return rst;
+    if (motion)
+        if (rm_status mst = check_motion_tick(ctx, who, *motion)) return mst;
+    const uint32_t n_shapes = motion ? motion->n_shapes : 0u;
     const uint32_t rows = refine_rows(p);
     double kernel_ms = 0., d2h_ms = 0.;
     uint32_t total = 0u;
     if (rows > 0u) {
         if (!ctx->progressive) ctx->progressive = new rm_progressive();
         rm_progressive &g = *ctx->progressive;
-        const rm_progressive_key key = progressive_key_of(ctx, p, lens, soft, n_lights);
+        const rm_progressive_key key = progressive_key_of(ctx, p, lens, soft, n_lights, motion);
         const bool same = !restart && g.have_key && std::memcmp(&key, &g.key, sizeof key) == 0 && g.radii.size() == n_lights &&
-                          (n_lights == 0u || std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) == 0);
+                          (n_lights == 0u || std::memcmp(g.radii.data(), radii, n_lights * sizeof(double)) == 0) &&
+                          g.velocities.size() == n_shapes &&
+                          (n_shapes == 0u || std::memcmp(g.velocities.data(), motion->velocities, n_shapes * sizeof(rm_vec3)) == 0);
         const uint32_t n_before = same ? g.n : 0u;
         const size_t pixels = (size_t)rows * p->frame_width;
         const bool saturated = n_before + lens->n_samples > RM_PROGRESSIVE_MAX_SAMPLES;   // (then n_before > 0: the frame stands)
@@ -162,14 +190,29 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
             }
             if (rm_status sst = rm_lens_sequence(n_before, lens->n_samples, g.table)) return sst;
             RM_HIP(ctx, hipMemcpyAsync(g.d_table, g.table, (size_t)lens->n_samples * 4u * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            const size_t n_offsets = (size_t)lens->n_samples * n_lights * 3u;
-            if (n_offsets > 0u) {                                          // (soft, and the scene has lights)
+            // (a motion tick's kernel reads a row for every light of the scene: zeros where the lights are points)
+            const uint32_t staged_lights = motion ? ctx->image.H.n_lights : n_lights;
+            const size_t n_offsets = (size_t)lens->n_samples * staged_lights * 3u;
+            if (n_offsets > 0u) {                                          // (soft or motion, and the scene has lights)
                 if (rm_status gst = grow_device_buffer(ctx, &g.d_offsets, &g.offsets_bytes, n_offsets * sizeof(double))) return gst;
-                g.offsets.resize(n_offsets);
-                if (rm_status sst = rm_light_sequence(n_before, lens->n_samples, radii, n_lights, g.offsets.data())) return sst;
+                g.offsets.assign(n_offsets, 0.);
+                if (soft)
+                    if (rm_status sst = rm_light_sequence(n_before, lens->n_samples, radii, n_lights, g.offsets.data())) return sst;
                 RM_HIP(ctx, hipMemcpyAsync(g.d_offsets, g.offsets.data(), n_offsets * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             }
+            const size_t n_shape_offsets = (size_t)lens->n_samples * n_shapes * 3u;
+            if (n_shape_offsets > 0u) {                                    // (motion, and the scene has shapes)
+                if (rm_status gst = grow_device_buffer(ctx, &g.d_shape_offsets, &g.shape_offsets_bytes, n_shape_offsets * sizeof(double))) return gst;
+                g.shape_offsets.resize(n_shape_offsets);
+                if (rm_status sst = rm_motion_sequence(n_before, lens->n_samples, motion->velocities, n_shapes, motion->shutter, g.shape_offsets.data()))
+                    return sst;
+                RM_HIP(ctx, hipMemcpyAsync(g.d_shape_offsets, g.shape_offsets.data(), n_shape_offsets * sizeof(double), hipMemcpyHostToDevice,
+                                           ctx->stream));
+            }
             auto launch = [&]() {
+                if (motion)
+                    return launch_motion(ctx, p, lens, g.d_table, n_offsets > 0u ? g.d_offsets : nullptr,
+                                         n_shape_offsets > 0u ? g.d_shape_offsets : nullptr, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream);
                 return soft ? launch_soft(ctx, p, lens, g.d_table, n_offsets > 0u ? g.d_offsets : nullptr, n_before, g.d_sum, g.d_mean, g.d_rgb8,
                                           ctx->stream)
                             : launch_accum(ctx, p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream);
@@ -177,6 +220,8 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
             g.key = key;
             g.radii.assign(radii, radii + n_lights);                       // (n_lights == 0: empty, radii may be NULL)
+            if (motion) g.velocities.assign(motion->velocities, motion->velocities + n_shapes);
+            else g.velocities.clear();
             g.n = n_before + lens->n_samples;
             g.have_key = true;
         }

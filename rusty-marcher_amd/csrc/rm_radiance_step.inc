@@ -12,7 +12,7 @@
 // How a lane comes by its ray is the including kernel's business; sample_direction below is the one way to form a sample's.
 //
 // Also here, once, what the including kernels share beside the step: their view of the scene (global_scene_view, rm_query.hip's
-// too), the display byte of a mean (to_byte) and the rule of the moved lights (OffsetLights).
+// too), the display byte of a mean (to_byte) and the rules of the moved lights (OffsetLights) and spheres (OffsetSpheres).
 
 namespace rmradiance {
 
@@ -44,6 +44,25 @@ struct OffsetLights {
     }
 };
 
+// Device sphere i of a sample whose spheres are moved: the record's centre plus the sample's row of a shape offset table, rounded
+// once a component (the moving spheres, rm_motion.hip; StoredSpheres of rm_trace.inc is the rule without).  The table is in the
+// order of the scene's shape list and the device order of the spheres need not be (a scene with a sphere hierarchy is permuted):
+// the queries' pid map leads from i to the shape, a wave-uniform load in the walks.  `at` is the one place the addition stands.
+struct OffsetSpheres {
+    static constexpr bool moves = true;
+    const double *row;                                                   // n_shapes x 3 doubles
+    const uint32_t *pid_map;                                             // 2 words a pid; word 0: the shape
+    __device__ __forceinline__ V3 at(double cx, double cy, double cz, uint32_t i) const {
+        const double *o = row + 3u * pid_map[2u * i];
+        return mk(cx + o[0], cy + o[1], cz + o[2]);
+    }
+    __device__ __forceinline__ SphereRec operator()(const SphereRec &s, uint32_t i) const {
+        const V3 c = at(s.cx, s.cy, s.cz, i);
+        return SphereRec{c.x, c.y, c.z, s.r2};
+    }
+    __device__ __forceinline__ V3 centre(const double *sp, uint32_t i) const { return at(sp[0], sp[1], sp[2], i); }
+};
+
 // The un-normalised direction of the sample (sx, sy): renderer.rs:128-135 at a real-valued position, the host's
 // backproject_tables operation for operation.  A: an argument block with the params' Renderer (width, height, half_fov,
 // ratio) and the context's basis (cam_r*, cam_u*, cam_f*; read where oriented).
@@ -58,10 +77,11 @@ __device__ __forceinline__ V3 sample_direction(const A &q, bool oriented, double
 
 // What comes back along the lane's ray (orig, dir), cast as a primary ray (n_recursion = 1) with the cap max_depth >= 1; zero
 // for a lane whose `on` is off.  Called by whole waves.  `lights`: where the lane's lights stand at every step of its ray, the
-// children's included (rm_trace.inc, StoredLights: as the scene image says).
-template <bool BVH, int POW, int STACK, class LIGHTS = StoredLights>
+// children's included (rm_trace.inc, StoredLights: as the scene image says).  `spheres`: where the lane's spheres stand, in the
+// same way (StoredSpheres).
+template <bool BVH, int POW, int STACK, class LIGHTS = StoredLights, class SPHERES = StoredSpheres>
 __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 dir, bool on, const V3 bg, const uint32_t max_depth,
-                                             const LIGHTS &lights = LIGHTS()) {
+                                             const LIGHTS &lights = LIGHTS(), const SPHERES &spheres = SPHERES()) {
     double weight = 1.;
     uint32_t depth = 1;                                                  // renderer.rs:83
     V3 acc = mk(0., 0., 0.);
@@ -72,7 +92,7 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
 
     while (__any(on)) {                                                  // one ray step; the loop itself is wave-uniform
         Hit h{0., 0u};
-        const bool got = closest_hit<BVH, false, false>(sc, orig, dir, on, h, false, 0ull) & on;
+        const bool got = closest_hit<BVH, false, false>(sc, orig, dir, on, h, false, 0ull, spheres) & on;
         // what this step adds to the lane's answer: weight x (background + direct light) on a hit (renderer.rs:272-275),
         // weight x background where a child leaves the scene (:302-303), nothing where the caller's ray does (:305), + the
         // children beyond the cap (:262-264).  Lanes without a ray add zero.
@@ -81,8 +101,8 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
         double w_cap = 0.;
         bool next = false;                                               // the lane goes on with a child of its ray
         if (__any(got)) {
-            const Surface s = surface_at<false>(sc, orig, dir, h, got);
-            L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, neg(normalized(dir)), s, got, h.pid, lights), bg);
+            const Surface s = surface_at<false>(sc, orig, dir, h, got, spheres);
+            L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, neg(normalized(dir)), s, got, h.pid, lights, spheres), bg);
             const bool glass = got & (s.mat[8] != 0.);                   // is_glass_like, renderer.rs:277
             if (__any(glass)) {
                 const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];

@@ -256,6 +256,17 @@ __device__ __forceinline__ SphereRec load_sphere(const double *__restrict__ S, c
     const double *sp = S + H.off_spheres + RM_SPHERE_WORDS * i;
     return SphereRec{sp[0], sp[1], sp[2], sp[3]};
 }
+
+// Where device sphere i stands, given its record.  The default is the record's own centre; a kernel whose samples move their
+// spheres (rm_motion.hip) hands closest_hit, any_hit, any_hit2, surface_at and shade_direct another rule.  `operator()` serves
+// the walks (a record fetched by a wave-uniform index), `centre` the normal (the lane's own hit): one rule forms both, so the
+// normal sees the centre the hit test saw.  Nothing else in those five reads a sphere's position but the hierarchy's boxes, the
+// bundle cull and the occluder masks, which hold for the stored centres: such a kernel runs without the three.
+struct StoredSpheres {
+    static constexpr bool moves = false;
+    __device__ __forceinline__ SphereRec operator()(const SphereRec &s, uint32_t) const { return s; }
+    __device__ __forceinline__ V3 centre(const double *sp, uint32_t) const { return mk(sp[0], sp[1], sp[2]); }
+};
 __device__ __forceinline__ PolyRec load_polygon(const double *__restrict__ S, const rm_dev_header &H, uint32_t i) {
     const double *pg = S + H.off_polygons + RM_POLYGON_WORDS * i;
     const uint32_t *u = reinterpret_cast<const uint32_t *>(pg + 6);
@@ -749,8 +760,11 @@ __device__ __forceinline__ void closest_triangle(const SceneView &sc, ClosestSta
 // `have_mask` (wave-uniform): the tile was classified and these are its primary rays -- only the
 // primitives of `mask` (bit = pid, scenes of up to 64 primitives) can be hit by any of them
 // (rm_classify.hip: the same conservative tests as the bundle cull, once per tile instead of once per wave).
-template <bool BVH, bool CULL, bool EDGES>
-__device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, bool on, Hit &out, bool have_mask, unsigned long long mask) {
+// `spheres`: where each sphere stands (StoredSpheres: as the scene image says; another rule walks flat, without cull or mask).
+template <bool BVH, bool CULL, bool EDGES, class SPHERES = StoredSpheres>
+__device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, bool on, Hit &out, bool have_mask, unsigned long long mask,
+                                            const SPHERES &spheres = SPHERES()) {
+    static_assert(!SPHERES::moves || (!BVH && !CULL), "moved spheres walk flat: boxes and bundles hold for the stored centres");
     const double *__restrict__ S = sc.G;
     const rm_dev_header &H = sc.H;
     ClosestState c{false, 0., 0., 0u};
@@ -819,14 +833,14 @@ __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, boo
         i = H.n_spheres;
     }
     for (; i + 4u <= H.n_spheres; i += 4u) {
-        const SphereRec s0 = load_sphere(S, H, i), s1 = load_sphere(S, H, i + 1u);
-        const SphereRec s2 = load_sphere(S, H, i + 2u), s3 = load_sphere(S, H, i + 3u);
+        const SphereRec s0 = spheres(load_sphere(S, H, i), i), s1 = spheres(load_sphere(S, H, i + 1u), i + 1u);
+        const SphereRec s2 = spheres(load_sphere(S, H, i + 2u), i + 2u), s3 = spheres(load_sphere(S, H, i + 3u), i + 3u);
         closest_sphere<true>(sc, c, s0, i, o, d, on);
         closest_sphere<true>(sc, c, s1, i + 1u, o, d, on);
         closest_sphere<true>(sc, c, s2, i + 2u, o, d, on);
         closest_sphere<true>(sc, c, s3, i + 3u, o, d, on);
     }
-    for (; i < H.n_spheres; i++) closest_sphere<true>(sc, c, load_sphere(S, H, i), i, o, d, on);
+    for (; i < H.n_spheres; i++) closest_sphere<true>(sc, c, spheres(load_sphere(S, H, i), i), i, o, d, on);
 
     for (uint32_t g = 0; g < H.n_polygons; g++) closest_polygon<true>(sc, c, g, o, d, on);
 
@@ -883,8 +897,9 @@ __device__ __forceinline__ bool shadow_sphere(const SphereRec &s, V3 o, V3 d, bo
 // centre and its square, the numerator of a plane hit -- is computed once, bit for bit what
 // each ray's own walk computes; the records are fetched once.  (Few-primitive kernels only:
 // the bundles of the two lights cull different primitives.)
+template <class SPHERES = StoredSpheres>
 __device__ __forceinline__ void any_hit2(const SceneView &sc, V3 o, V3 d0, V3 d1, bool decided0, bool decided1, bool &out0,
-                                         bool &out1) {
+                                         bool &out1, const SPHERES &spheres = SPHERES()) {
     const double *__restrict__ S = sc.G;
     const rm_dev_header &H = sc.H;
     bool occ0 = decided0, occ1 = decided1;
@@ -897,12 +912,12 @@ __device__ __forceinline__ void any_hit2(const SceneView &sc, V3 o, V3 d0, V3 d1
     };
     uint32_t i = 0;
     for (; i + 4u <= H.n_spheres; i += 4u) {
-        const SphereRec s0 = load_sphere(S, H, i), s1 = load_sphere(S, H, i + 1u);
-        const SphereRec s2 = load_sphere(S, H, i + 2u), s3 = load_sphere(S, H, i + 3u);
+        const SphereRec s0 = spheres(load_sphere(S, H, i), i), s1 = spheres(load_sphere(S, H, i + 1u), i + 1u);
+        const SphereRec s2 = spheres(load_sphere(S, H, i + 2u), i + 2u), s3 = spheres(load_sphere(S, H, i + 3u), i + 3u);
         sphere(s0); sphere(s1); sphere(s2); sphere(s3);
         if (__all(occ0 & occ1)) { out0 = occ0; out1 = occ1; return; }
     }
-    for (; i < H.n_spheres; i++) sphere(load_sphere(S, H, i));
+    for (; i < H.n_spheres; i++) sphere(spheres(load_sphere(S, H, i), i));
     for (uint32_t g = 0; g < H.n_polygons; g++) {
         if (__all(occ0 & occ1)) break;
         const PolyRec pg = load_polygon(S, H, g);
@@ -983,8 +998,10 @@ __device__ __forceinline__ void shadow_masks2(const SceneView &sc, bool got, uin
 // exactly zero); they come back as occluded.  `through` / `rho`: every shadow ray passes
 // within rho of that point -- the light (renderer.rs:166-172: the direction is taken from
 // the hit point, the origin is 1e-3 of the normal off it).
-template <bool BVH, bool CULL, bool EDGES>
-__device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool decided, V3 through, double rho) {
+template <bool BVH, bool CULL, bool EDGES, class SPHERES = StoredSpheres>
+__device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool decided, V3 through, double rho,
+                                        const SPHERES &spheres = SPHERES()) {
+    static_assert(!SPHERES::moves || (!BVH && !CULL), "moved spheres walk flat: boxes and bundles hold for the stored centres");
     const double *__restrict__ S = sc.G;
     const rm_dev_header &H = sc.H;
     bool occ = decided;
@@ -1039,15 +1056,15 @@ __device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool de
         i = H.n_spheres;
     }
     for (; i + 4u <= H.n_spheres; i += 4u) {
-        const SphereRec s0 = load_sphere(S, H, i), s1 = load_sphere(S, H, i + 1u);
-        const SphereRec s2 = load_sphere(S, H, i + 2u), s3 = load_sphere(S, H, i + 3u);
+        const SphereRec s0 = spheres(load_sphere(S, H, i), i), s1 = spheres(load_sphere(S, H, i + 1u), i + 1u);
+        const SphereRec s2 = spheres(load_sphere(S, H, i + 2u), i + 2u), s3 = spheres(load_sphere(S, H, i + 3u), i + 3u);
         occ = occ | shadow_sphere(s0, o, d, occ);
         occ = occ | shadow_sphere(s1, o, d, occ);
         occ = occ | shadow_sphere(s2, o, d, occ);
         occ = occ | shadow_sphere(s3, o, d, occ);
         if (__all(occ)) return occ;
     }
-    for (; i < H.n_spheres; i++) occ = occ | shadow_sphere(load_sphere(S, H, i), o, d, occ);
+    for (; i < H.n_spheres; i++) occ = occ | shadow_sphere(spheres(load_sphere(S, H, i), i), o, d, occ);
     if (__all(occ)) return occ;
 
     for (uint32_t g = 0; g < H.n_polygons; g++) {
@@ -1093,8 +1110,9 @@ struct Surface {
 
 // `got`: lanes with a hit.  The other lanes read record 0 of everything (in bounds: the
 // blob ends in 64 words of padding) and their surface is never used.
-template <bool DIV>
-__device__ __forceinline__ Surface surface_at(const SceneView &sc, V3 o, V3 d, const Hit &h, bool got RM_SUS_PARAM) {
+template <bool DIV, class SPHERES = StoredSpheres>
+__device__ __forceinline__ Surface surface_at(const SceneView &sc, V3 o, V3 d, const Hit &h, bool got RM_SUS_PARAM,
+                                              const SPHERES &spheres = SPHERES()) {
     Surface s;
     s.point = o + scaled(d, h.t);
     const uint32_t ns = sc.H.n_spheres, np = sc.H.n_polygons;
@@ -1105,7 +1123,8 @@ __device__ __forceinline__ Surface surface_at(const SceneView &sc, V3 o, V3 d, c
     s.normal = mk(0., 0., 0.);
     if (where<DIV>(is_s)) {
         const double *sp = sc.S + sc.H.off_spheres + RM_SPHERE_WORDS * (is_s ? pid : 0u);
-        s.normal = RM_NORMALIZED(mk(s.point.x - sp[0], s.point.y - sp[1], s.point.z - sp[2]), is_s);   // sphere.rs:58
+        const V3 centre = spheres.centre(sp, is_s ? pid : 0u);
+        s.normal = RM_NORMALIZED(mk(s.point.x - centre.x, s.point.y - centre.y, s.point.z - centre.z), is_s);   // sphere.rs:58
     }
     if (where<DIV>(is_p | is_t)) {
         const uint32_t word = is_p ? sc.H.off_polygons + RM_POLYGON_WORDS * (pid - ns)          // polygon.rs:95
@@ -1205,9 +1224,10 @@ __device__ __forceinline__ LightAt light_at(const SceneView &sc, uint32_t l, con
 
 // `pid`: the primitive each lane's hit lies on.
 // `lights`: where each light stands (StoredLights: as the scene image says).
-template <int POW, bool BVH, bool CULL, bool EDGES, class LIGHTS = StoredLights>
+// `spheres`: where each sphere stands in the shadow walks (StoredSpheres: as the scene image says).
+template <int POW, bool BVH, bool CULL, bool EDGES, class LIGHTS = StoredLights, class SPHERES = StoredSpheres>
 __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, const Surface &s, bool got, uint32_t pid RM_SUS_PARAM,
-                                           const LIGHTS &lights = LIGHTS()) {
+                                           const LIGHTS &lights = LIGHTS(), const SPHERES &spheres = SPHERES()) {
     const double *m = s.mat;
     const double exponent = m[5];
     // (colour and specular weight are fetched where a light is found unshadowed: held in
@@ -1234,7 +1254,8 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
         }
     };
     // plain-walk kernels: the occluder masks of the walks, where the scene has them
-    const bool masks = !BVH && !CULL && sc.H.off_occ != 0u;
+    // (keyed on the stored centres: a rule that moves the spheres walks without them, whatever the header says)
+    const bool masks = !BVH && !CULL && !SPHERES::moves && sc.H.off_occ != 0u;
     for (uint32_t l = 0; l < sc.H.n_lights;) {
         const LightAt a = light_at(sc, l, s, dir_to_viewer, exponent, got RM_SUS_ARG, lights);
         const bool dec_a = !got | a.dark;
@@ -1256,7 +1277,7 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
                 if (masks && (m_a & m_b) != ((n >= 64u) ? ~0ull : (1ull << n) - 1ull))
                     any_hit2_masked(sc, from, a.dir, b.dir, dec_a, dec_b, occ_a, occ_b, m_a, m_b);
                 else
-                    any_hit2(sc, from, a.dir, b.dir, dec_a, dec_b, occ_a, occ_b);
+                    any_hit2(sc, from, a.dir, b.dir, dec_a, dec_b, occ_a, occ_b, spheres);
                 RM_PHASE_ADD(sc, 1, t_sh);
                 add_light(l, a, !occ_a);                              // :174
                 add_light(l + 1u, b, !occ_b);
@@ -1265,7 +1286,7 @@ __device__ __forceinline__ V3 shade_direct(const SceneView &sc, V3 neg_dir, cons
             }
         }
         const unsigned long long t_sh = RM_PHASE_T();
-        const bool lit = !any_hit<BVH, CULL, EDGES>(sc, a.from, a.dir, dec_a, a.pos, sc.H.shadow_rho);   // :174
+        const bool lit = !any_hit<BVH, CULL, EDGES>(sc, a.from, a.dir, dec_a, a.pos, sc.H.shadow_rho, spheres);   // :174
         RM_PHASE_ADD(sc, 1, t_sh);
         add_light(l, a, lit);
         l += 1u;

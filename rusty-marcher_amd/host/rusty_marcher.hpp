@@ -464,6 +464,31 @@ struct Renderer {
             }
         return status(t0, frame.width, frame.height);
     }
+    // render_progressive_soft with moving spheres (rm_render_progressive_motion): shape k of the scene, a sphere, moves by
+    // velocities[k] -- one vector a shape, zero for what is not a sphere -- while the shutter stands open for `shutter`, and every
+    // sample sees it at a time of its own, so the frame converges to a picture blurred along the motion.  radii: one radius a light;
+    // empty: point lights.  Beyond what begins a frame again in render_progressive_soft, a changed velocity or shutter does, and so
+    // does a switch between the calls.  Every ray of such a frame tests every primitive: a hierarchy holds for spheres that stand still.
+    std::string render_progressive_motion(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const std::vector<Vec3f> &velocities,
+                                          double shutter, uint32_t n_samples, const std::vector<double> &radii = {}, double aperture = 0.,
+                                          double focus = 1., bool restart = false) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        std::vector<rm_vec3> v;
+        for (const Vec3f &e : velocities) v.push_back(e.c());
+        check(rm_render_progressive_motion(ctx_, &p, &lens, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), v.data(),
+                                           (uint32_t)v.size(), shutter, restart ? 1 : 0, flat.data(), nullptr, &last_samples, &last_timing),
+              ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
     // A tick of a converging frame (rm_render_converging): render_progressive -- with area lights where `radii` holds one radius a
     // light; empty: point lights -- that casts its n_samples more samples only for the pixels still noisy and their neighbours.  A
     // pixel is settled once it has converge.min_samples samples and the standard error of the mean of r + g + b is at most

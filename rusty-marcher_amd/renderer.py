@@ -174,6 +174,32 @@ class Renderer:
         a pinhole unless an aperture is given."""
         return self.render_progressive_soft(frame, scene, light_radii, aperture, focus, n_samples, restart=True)
 
+    def render_progressive_motion(self, frame, scene, velocities, shutter, n_samples, light_radii=None, aperture=0., focus=1., restart=False):
+        """render_progressive_soft with moving spheres (rm_render_progressive_motion): shape k of the scene, a sphere, moves by
+        velocities[k] -- one Vec3f or None a shape, None or zero for what is not a sphere -- while the shutter stands open for
+        `shutter`, and every sample sees it at a time of its own, so the frame converges to a picture blurred along the motion.
+        light_radii: one radius a light for area lights, None for points.  Beyond what begins a frame again in
+        render_progressive_soft, a changed velocity or shutter does, and so does a switch between the calls.  Every ray of such
+        a frame tests every primitive: a hierarchy holds for spheres that stand still."""
+        backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        v = backend._velocities(velocities, len(scene.shapes))
+        backend._shutter(shutter)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        return self._tick(frame, scene, lambda ctx, p: ctx.render_progressive_motion(p, v, shutter, aperture, focus, n_samples, radii, restart,
+                                                                                      host_rgb=frame.buffer))
+
+    def render_motion_blur(self, frame, scene, velocities, shutter, n_samples):
+        """One frame with motion blur: a restarted render_progressive_motion ticked in slices of at most 64 until the frame holds
+        n_samples samples a pixel, through a pinhole, point lights.  Prints and returns what the last tick does."""
+        if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= backend.PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("n_samples must be an integer in 1..%d, got %r" % (backend.PROGRESSIVE_MAX_SAMPLES, n_samples))
+        left, message = int(n_samples), None
+        while left > 0:
+            step = min(left, 64)
+            message = self.render_progressive_motion(frame, scene, velocities, shutter, step, restart=left == n_samples)
+            left -= step
+        return message
+
     def render_converging(self, frame, scene, tolerance, n_samples, min_samples=16, max_samples=1024, light_radii=None, aperture=0., focus=1.,
                           restart=False):
         """A tick of a converging frame (rm_render_converging): render_progressive -- with area lights where light_radii is

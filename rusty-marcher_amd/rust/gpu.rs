@@ -307,6 +307,9 @@ extern "C" {
     fn rm_light_sequence(first: u32, count: u32, radii: *const f64, n_lights: u32, offsets: *mut f64) -> c_int;
     fn rm_accumulate_soft_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_offsets: *const c_void, n_lights: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_progressive_soft(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_motion_sequence(first: u32, count: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, offsets: *mut f64) -> c_int;
+    fn rm_accumulate_motion_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_progressive_motion(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
     fn rm_converge_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
     fn rm_accumulate_converging_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_offsets: *const c_void, n_lights: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_render_converging(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
@@ -704,6 +707,108 @@ impl Gpu {
         let n = 3 * radii.len() * count as usize;
         let mut offsets = vec![0f64; n + 1]; // (+ 1: never a dangling pointer)
         check(unsafe { rm_light_sequence(first, count, radii.as_ptr(), radii.len() as u32, offsets.as_mut_ptr()) }, ptr::null());
+        offsets.truncate(n);
+        offsets
+    }
+
+    /// `render_progressive_soft` with moving spheres: shape k of the scene, a sphere, moves by `velocities[k]` -- one vector a
+    /// shape, zero for what is not a sphere -- while the shutter stands open for `shutter`, and every sample sees it at a time of
+    /// its own, so the frame converges to a picture blurred along the motion.  `radii`: one radius a light; `None`: point
+    /// lights.  Beyond what begins a frame again in `render_progressive_soft`, a changed velocity or shutter does, and so does a
+    /// switch between the calls.  Every ray of such a frame tests every primitive: a hierarchy holds for spheres that stand still.
+    pub fn render_progressive_motion(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        radii: Option<&[f64]>,
+        velocities: &[Vec3f],
+        shutter: f64,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let v: Vec<RmVec3> = velocities.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect();
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut total: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_progressive_motion(self.ctx, &p, &lens, radii_ptr, n_lights, v.as_ptr(), v.len() as u32, shutter, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut total, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), total)
+    }
+
+    /// The device call under `render_progressive_motion`: `accumulate_soft` with `device_shape_offsets`, `n_samples` x `n_shapes`
+    /// x 3 f64 -- rows of `motion_sequence`, or any offsets of the caller's making -- that move the sphere that is shape k of
+    /// sample row s.  `n_lights` and `n_shapes` are the resident scene's; a caller with point lights passes zeros.
+    pub fn accumulate_motion(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_motion_device(self.ctx, &p, &lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// Rows `first .. first + count` of the library's shape offset sequence for shapes of the velocities `velocities` and a
+    /// shutter open for `shutter`: three f64 a shape, `velocities.len()` shapes a row.
+    pub fn motion_sequence(first: u32, count: u32, velocities: &[Vec3f], shutter: f64) -> Vec<f64> {
+        let n = 3 * velocities.len() * count as usize;
+        let v: Vec<RmVec3> = velocities.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect();
+        let mut offsets = vec![0f64; n + 1]; // (+ 1: never a dangling pointer)
+        check(unsafe { rm_motion_sequence(first, count, v.as_ptr(), v.len() as u32, shutter, offsets.as_mut_ptr()) }, ptr::null());
         offsets.truncate(n);
         offsets
     }
