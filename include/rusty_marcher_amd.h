@@ -1129,6 +1129,70 @@ rm_status rm_render_converging(rm_ctx *ctx, const rm_params *params, const rm_le
                                double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
                                rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
 
+/* ---- converging frames with moving spheres: motion blur, noisy pixels only ---------------------
+ * The converging frames sample the lens and the lights; the moving spheres sample time.  These
+ * calls do both: a moving sphere leaves a band of pixels that settle slowly, the rest of the
+ * picture settles after min_samples, and only the band goes on being sampled.  Additive to ABI
+ * version 5; a host detects them by " converge-motion" in rm_build_info().
+ *
+ * A pass is rm_accumulate_converging_device's word for word -- select, the rows a listed pixel
+ * casts, fold, mean, bytes, list and mask -- with one rule added, the moving spheres':
+ *   - a listed pixel with count n casts rows n .. n + ns - 1 of the three tables;
+ *   - for row r the sphere that is shape k of the scene stands at C'.c = C.c + shape_offsets[r][k].c
+ *     per component, C the resident scene's: one addition, rounded once;
+ *   - C' takes C's place in the closest-hit test, both shadow tests and the normal, at every
+ *     bounce;
+ *   - the shape offset table is [table_rows][n_shapes][3] doubles in the order of the scene's shape
+ *     list, a prefix of rm_motion_sequence in the tick; the device's spheres are found in it
+ *     through the queries' pid map.  Rows of shapes that are not spheres are never read.
+ * The light offset table is [table_rows][n_lights][3] and required where the scene has lights (a
+ * caller with point lights passes zeros), as in rm_accumulate_motion_device.
+ *
+ * Two consequences:
+ *   - with every shape offset +0. or -0. a pass is byte for byte rm_accumulate_converging_device's
+ *     for the same light offsets -- sum, stats, count, mean, bytes, mask, and the list as a set --
+ *     for centre coordinates that are not -0. (-0. + +0. is +0.);
+ *   - the fold is a left fold in table order: a pixel with count c holds byte for byte the sum and
+ *     the mean rm_accumulate_motion_device leaves after c rows of the same three tables, however
+ *     the passes were sliced.  With tolerance < 0 a run of passes is the plain motion run byte for
+ *     byte in sum, mean and bytes.
+ *
+ * Cost: as the moving spheres', the kernel tests every primitive against every ray (the flat walk),
+ * whatever hierarchies the scene image holds.
+ *
+ * rm_accumulate_converging_motion_device is asynchronous on hip_stream, neither reads nor writes
+ * render state and keeps all of its state in the caller's buffers.  Its checks are
+ * rm_accumulate_converging_device's and rm_accumulate_motion_device's together: n_lights must be
+ * the resident scene's and device_light_offsets not NULL when it has lights; n_shapes must be the
+ * resident scene's shape count and device_shape_offsets not NULL when it holds a sphere.  A refused
+ * call names the offender in rm_last_error and touches no buffer.  The tables' contents are a
+ * precondition: a non-finite offset gives unspecified pixels, never a fault.
+ *
+ * rm_render_converging_motion is the viewer's tick: rm_render_converging on the same context-owned
+ * state -- the two ticks share one frame -- with a third resident prefix, the shape offsets
+ * (rm_motion_sequence of velocities and shutter, appended to as the frame grows), and the key
+ * extended by n_shapes, the bytes of velocities and of shutter.  So the frame begins again when a
+ * velocity or the shutter changes, when a caller switches between the two ticks (velocities of zero
+ * are velocities, not the plain call), and on everything that begins it again in
+ * rm_render_converging; rm_converge and n_samples stay outside the key.  radii == NULL is "no
+ * radii" and stages light offsets of zero for every light of the scene.  Checked before anything
+ * else happens: rm_render_converging's checks, n_shapes the resident scene's, velocities and
+ * shutter as rm_motion_sequence demands, and a velocity that is not zero for a shape that is not a
+ * sphere -- RM_ERR_INVALID_ARG, the shape named in rm_last_error; a refused call changes nothing of
+ * the state.  A finished picture launches nothing.  The report, rows == 0 and timing are
+ * rm_render_converging's.
+ */
+rm_status rm_accumulate_converging_motion_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                                 const rm_converge *converge, const void *device_table, uint32_t table_rows,
+                                                 const void *device_light_offsets, uint32_t n_lights,
+                                                 const void *device_shape_offsets, uint32_t n_shapes, int fresh,
+                                                 const rm_converge_frame *buffers, void *hip_stream);
+rm_status rm_render_converging_motion(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                                      const double *radii /* NULL: point lights */, uint32_t n_lights,
+                                      const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart,
+                                      double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                      rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

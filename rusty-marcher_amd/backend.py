@@ -171,6 +171,43 @@ def _converge(tolerance, min_samples, max_samples, n_samples, table_rows=PROGRES
     return _lib.rm_converge(tolerance, int(min_samples), int(max_samples))
 
 
+def _converging_args(ctx, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples, max_samples, mean, rgb8, mask,
+                     workspace):
+    """What Context.accumulate_converging_device and accumulate_converging_motion_device check of their common arguments (ctx: the
+    context)
+    -> (rm_lens, rm_converge, the table's tensor, the workspace)."""
+    torch = _torch()
+    h, w = params.frame_height, params.frame_width
+    for name, t, dtype, shape in (("sum", sum, torch.float64, (h, w, 3)), ("stats", stats, torch.float64, (h, w, 2)),
+                                  ("count", count, torch.int32, (h, w)), ("mean", mean, torch.float64, (h, w, 3)),
+                                  ("rgb8", rgb8, torch.uint8, (h, w, 3)), ("mask", mask, torch.uint8, (h, w))):
+        if t is None and name in ("mean", "rgb8", "mask"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, shape))
+        if t.device.type != "cuda" or t.device.index != ctx.device:
+            raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, ctx.device, t.device))
+    if mean is not None and mean.data_ptr() == sum.data_ptr():
+        raise ValueError("mean must not be the sum's own tensor")
+    lens = _lens(aperture, focus, n_samples)
+    if isinstance(table, torch.Tensor):
+        if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+            raise ValueError("table must be a contiguous float64 torch tensor of shape (rows, 4)")
+        if table.device != sum.device:
+            raise ValueError("table must live on %s, not %s" % (sum.device, table.device))
+    else:
+        rows = np.asarray(table)
+        table = torch.from_numpy(_lens_rows(rows, rows.shape[0] if rows.ndim == 2 else 0)).to(sum.device)
+    conv = _converge(tolerance, min_samples, max_samples, lens.n_samples, table.shape[0])
+    need = Context.converge_workspace(ctx, params) // 4
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=sum.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.shape[0] < need \
+            or not workspace.is_contiguous() or workspace.device != sum.device:
+        raise ValueError("workspace must be a contiguous int32 torch tensor of at least %d words on %s" % (need, sum.device))
+    return lens, conv, table, workspace
+
+
 def _accumulate_args(device, params, sum, aperture, focus, table, n_before, mean, rgb8):
     """What accumulate_lens_device and accumulate_soft_device check of their common arguments -> (rm_lens, the table's tensor)."""
     torch = _torch()
@@ -798,28 +835,8 @@ class Context:
         (h, w, 3) and mask (h, w, uint8) are optional outputs.  Asynchronous on `stream` (torch's current one by default).
         -> the workspace, an int32 tensor: ws[0] is the number of listed pixels, ws[1:1 + ws[0]] their indices y * w + x."""
         torch = _torch()
-        h, w = params.frame_height, params.frame_width
-        for name, t, dtype, shape in (("sum", sum, torch.float64, (h, w, 3)), ("stats", stats, torch.float64, (h, w, 2)),
-                                      ("count", count, torch.int32, (h, w)), ("mean", mean, torch.float64, (h, w, 3)),
-                                      ("rgb8", rgb8, torch.uint8, (h, w, 3)), ("mask", mask, torch.uint8, (h, w))):
-            if t is None and name in ("mean", "rgb8", "mask"):
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, shape))
-            if t.device.type != "cuda" or t.device.index != self.device:
-                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
-        if mean is not None and mean.data_ptr() == sum.data_ptr():
-            raise ValueError("mean must not be the sum's own tensor")
-        lens = _lens(aperture, focus, n_samples)
-        if isinstance(table, torch.Tensor):
-            if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
-                raise ValueError("table must be a contiguous float64 torch tensor of shape (rows, 4)")
-            if table.device != sum.device:
-                raise ValueError("table must live on %s, not %s" % (sum.device, table.device))
-        else:
-            rows = np.asarray(table)
-            table = torch.from_numpy(_lens_rows(rows, rows.shape[0] if rows.ndim == 2 else 0)).to(sum.device)
-        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples, table.shape[0])
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
         n_lights = 0
         if offsets is not None:
             if isinstance(offsets, torch.Tensor):
@@ -834,12 +851,6 @@ class Context:
                     raise ValueError("offsets must be a finite float64 array of shape (%d, n_lights, 3), got %s" % (table.shape[0], off.shape))
                 offsets = torch.from_numpy(off).to(sum.device)
             n_lights = int(offsets.shape[1])
-        need = self.converge_workspace(params) // 4
-        if workspace is None:
-            workspace = torch.empty((need,), dtype=torch.int32, device=sum.device)
-        elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.shape[0] < need \
-                or not workspace.is_contiguous() or workspace.device != sum.device:
-            raise ValueError("workspace must be a contiguous int32 torch tensor of at least %d words on %s" % (need, sum.device))
         vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
         _lib.check(self.L.rm_accumulate_converging_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), int(table.shape[0]),
@@ -868,6 +879,55 @@ class Context:
                                                host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
                                                host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
                                                C.byref(report), C.byref(timing)), self.ptr)
+        return timing, report
+
+    # ---- converging frames with moving spheres (include/rusty_marcher_amd.h, "converging frames with moving spheres") ----
+    def accumulate_converging_motion_device(self, params, sum, stats, count, aperture, focus, n_samples, table, light_offsets, shape_offsets,
+                                            tolerance, min_samples, max_samples, fresh, mean=None, rgb8=None, mask=None, workspace=None,
+                                            stream=None):
+        """rm_accumulate_converging_motion_device: accumulate_converging_device with a shape offset table as well -- the sample
+        that is row r of the tables sees the sphere that is shape k of the scene at its centre + shape_offsets[r][k], in every
+        hit test, shadow test and normal.  light_offsets: (rows, n_lights, 3), zeros for point lights; shape_offsets:
+        (rows, n_shapes, 3), rows of shapes that are not spheres are not read; `rows` is the table's, at least max_samples.
+        Each a contiguous float64 tensor on the context's device, or an array, which is checked (finite) and copied over;
+        n_lights and n_shapes must be the uploaded scene's.  -> the workspace, as accumulate_converging_device."""
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
+        rows = int(table.shape[0])
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", rows, sum.device)
+        shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", rows, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), int(shape_offsets.shape[1])
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        _lib.check(self.L.rm_accumulate_converging_motion_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), rows,
+                                                                 vp(light_offsets) if n_lights > 0 else None, n_lights,
+                                                                 vp(shape_offsets) if n_shapes > 0 else None, n_shapes, 1 if fresh else 0,
+                                                                 C.byref(frame), C.c_void_p(self._stream(stream))), self.ptr)
+        return workspace
+
+    def render_converging_motion(self, params, velocities, shutter, aperture, focus, n_samples, tolerance, min_samples, max_samples, radii=None,
+                                 restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_converging_motion: render_converging with moving spheres -- the sphere that is shape k of the uploaded scene
+        moves by velocities[k] while the shutter stands open, and every sample sees it at a time of its own.  velocities: one
+        vector (or None) for every shape, zero for what is not a sphere; radii: one radius a light, None for point lights.  The
+        frame is render_converging's own: it begins again when a velocity or the shutter changes or the caller switches between
+        the two ticks, and on everything that begins it again there.  -> (rm_timing, rm_converge_report)."""
+        lens = _lens(aperture, focus, n_samples)
+        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
+        v, shutter = _velocities(velocities), _shutter(shutter)
+        r = _radii(radii) if radii is not None else None
+        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
+        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
+                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        timing, report = _lib.rm_timing(), _lib.rm_converge_report()
+        _lib.check(self.L.rm_render_converging_motion(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
+                                                      r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                      r.shape[0] if r is not None else 0,
+                                                      v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, 1 if restart else 0,
+                                                      host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
+                                                      host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
+                                                      C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
     def primary_hits_device(self, params, out=None, stream=None):

@@ -29,9 +29,10 @@
 // table_rows - n_samples.  With buffers that only these two launches write none of them changes a value; with damaged ones the
 // pixels are unspecified and no address leaves the buffers.
 //
-// The body is text of its own, not rm_accum_body.inc generalised: there the row, the lens point and the lights are hoisted
-// out of the loop over the groups and the divisor is the launch's, and making those per pixel in the shared body would change
-// the kernels of rm_accum.hip and rm_soft.hip (profiles/converge_resource_usage.txt has all three side by side).
+// The shade body is rm_converge_body.inc's, which rm_converge_motion.hip shares (spheres moved as well).  It is text of its own,
+// not rm_accum_body.inc generalised: there the row, the lens point and the lights are hoisted out of the loop over the groups
+// and the divisor is the launch's, and making those per pixel in that body would change the kernels of rm_accum.hip and
+// rm_soft.hip (profiles/converge_resource_usage.txt has all three side by side).
 //
 // Strict flavour, scene in global memory, occluder masks off, contraction off: as rm_accum.hip.
 #define RM_KERNEL_FAST 0
@@ -93,91 +94,13 @@ template <bool BVH, int POW, int STACK, bool OFFSET>
 __global__ __launch_bounds__(64) void rm_converge_shade_t(const double *__restrict__ scene_blob, ConvergeArgs a) {
     __shared__ uint32_t bstack[64];
     __shared__ double sums[64 * 3];
-    const LensArgs &q = a.L;
-    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
-
-    const uint32_t total = q.rows * q.frame_width;                       // (below 2^31: the host checked)
-    const uint32_t listed = min(uniform_u32(a.ws[0]), total);            // read once; held to the frame (the head of the file: a workspace damaged between the launches)
-    const uint32_t ns = q.n_samples, P = 64u / ns;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t slot = lane / ns, s = lane % ns;                      // the lane's list entry within the group, its sample of that pixel
-    const uint32_t words = 3u * q.H.n_lights;
-    const V3 bg = mk(q.bg_x, q.bg_y, q.bg_z);
-    const V3 cam = mk(q.cam_x, q.cam_y, q.cam_z);
-    const bool pinhole = q.aperture == 0.;                               // wave-uniform
-
-    for (uint32_t g = blockIdx.x; (unsigned long long)g * P < listed; g += gridDim.x) {
-        const uint32_t k = g * P + slot;                                 // (g P < listed < 2^31, slot < 64)
-        bool on = (slot < P) & (k < listed);
-        uint32_t pix = on ? a.ws[1u + k] : 0u;
-        on = on & (pix < total);                                         // (the same: an entry that is no pixel is dropped)
-        pix = on ? pix : 0u;
-        const uint32_t n = on ? min(count_of(a, pix), a.last_first) : 0u;   // (the same: a count changed since the select launch stays a row of the table)
-        const uint32_t r = n + s;                                        // the lane's table row, < table_rows in every lane
-        const double *row = q.table + 4u * (size_t)r;
-        V3 orig = mk(0., 0., 0.), dir = mk(0., 0., -1.);                 // (a lane without a sample holds a harmless ray it never casts)
-        if (on) {
-            const double sx = (double)(pix % q.frame_width) + row[0], sy = (double)(pix / q.frame_width) + row[1];
-            const V3 D = sample_direction(q, q.oriented != 0u, sx, sy);
-            if (pinhole) {
-                orig = cam;
-                dir = normalized(D);
-            } else {
-                const double au = q.aperture * row[2], av = q.aperture * row[3];
-                const V3 lens = mk(q.cam_x + ((au * q.cam_rx) + (av * q.cam_ux)), q.cam_y + ((au * q.cam_ry) + (av * q.cam_uy)),
-                                   q.cam_z + ((au * q.cam_rz) + (av * q.cam_uz)));
-                const V3 F = mk(q.cam_x + D.x * q.focus, q.cam_y + D.y * q.focus, q.cam_z + D.z * q.focus);
-                orig = lens;
-                dir = normalized(F - lens);
-            }
-        }
-        V3 acc = bg;
-        if (q.max_depth != 0u) {                                         // wave-uniform
-            if constexpr (OFFSET)
-                acc = radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, OffsetLights{a.offsets + (size_t)r * words});
-            else
-                acc = radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, StoredLights());
-        }
-        sums[lane * 3u] = acc.x; sums[lane * 3u + 1u] = acc.y; sums[lane * 3u + 2u] = acc.z;
-        __syncthreads();
-        if (on & (s == 0u)) {
-            double *sum = a.sum + (size_t)pix * 3u;                      // (pix < rows x frame_width: inside every buffer)
-            double *st = a.stats + (size_t)pix * 2u;
-            double rx, ry, rz, Y, Q;
-            uint32_t t;
-            if (n > 0u) {
-                rx = sum[0]; ry = sum[1]; rz = sum[2];
-                Y = st[0]; Q = st[1];
-                t = 0u;
-            } else {
-                rx = sums[lane * 3u]; ry = sums[lane * 3u + 1u]; rz = sums[lane * 3u + 2u];
-                Y = (rx + ry) + rz;
-                Q = Y * Y;
-                t = 1u;
-            }
-            for (; t < ns; t++) {                                        // table order (lane + t <= 63: lane = slot ns, slot < P)
-                const double cx = sums[(lane + t) * 3u], cy = sums[(lane + t) * 3u + 1u], cz = sums[(lane + t) * 3u + 2u];
-                const double y = (cx + cy) + cz;
-                rx = rx + cx; ry = ry + cy; rz = rz + cz;
-                Y = Y + y;
-                Q = Q + y * y;
-            }
-            sum[0] = rx; sum[1] = ry; sum[2] = rz;
-            st[0] = Y; st[1] = Q;
-            a.count[pix] = n + ns;
-            const double div = (double)(n + ns);                         // (at most 65536: the host checked)
-            const double mx = rx / div, my = ry / div, mz = rz / div;
-            if (a.mean) {
-                double *out = a.mean + (size_t)pix * 3u;
-                out[0] = mx; out[1] = my; out[2] = mz;
-            }
-            if (a.rgb8) {
-                uint8_t *out = a.rgb8 + (size_t)pix * 3u;
-                out[0] = to_byte(mx); out[1] = to_byte(my); out[2] = to_byte(mz);
-            }
-        }
-        __syncthreads();                                                 // the next group's answers overwrite `sums`
-    }
+    const uint32_t words = 3u * a.L.H.n_lights;                          // (r words < table_rows x 3 x n_lights: inside the table)
+    const auto lights_of = [&](uint32_t r) {
+        if constexpr (OFFSET) return OffsetLights{a.offsets + (size_t)r * words};
+        else return StoredLights();
+    };
+    const auto spheres_of = [](uint32_t) { return StoredSpheres(); };
+#include "rm_converge_body.inc"
 }
 
 }  // namespace rmconverge

@@ -28,6 +28,7 @@
 #include "rm_soft.hpp"
 #include "rm_motion.hpp"
 #include "rm_converge.hpp"
+#include "rm_converge_motion.hpp"
 
 using namespace rmdev;
 
@@ -225,7 +226,7 @@ struct rm_ctx {
     // progressive frames (rm_accum_host.inc): made by the first rm_render_progressive
     rm_progressive *progressive = nullptr;
 
-    // converging frames (rm_converge_host.inc): made by the first rm_render_converging; shares nothing with `progressive`
+    // converging frames (rm_converge_host.inc): made by the first rm_render_converging or rm_render_converging_motion; shares nothing with `progressive`
     rm_converging *converging = nullptr;
 
     // post-process scratch
@@ -330,7 +331,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1120,3 +1121,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_soft_host.inc"
 #include "rm_motion_host.inc"
 #include "rm_converge_host.inc"
+#include "rm_converge_motion_host.inc"

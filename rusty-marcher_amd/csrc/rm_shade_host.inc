@@ -1,6 +1,7 @@
 // rm_shade_host.inc -- what the host sides of the shading kernels share: the radiance queries (rm_radiance_host.inc), adaptive
 // anti-aliasing (rm_refine_host.inc), the thin-lens camera (rm_lens_host.inc), progressive frames (rm_accum_host.inc), area
-// lights (rm_soft_host.inc), moving spheres (rm_motion_host.inc) and converging frames (rm_converge_host.inc).  Included at the end of rm_device.hip in front of them,
+// lights (rm_soft_host.inc), moving spheres (rm_motion_host.inc), converging frames (rm_converge_host.inc) and converging frames with
+// moving spheres (rm_converge_motion_host.inc).  Included at the end of rm_device.hip in front of them,
 // behind rm_query_host.inc whose check of the params it uses.
 //
 // One launch path (launch_shading): the variant and the grid are rm_plan.cpp's arithmetic (rm_shading_variant_of,

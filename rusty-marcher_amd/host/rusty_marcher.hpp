@@ -512,6 +512,32 @@ struct Renderer {
             }
         return last_report;
     }
+    // render_converging with moving spheres (rm_render_converging_motion): shape k of the scene, a sphere, moves by velocities[k] --
+    // one vector a shape, zero for what is not a sphere -- while the shutter stands open for `shutter`, and every sample sees it at
+    // a time of its own; only the pixels still noisy, the blurred band among them, go on being sampled.  The frame is
+    // render_converging's own: beyond what begins it again there, a changed velocity or shutter does, and so does a switch between
+    // the two calls.  Every ray of such a frame tests every primitive: a hierarchy holds for spheres that stand still.
+    rm_converge_report render_converging_motion(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const std::vector<Vec3f> &velocities,
+                                                double shutter, const rm_converge &converge, uint32_t n_samples,
+                                                const std::vector<double> &radii = {}, double aperture = 0., double focus = 1.,
+                                                bool restart = false) {
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        std::vector<rm_vec3> v;
+        for (const Vec3f &e : velocities) v.push_back(e.c());
+        check(rm_render_converging_motion(ctx_, &p, &lens, &converge, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), v.data(),
+                                          (uint32_t)v.size(), shutter, restart ? 1 : 0, flat.data(), nullptr, &last_report, &last_timing),
+              ctx_);
+        last_samples = last_report.max_count;
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return last_report;
+    }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
     void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }

@@ -24,7 +24,7 @@ class Renderer:
         self.last_timing = None
         self.last_refined = None                                           # render_antialiased: pixels it refined
         self.last_samples = None                                           # render_progressive: samples a pixel in its frame
-        self.last_report = None                                            # render_converging: the last tick's rm_converge_report
+        self.last_report = None                                            # render_converging, render_converging_motion: the last tick's rm_converge_report
 
     def render(self, frame, scene):
         t0 = time.perf_counter()
@@ -229,6 +229,41 @@ class Renderer:
         report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus, restart=True)
         while report.listed > 0:
             report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus)
+        return report
+
+    def render_converging_motion(self, frame, scene, velocities, shutter, tolerance, n_samples, min_samples=16, max_samples=1024,
+                                 light_radii=None, aperture=0., focus=1., restart=False):
+        """render_converging with moving spheres (rm_render_converging_motion): shape k of the scene, a sphere, moves by
+        velocities[k] -- one Vec3f or None a shape, None or zero for what is not a sphere -- while the shutter stands open for
+        `shutter`, and every sample sees it at a time of its own; only the pixels still noisy, the blurred band among them, go on
+        being sampled.  The frame is render_converging's own: beyond what begins it again there, a changed velocity or shutter
+        does, and so does a switch between the two calls.  Every ray of such a frame tests every primitive: a hierarchy holds
+        for spheres that stand still.  Returns the tick's report, as render_converging does."""
+        backend._converge(tolerance, min_samples, max_samples, backend._lens(aperture, focus, n_samples).n_samples)
+        v = backend._velocities(velocities, len(scene.shapes))
+        backend._shutter(shutter)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        got = []
+
+        def call(ctx, p):
+            timing, report = ctx.render_converging_motion(p, v, shutter, aperture, focus, n_samples, tolerance, min_samples, max_samples, radii,
+                                                          restart, host_rgb=frame.buffer)
+            got.append(report)
+            return timing, report.max_count
+
+        self._tick(frame, scene, call)
+        self.last_report = got[0]
+        return got[0]
+
+    def render_converged_motion(self, frame, scene, velocities, shutter, tolerance, n_samples, min_samples=16, max_samples=1024,
+                                light_radii=None, aperture=0., focus=1.):
+        """A finished picture with motion blur: a restarted render_converging_motion ticked until a tick lists nothing.
+        -> the last tick's report."""
+        report = self.render_converging_motion(frame, scene, velocities, shutter, tolerance, n_samples, min_samples, max_samples, light_radii,
+                                               aperture, focus, restart=True)
+        while report.listed > 0:
+            report = self.render_converging_motion(frame, scene, velocities, shutter, tolerance, n_samples, min_samples, max_samples, light_radii,
+                                                   aperture, focus)
         return report
 
     def _tick(self, frame, scene, call):

@@ -313,6 +313,8 @@ extern "C" {
     fn rm_converge_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
     fn rm_accumulate_converging_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_offsets: *const c_void, n_lights: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_render_converging(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
+    fn rm_accumulate_converging_motion_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_converging_motion(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -899,6 +901,99 @@ impl Gpu {
         check(
             unsafe {
                 rm_accumulate_converging_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_offsets, n_lights, if fresh { 1 } else { 0 }, &buffers, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// `render_converging` with moving spheres: shape k of the scene, a sphere, moves by `velocities[k]` -- one vector a shape,
+    /// zero for what is not a sphere -- while the shutter stands open for `shutter`, and every sample sees it at a time of its
+    /// own; only the pixels still noisy, the blurred band among them, go on being sampled.  The frame is `render_converging`'s
+    /// own: beyond what begins it again there, a changed velocity or shutter does, and so does a switch between the two calls.
+    /// Every ray of such a frame tests every primitive: a hierarchy holds for spheres that stand still.
+    pub fn render_converging_motion(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        converge: RmConverge,
+        radii: Option<&[f64]>,
+        velocities: &[Vec3f],
+        shutter: f64,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, RmConvergeReport) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let v: Vec<RmVec3> = velocities.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect();
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut report = RmConvergeReport::default();
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_converging_motion(self.ctx, &p, &lens, &converge, radii_ptr, n_lights, v.as_ptr(), v.len() as u32, shutter, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut report, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), report)
+    }
+
+    /// The device call under `render_converging_motion`: `accumulate_converging` with `device_shape_offsets`, `table_rows` x
+    /// `n_shapes` x 3 f64 -- rows of `motion_sequence`, or any offsets of the caller's making -- that move the sphere that is
+    /// shape k for the sample that is row r of the tables.  `n_lights` and `n_shapes` are the resident scene's; a caller with
+    /// point lights passes zeros.
+    pub fn accumulate_converging_motion(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_motion_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, if fresh { 1 } else { 0 }, &buffers, hip_stream)
             },
             self.ctx,
         );
