@@ -139,6 +139,28 @@ def _shutter(shutter):
     return float(shutter)
 
 
+def _sequence_rows(first, count):
+    """first and count of a sequence call: non-negative integers with first + count <= RM_PROGRESSIVE_MAX_SAMPLES."""
+    for name, v in (("first", first), ("count", count)):
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+    if first + count > PROGRESSIVE_MAX_SAMPLES:
+        raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+    return int(first), int(count)
+
+
+def _host_outputs(params, host_rgb, host_rgb8):
+    """The two optional host outputs of a tick, each a C-contiguous array that holds the frame's whole patch rows
+    -> their pointers (None where not given)."""
+    need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
+    out = []
+    for name, a, dtype, ctype in (("host_rgb", host_rgb, np.float64, C.c_double), ("host_rgb8", host_rgb8, np.uint8, C.c_uint8)):
+        if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
+            raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        out.append(a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None)
+    return out
+
+
 def _offset_tensor(offsets, name, what, n_samples, device):
     """A light or shape offset table as a contiguous float64 tensor (n_samples, n, 3) on `device`: a tensor is checked, an array is
     checked (finite) and copied over."""
@@ -657,11 +679,7 @@ class Context:
     def lens_sequence(self, first, count):
         """rm_lens_sequence: rows first .. first + count - 1 of the library's unbounded sample sequence, (count, 4) float64 rows
         (dx, dy, u, v); every prefix is well spread.  Host arithmetic: needs neither a context nor a GPU."""
-        for name, v in (("first", first), ("count", count)):
-            if isinstance(v, bool) or int(v) != v or v < 0:
-                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
-        if first + count > PROGRESSIVE_MAX_SAMPLES:
-            raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+        first, count = _sequence_rows(first, count)
         t = np.zeros((int(count), 4), dtype=np.float64)
         _lib.check(self.L.rm_lens_sequence(int(first), int(count), t.ctypes.data_as(C.POINTER(C.c_double))), None)
         return t
@@ -685,15 +703,10 @@ class Context:
         copied into host_rgb (float64) and its display bytes into host_rgb8 (uint8) where given: C-contiguous arrays that hold
         the frame's whole patch rows.  -> (rm_timing, samples a pixel in the frame now)."""
         lens = _lens(aperture, focus, n_samples)
-        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
-        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
-            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
-                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        host = _host_outputs(params, host_rgb, host_rgb8)
         timing, total = _lib.rm_timing(), C.c_uint32(0)
         _lib.check(self.L.rm_render_progressive(self.ptr, C.byref(params), C.byref(lens), 1 if restart else 0,
-                                                host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
-                                                host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
-                                                C.byref(total), C.byref(timing)), self.ptr)
+                                                *host, C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
     # ---- area lights (include/rusty_marcher_amd.h, "area lights") ----
@@ -701,11 +714,7 @@ class Context:
         """rm_light_sequence: rows first .. first + count - 1 of the library's light offset sequence for lights of the radii
         `radii`, (count, len(radii), 3) float64: row s moves light l to a point of the sphere of radius radii[l] about its
         position.  Host arithmetic: needs neither a context nor a GPU."""
-        for name, v in (("first", first), ("count", count)):
-            if isinstance(v, bool) or int(v) != v or v < 0:
-                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
-        if first + count > PROGRESSIVE_MAX_SAMPLES:
-            raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+        first, count = _sequence_rows(first, count)
         r = _radii(radii)
         off = np.zeros((int(count), r.shape[0], 3), dtype=np.float64)
         _lib.check(self.L.rm_light_sequence(int(first), int(count), r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0],
@@ -717,19 +726,8 @@ class Context:
         position + offsets[s][l].  offsets: a contiguous float64 tensor (n_samples, n_lights, 3) on the context's device, or
         an array, which is checked (finite) and copied over; n_lights must be the uploaded scene's.
         -> (the table's tensor, the offsets' tensor)."""
-        torch = _torch()
         lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
-        if isinstance(offsets, torch.Tensor):
-            if offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != lens.n_samples or offsets.shape[2] != 3 \
-                    or not offsets.is_contiguous():
-                raise ValueError("offsets must be a contiguous float64 torch tensor of shape (%d, n_lights, 3)" % lens.n_samples)
-            if offsets.device != sum.device:
-                raise ValueError("offsets must live on %s, not %s" % (sum.device, offsets.device))
-        else:
-            off = np.ascontiguousarray(offsets, dtype=np.float64)
-            if off.ndim != 3 or off.shape[0] != lens.n_samples or off.shape[2] != 3 or not np.isfinite(off).all():
-                raise ValueError("offsets must be a finite float64 array of shape (%d, n_lights, 3), got %s" % (lens.n_samples, off.shape))
-            offsets = torch.from_numpy(off).to(sum.device)
+        offsets = _offset_tensor(offsets, "offsets", "n_lights", lens.n_samples, sum.device)
         n_lights = int(offsets.shape[1])
         _lib.check(self.L.rm_accumulate_soft_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
                                                     C.c_void_p(offsets.data_ptr()) if n_lights > 0 else None, n_lights, int(n_before),
@@ -745,16 +743,11 @@ class Context:
         -> (rm_timing, samples a pixel in the frame now)."""
         lens = _lens(aperture, focus, n_samples)
         r = _radii(radii)
-        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
-        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
-            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
-                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        host = _host_outputs(params, host_rgb, host_rgb8)
         timing, total = _lib.rm_timing(), C.c_uint32(0)
         _lib.check(self.L.rm_render_progressive_soft(self.ptr, C.byref(params), C.byref(lens), r.ctypes.data_as(C.POINTER(C.c_double)),
                                                      r.shape[0], 1 if restart else 0,
-                                                     host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
-                                                     host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
-                                                     C.byref(total), C.byref(timing)), self.ptr)
+                                                     *host, C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
     # ---- moving spheres (include/rusty_marcher_amd.h, "moving spheres") ----
@@ -762,11 +755,7 @@ class Context:
         """rm_motion_sequence: rows first .. first + count - 1 of the library's shape offset sequence for shapes of the velocities
         `velocities` and a shutter open for `shutter`, (count, len(velocities), 3) float64: row s moves shape k by velocities[k]
         times the row's time within the shutter.  Host arithmetic: needs neither a context nor a GPU."""
-        for name, v in (("first", first), ("count", count)):
-            if isinstance(v, bool) or int(v) != v or v < 0:
-                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
-        if first + count > PROGRESSIVE_MAX_SAMPLES:
-            raise ValueError("first + count must be at most %d, got %d + %d" % (PROGRESSIVE_MAX_SAMPLES, first, count))
+        first, count = _sequence_rows(first, count)
         v, shutter = _velocities(velocities), _shutter(shutter)
         off = np.zeros((int(count), v.shape[0], 3), dtype=np.float64)
         _lib.check(self.L.rm_motion_sequence(int(first), int(count), v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter,
@@ -803,18 +792,13 @@ class Context:
         lens = _lens(aperture, focus, n_samples)
         v, shutter = _velocities(velocities), _shutter(shutter)
         r = _radii(radii) if radii is not None else None
-        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
-        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
-            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
-                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        host = _host_outputs(params, host_rgb, host_rgb8)
         timing, total = _lib.rm_timing(), C.c_uint32(0)
         _lib.check(self.L.rm_render_progressive_motion(self.ptr, C.byref(params), C.byref(lens),
                                                        r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
                                                        r.shape[0] if r is not None else 0,
                                                        v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, 1 if restart else 0,
-                                                       host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
-                                                       host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
-                                                       C.byref(total), C.byref(timing)), self.ptr)
+                                                       *host, C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
     # ---- converging frames (include/rusty_marcher_amd.h, "converging frames") ----
@@ -834,22 +818,11 @@ class Context:
         which is checked and copied over; offsets: optionally as many rows of light_sequence, (rows, n_lights, 3).  mean, rgb8
         (h, w, 3) and mask (h, w, uint8) are optional outputs.  Asynchronous on `stream` (torch's current one by default).
         -> the workspace, an int32 tensor: ws[0] is the number of listed pixels, ws[1:1 + ws[0]] their indices y * w + x."""
-        torch = _torch()
         lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
                                                         max_samples, mean, rgb8, mask, workspace)
         n_lights = 0
         if offsets is not None:
-            if isinstance(offsets, torch.Tensor):
-                if offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != table.shape[0] or offsets.shape[2] != 3 \
-                        or not offsets.is_contiguous():
-                    raise ValueError("offsets must be a contiguous float64 torch tensor of shape (%d, n_lights, 3)" % table.shape[0])
-                if offsets.device != sum.device:
-                    raise ValueError("offsets must live on %s, not %s" % (sum.device, offsets.device))
-            else:
-                off = np.ascontiguousarray(offsets, dtype=np.float64)
-                if off.ndim != 3 or off.shape[0] != table.shape[0] or off.shape[2] != 3 or not np.isfinite(off).all():
-                    raise ValueError("offsets must be a finite float64 array of shape (%d, n_lights, 3), got %s" % (table.shape[0], off.shape))
-                offsets = torch.from_numpy(off).to(sum.device)
+            offsets = _offset_tensor(offsets, "offsets", "n_lights", int(table.shape[0]), sum.device)
             n_lights = int(offsets.shape[1])
         vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
@@ -868,17 +841,12 @@ class Context:
         lens = _lens(aperture, focus, n_samples)
         conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
         r = _radii(radii) if radii is not None else None
-        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
-        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
-            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
-                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        host = _host_outputs(params, host_rgb, host_rgb8)
         timing, report = _lib.rm_timing(), _lib.rm_converge_report()
         _lib.check(self.L.rm_render_converging(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
                                                r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
                                                r.shape[0] if r is not None else 0, 1 if restart else 0,
-                                               host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
-                                               host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
-                                               C.byref(report), C.byref(timing)), self.ptr)
+                                               *host, C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
     # ---- converging frames with moving spheres (include/rusty_marcher_amd.h, "converging frames with moving spheres") ----
@@ -916,18 +884,13 @@ class Context:
         conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
         v, shutter = _velocities(velocities), _shutter(shutter)
         r = _radii(radii) if radii is not None else None
-        need = (params.frame_height - params.frame_height % 32) * params.frame_width * 3
-        for name, a, dtype in (("host_rgb", host_rgb, np.float64), ("host_rgb8", host_rgb8, np.uint8)):
-            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.size < need):
-                raise ValueError("%s must be a C-contiguous %s array that holds the frame's whole patch rows" % (name, np.dtype(dtype).name))
+        host = _host_outputs(params, host_rgb, host_rgb8)
         timing, report = _lib.rm_timing(), _lib.rm_converge_report()
         _lib.check(self.L.rm_render_converging_motion(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
                                                       r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
                                                       r.shape[0] if r is not None else 0,
                                                       v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, 1 if restart else 0,
-                                                      host_rgb.ctypes.data_as(C.POINTER(C.c_double)) if host_rgb is not None else None,
-                                                      host_rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if host_rgb8 is not None else None,
-                                                      C.byref(report), C.byref(timing)), self.ptr)
+                                                      *host, C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
     def primary_hits_device(self, params, out=None, stream=None):

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <new>
 #include <string>
@@ -20,6 +21,7 @@
 #include "rm_internal.h"
 #include "rm_kernel_args.hpp"
 #include "rm_plan.hpp"
+#include "rm_sampling.hpp"
 #include "rm_query.hpp"
 #include "rm_radiance.hpp"
 #include "rm_refine.hpp"
@@ -120,8 +122,8 @@ struct rm_feedback {
 };
 
 struct rm_hostio;   // rm_hostio.inc: staging buffer, row-scatter threads, display frame
-struct rm_progressive;   // rm_accum_host.inc: staged table, sum, mean and bytes of rm_render_progressive, its count and key
-struct rm_converging;    // rm_converge_host.inc: the buffers, resident sequences, pass total and key of rm_render_converging
+struct rm_progressive;   // rm_motion_host.inc: staged tables, sum, mean and bytes of rm_render_progressive*, its count and frame identity
+struct rm_converging;    // rm_converge_motion_host.inc: the buffers, resident sequences, pass total and frame identity of rm_render_converging*
 
 // The classification's output for the render launches on one stream: a mask per tile.  (Launches on a
 // stream are ordered: a render launch reads what the classification launch in front of it wrote, and the
@@ -223,10 +225,10 @@ struct rm_ctx {
     void *d_lens_frame = nullptr;
     size_t lens_frame_bytes = 0;
 
-    // progressive frames (rm_accum_host.inc): made by the first rm_render_progressive
+    // progressive frames (rm_motion_host.inc): made by the first rm_render_progressive, _soft or _motion
     rm_progressive *progressive = nullptr;
 
-    // converging frames (rm_converge_host.inc): made by the first rm_render_converging or rm_render_converging_motion; shares nothing with `progressive`
+    // converging frames (rm_converge_motion_host.inc): made by the first rm_render_converging or rm_render_converging_motion; shares nothing with `progressive`
     rm_converging *converging = nullptr;
 
     // post-process scratch

@@ -1,129 +1,149 @@
-// rm_motion_host.inc -- host side of the moving spheres (include/rusty_marcher_amd.h, "moving spheres"); included at the end of
-// rm_device.hip, behind rm_soft_host.inc whose checks (check_soft_lights, and through it check_accum_device) it shares, and
-// rm_accum_host.inc whose sequence arithmetic (radical_inverse) and tick (rm_render_progressive_impl, which stages the three
-// slices and calls launch_motion below) it shares.  The kernel is rm_motion.hip's.
+// rm_motion_host.inc -- host side of the moving spheres (include/rusty_marcher_amd.h, "moving spheres") and, behind all three
+// launches it can end in, the tick of the progressive frames, the area lights and the moving spheres; included at the end of
+// rm_device.hip, behind rm_accum_host.inc whose checks (check_accum, check_accum_device, check_offset_tables, check_rules) and
+// argument block (accum_call, accum_args) and rm_soft_host.inc whose launch (launch_soft) it uses.  The kernel is rm_motion.hip's.
 //
 // rm_accumulate_motion_device touches no render state and keeps none of its own: one launch on the caller's stream, nothing
-// waited for.  rm_render_progressive_motion is rm_render_progressive_soft with the velocities and the shutter in the frame's key.
+// waited for.  rm_render_progressive is a launch on the context's stream with a staged slice of rm_lens_sequence and three
+// buffers the context owns (sum, mean, bytes: not the resident frame, not the lens frame), the count of samples in the sum and
+// the identity of the frame the sum belongs to (rm_sampling.hpp).  rm_render_progressive_soft is that with radii in the rules
+// and a slice of rm_light_sequence staged, rm_render_progressive_motion with velocities and a shutter as well and a slice of
+// rm_motion_sequence: which tables a tick stages is rm_staging_of's rule.
 
-// The shape list of the resident scene: the description's first array, kept by the upload (rm_ctx::desc_bytes)
-static uint32_t resident_shape_count(const rm_ctx *ctx) { return (uint32_t)(ctx->desc_sizes[0] / sizeof(rm_shape_ref)); }
-
-static rm_shape_ref resident_shape(const rm_ctx *ctx, uint32_t k) {
-    rm_shape_ref r;
-    std::memcpy(&r, ctx->desc_bytes.data() + (size_t)k * sizeof(rm_shape_ref), sizeof r);
-    return r;
-}
-
-// n_shapes of a motion call: the resident scene's
-static rm_status check_motion_shapes(rm_ctx *ctx, const char *who, uint32_t n_shapes) {
-    if (n_shapes != resident_shape_count(ctx)) {
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "%s: n_shapes %u, the resident scene has %u", who, n_shapes, resident_shape_count(ctx));
-        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
-    }
-    return RM_OK;
-}
-
-// Velocities are finite and the shutter is a finite number >= 0 (a NaN fails the comparison); ctx may be NULL (rm_motion_sequence
-// has none)
-static rm_status check_velocities(rm_ctx *ctx, const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter) {
-    if (n_shapes > 0u && !velocities) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL velocities");
-    for (uint32_t k = 0; k < n_shapes; k++)
-        if (!finite3(velocities[k])) {
-            char buf[192];
-            std::snprintf(buf, sizeof buf, "%s: velocities[%u] = (%g, %g, %g) is not finite", who, k, velocities[k].x, velocities[k].y, velocities[k].z);
-            return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
-        }
-    if (!std::isfinite(shutter) || !(shutter >= 0.)) {
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "%s: shutter = %g is not a finite number >= 0", who, shutter);
-        return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
-    }
-    return RM_OK;
-}
-
-// What the tick checks of its velocities (behind check_accum: a scene is resident): the count, the numbers, and that only spheres move
-static rm_status check_motion_tick(rm_ctx *ctx, const char *who, const rm_motion_tick &m) {
-    if (rm_status sst = check_motion_shapes(ctx, who, m.n_shapes)) return sst;
-    if (rm_status vst = check_velocities(ctx, who, m.velocities, m.n_shapes, m.shutter)) return vst;
-    for (uint32_t k = 0; k < m.n_shapes; k++) {
-        const rm_vec3 &v = m.velocities[k];
-        if (resident_shape(ctx, k).kind != RM_SHAPE_SPHERE && (v.x != 0. || v.y != 0. || v.z != 0.)) {
-            char buf[192];
-            std::snprintf(buf, sizeof buf, "%s: velocities[%u] is not zero and shape %u is not a sphere (only spheres move)", who, k, k);
-            return ctx_fail(ctx, RM_ERR_INVALID_ARG, buf);
-        }
-    }
-    return RM_OK;
-}
-
-// The launch on `stream`; everything was checked, rows > 0.  offsets: NULL where the scene has no lights; shape_offsets: NULL
-// where it has no spheres.
-static rm_status launch_motion(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *table, const void *offsets,
-                               const void *shape_offsets, uint32_t n_before, void *sum, void *mean, void *rgb8, hipStream_t stream) {
+// The launch; offsets: NULL where the scene has no lights; shape_offsets: NULL where it has no spheres.
+static rm_status launch_motion(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets) {
     MotionArgs a{};
-    a.S.A.L = lens_args(ctx, p, lens, table, nullptr);
-    a.S.A.n_before = n_before;
-    a.S.A.sum = static_cast<double *>(sum);
-    a.S.A.mean = static_cast<double *>(mean);
-    a.S.A.rgb8 = static_cast<uint8_t *>(rgb8);
+    a.S.A = accum_args(ctx, c);
     a.S.offsets = static_cast<const double *>(offsets);
     a.shape_offsets = static_cast<const double *>(shape_offsets);
     a.pid_map = ctx->d_pid_map;
     a.n_shapes = resident_shape_count(ctx);
-    return launch_shading(ctx, shade_family{"moving spheres", rm_motion_kernel}, a.S.A.L.max_depth, lens_extent(ctx, a.S.A.L), a, stream);
+    return launch_shading(ctx, shade_family{"moving spheres", rm_motion_kernel}, a.S.A.L.max_depth, lens_extent(ctx, a.S.A.L), a, c.stream);
 }
 
-static rm_status rm_accumulate_motion_device_impl(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table,
-                                                  const void *device_light_offsets, uint32_t n_lights, const void *device_shape_offsets,
-                                                  uint32_t n_shapes, uint32_t n_before, void *device_sum, void *device_mean,
-                                                  void *device_rgb8, void *hip_stream) {
-    const char *who = "rm_accumulate_motion_device";
+// A staged slice of an offset sequence: host side and device side, grown on demand
+struct rm_staged_slice {
+    std::vector<double> host;
+    void *d = nullptr;
+    size_t bytes = 0;                        // d has room for that many
+};
+
+// The progressive state of a context (rm_ctx::progressive; made on the first call, released by rm_destroy)
+struct rm_progressive {
+    void *d_table = nullptr;                 // RM_LENS_MAX_SAMPLES rows
+    void *d_sum = nullptr, *d_mean = nullptr, *d_rgb8 = nullptr;
+    size_t pixels = 0;                       // the three buffers have room for that many
+    double table[RM_LENS_MAX_SAMPLES * 4u];  // the slice as staged
+    bool have_key = false;                   // a call has succeeded, and nothing failed half-way since
+    rm_frame_identity id;                    // the frame the sum belongs to
+    uint32_t n = 0;                          // samples a pixel in the sum
+    rm_staged_slice lights, shapes;          // the slices of rm_light_sequence (or zeros) and of rm_motion_sequence
+};
+
+static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
+    rm_progressive *g = ctx->progressive;
+    if (!g) return;
+    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->lights.d, g->shapes.d})
+        if (b && device_ok) (void)hipFree(b);
+    delete g;
+    ctx->progressive = nullptr;
+}
+
+// `doubles` doubles of fill(out) into the slice and on their way to the device, on the context's stream; 0: nothing is staged
+template <class FILL>
+static rm_status stage_slice(rm_ctx *ctx, rm_staged_slice &s, size_t doubles, FILL fill) {
+    if (doubles == 0u) return RM_OK;
+    if (rm_status gst = grow_device_buffer(ctx, &s.d, &s.bytes, doubles * sizeof(double))) return gst;
+    s.host.resize(doubles);
+    if (rm_status sst = fill(s.host.data())) return sst;
+    RM_HIP(ctx, hipMemcpyAsync(s.d, s.host.data(), doubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return RM_OK;
+}
+
+// The tick of the three calls; `rules` says which: checked here, the tables they ask for staged, the launch by them.
+static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, const rm_sampling_rules &rules,
+                                            int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
-    if (rm_status cst = check_accum_device(ctx, who, p, lens, device_table, n_before, device_sum, device_mean)) return cst;
-    if (rm_status lst = check_soft_lights(ctx, who, n_lights)) return lst;
-    if (n_lights > 0u && !device_light_offsets) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL light offsets");
-    if (rm_status sst = check_motion_shapes(ctx, who, n_shapes)) return sst;
-    const bool has_spheres = ctx->image.H.n_spheres > 0u;
-    if (has_spheres && !device_shape_offsets) return ctx_fail(ctx, RM_ERR_INVALID_ARG, std::string(who) + ": NULL shape offsets");
-    if (refine_rows(p) == 0u) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_motion(ctx, p, lens, device_table, n_lights > 0u ? device_light_offsets : nullptr,
-                         has_spheres ? device_shape_offsets : nullptr, n_before, device_sum, device_mean, device_rgb8, (hipStream_t)hip_stream);
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
+    if (rm_status rst = check_rules(ctx, who, rules)) return rst;
+    const uint32_t rows = refine_rows(p), ns = lens->n_samples;
+    const size_t pixels = (size_t)rows * p->frame_width;
+    double kernel_ms = 0.;
+    if (rows > 0u) {
+        if (!ctx->progressive) ctx->progressive = new rm_progressive();
+        rm_progressive &g = *ctx->progressive;
+        rm_frame_identity id = rm_frame_identity_of(*p, *lens, ctx->camera, ctx->basis, ctx->oriented, ctx->upload_copies, rules);
+        const uint32_t n_before = !restart && g.have_key && rm_same_frame(g.id, id) ? g.n : 0u;
+        const bool saturated = n_before + ns > RM_PROGRESSIVE_MAX_SAMPLES;     // (then n_before > 0: the frame stands)
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        if (!saturated) {
+            g.have_key = false;                                            // (until this call is through)
+            if (!g.d_table) RM_HIP(ctx, hipMalloc(&g.d_table, sizeof g.table));
+            if (rm_status gst = grow_frame_buffers(ctx, &g.pixels, pixels, {{&g.d_sum, pixels * 3u * sizeof(double)},
+                                                                            {&g.d_mean, pixels * 3u * sizeof(double)}, {&g.d_rgb8, pixels * 3u}}))
+                return gst;
+            if (rm_status sst = rm_fill_lens_rows(n_before, ns, g.table)) return sst;
+            RM_HIP(ctx, hipMemcpyAsync(g.d_table, g.table, (size_t)ns * 4u * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            const rm_staging staged = rm_staging_of(RM_TICK_PROGRESSIVE, rules, ctx->image.H.n_lights, ctx->image.H.n_spheres, resident_shape_count(ctx));
+            if (rm_status sst = stage_slice(ctx, g.lights, (size_t)ns * staged.light_columns * 3u,
+                                            [&](double *out) { return rm_fill_light_rows(rules, staged, n_before, ns, out); }))
+                return sst;
+            if (rm_status sst = stage_slice(ctx, g.shapes, (size_t)ns * staged.shape_columns * 3u,
+                                            [&](double *out) { return rm_fill_shape_rows(rules, n_before, ns, out); }))
+                return sst;
+            const accum_call call{p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream};
+            const void *lights = staged.light_columns > 0u ? g.lights.d : nullptr, *shapes = staged.shape_columns > 0u ? g.shapes.d : nullptr;
+            auto launch = [&]() {
+                return rules.motion ? launch_motion(ctx, call, lights, shapes) : rules.soft ? launch_soft(ctx, call, lights) : launch_accum(ctx, call);
+            };
+            if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
+            g.id = std::move(id);
+            g.n = n_before + ns;
+            g.have_key = true;
+        }
+    }
+    const rm_progressive *g = rows > 0u ? ctx->progressive : nullptr;
+    if (rm_status fst = finish_tick(ctx, pixels, g ? g->d_mean : nullptr, g ? g->d_rgb8 : nullptr, host_rgb, host_rgb8, kernel_ms, timing, t_begin))
+        return fst;
+    if (n_total) *n_total = g ? g->n : 0u;
+    return RM_OK;
 }
 
 extern "C" {
 
-rm_status rm_motion_sequence(uint32_t first, uint32_t count, const rm_vec3 *velocities, uint32_t n_shapes, double shutter, double *offsets) {
-    const char *who = "rm_motion_sequence";
-    if ((uint64_t)first + count > RM_PROGRESSIVE_MAX_SAMPLES) {
-        char buf[128];
-        std::snprintf(buf, sizeof buf, "%s: first + count = %u + %u is more than %u", who, first, count, RM_PROGRESSIVE_MAX_SAMPLES);
-        return ctx_fail(nullptr, RM_ERR_INVALID_ARG, buf);
-    }
-    if (count == 0u || n_shapes == 0u) return RM_OK;
-    if (rm_status vst = check_velocities(nullptr, who, velocities, n_shapes, shutter)) return vst;
-    if (!offsets) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL offsets");
-    for (uint32_t k = 0; k < count; k++) {
-        const double t = shutter * radical_inverse(first + k, 17u);      // (row 0: t = 0, the scene as uploaded)
-        for (uint32_t j = 0; j < n_shapes; j++) {
-            double *o = offsets + ((size_t)k * n_shapes + j) * 3u;
-            o[0] = velocities[j].x * t;
-            o[1] = velocities[j].y * t;
-            o[2] = velocities[j].z * t;
-        }
-    }
-    return RM_OK;
-}
-
-rm_status rm_accumulate_motion_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+rm_status rm_accumulate_motion_device(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const void *device_table,
                                       const void *device_light_offsets, uint32_t n_lights, const void *device_shape_offsets,
                                       uint32_t n_shapes, uint32_t n_before, void *device_sum, void *device_mean, void *device_rgb8,
                                       void *hip_stream) {
-    return guarded(ctx, "rm_accumulate_motion_device", [&]() {
-        return rm_accumulate_motion_device_impl(ctx, params, lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes,
-                                                n_before, device_sum, device_mean, device_rgb8, hip_stream);
+    const char *who = "rm_accumulate_motion_device";
+    return guarded(ctx, who, [&]() -> rm_status {
+        if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+        if (rm_status cst = check_accum_device(ctx, who, p, lens, device_table, n_before, device_sum, device_mean)) return cst;
+        const shape_table shapes{device_shape_offsets, n_shapes};
+        if (rm_status ost = check_offset_tables(ctx, who, "light offsets", device_light_offsets, n_lights, &shapes)) return ost;
+        if (refine_rows(p) == 0u) return RM_OK;
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        return launch_motion(ctx, accum_call{p, lens, device_table, n_before, device_sum, device_mean, device_rgb8, (hipStream_t)hip_stream},
+                             n_lights > 0u ? device_light_offsets : nullptr, ctx->image.H.n_spheres > 0u ? device_shape_offsets : nullptr);
+    });
+}
+
+rm_status rm_render_progressive(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, int restart, double *host_rgb, uint8_t *host_rgb8,
+                                uint32_t *n_total, rm_timing *timing) {
+    return guarded(ctx, "rm_render_progressive", [&]() {
+        return rm_render_progressive_impl(ctx, "rm_render_progressive", params, lens, rm_sampling_rules{}, restart, host_rgb, host_rgb8, n_total, timing);
+    });
+}
+
+rm_status rm_render_progressive_soft(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *radii, uint32_t n_lights,
+                                     int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
+    return guarded(ctx, "rm_render_progressive_soft", [&]() {
+        rm_sampling_rules rules;
+        rules.soft = true;                                               // (NULL radii are no point lights here: refused where the scene has lights)
+        rules.radii = radii;
+        rules.n_lights = n_lights;
+        return rm_render_progressive_impl(ctx, "rm_render_progressive_soft", params, lens, rules, restart, host_rgb, host_rgb8, n_total, timing);
     });
 }
 
@@ -131,10 +151,9 @@ rm_status rm_render_progressive_motion(rm_ctx *ctx, const rm_params *params, con
                                        const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart, double *host_rgb,
                                        uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
     return guarded(ctx, "rm_render_progressive_motion", [&]() {
-        const rm_motion_tick motion{velocities, n_shapes, shutter};
-        const bool soft = radii != nullptr;                              // (NULL: point lights, n_lights is not looked at)
-        return rm_render_progressive_impl(ctx, "rm_render_progressive_motion", params, lens, soft, radii, soft ? n_lights : 0u, restart, host_rgb,
-                                          host_rgb8, n_total, timing, &motion);
+        return rm_render_progressive_impl(ctx, "rm_render_progressive_motion", params, lens,
+                                          rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb, host_rgb8, n_total,
+                                          timing);
     });
 }
 

@@ -7,7 +7,8 @@
 // One launch path (launch_shading): the variant and the grid are rm_plan.cpp's arithmetic (rm_shading_variant_of,
 // rm_shading_grid), the kernel is the family's picker's, the occupancy is asked here and nowhere else.  A family's launcher fills
 // its argument block and calls it.  Beside it the checks every sampled frame passes, the view fields every argument block
-// carries, and the timed launch of the calls that own their buffers.
+// carries, the timed launch of the calls that own their buffers, and what the two ticks (rm_motion_host.inc,
+// rm_converge_motion_host.inc) do alike around theirs: grow their output buffers, copy mean and bytes back.
 
 // The rows a render writes, and so a sampled frame covers (renderer.rs:53: the bottom frame_height % 32 rows are never rendered)
 static uint32_t refine_rows(const rm_params *p) { return p->frame_height - p->frame_height % RM_PATCH_SIZE; }
@@ -116,4 +117,32 @@ static void fill_timing(rm_timing *timing, double kernel_ms, double d2h_ms, std:
     timing->kernel_ms = kernel_ms;
     timing->d2h_ms = d2h_ms;
     timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+}
+
+// Makes the output buffers a tick owns hold `pixels` pixels (*have: what they have room for).  They share one shape, so where
+// one is too small every one is replaced; a failed allocation leaves *have 0.
+static rm_status grow_frame_buffers(rm_ctx *ctx, size_t *have, size_t pixels, std::initializer_list<std::pair<void **, size_t>> buffers) {
+    if (*have >= pixels) return RM_OK;
+    *have = 0;
+    for (const auto &b : buffers) {
+        size_t none = 0;
+        if (rm_status gst = grow_device_buffer(ctx, b.first, &none, b.second)) return gst;
+    }
+    *have = pixels;
+    return RM_OK;
+}
+
+// The tail of a tick: mean and display bytes of `pixels` pixels (0: a frame without a whole patch row, nothing to copy) back to
+// the host where asked, timed, and the timing filled in
+static rm_status finish_tick(rm_ctx *ctx, size_t pixels, const void *d_mean, const void *d_rgb8, double *host_rgb, uint8_t *host_rgb8,
+                             double kernel_ms, rm_timing *timing, std::chrono::steady_clock::time_point t_begin) {
+    double d2h_ms = 0.;
+    if (pixels > 0u) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (host_rgb) RM_HIP(ctx, hipMemcpy(host_rgb, d_mean, pixels * 3u * sizeof(double), hipMemcpyDeviceToHost));
+        if (host_rgb8) RM_HIP(ctx, hipMemcpy(host_rgb8, d_rgb8, pixels * 3u, hipMemcpyDeviceToHost));
+        d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    fill_timing(timing, kernel_ms, d2h_ms, t_begin);
+    return RM_OK;
 }

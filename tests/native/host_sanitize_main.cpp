@@ -2,9 +2,11 @@
 // scene builder, OBJ ingest (good and malformed files), status formatting, the hierarchy
 // builder (csrc/rm_bvh.hpp) and the device image the upload builds from a description, good
 // and bad ones (csrc/rm_image.cpp); and the two decisions of a shading launch (csrc/rm_plan.cpp rm_shading_variant_of,
-// rm_shading_grid) over the cases of tests/test_launch_plan.py.  CPU only.
+// rm_shading_grid) over the cases of tests/test_launch_plan.py; and the sampled frames' host arithmetic (csrc/rm_sampling.cpp):
+// the three sequences, the frame identity and the staging rule.  CPU only.
 #include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -15,6 +17,7 @@
 #include "rm_bvh.hpp"
 #include "rm_image.hpp"
 #include "rm_plan.hpp"
+#include "rm_sampling.hpp"
 
 // the device half (rm_device.hip) is not part of this CPU-only build: its one symbol the
 // host half's callers need is the error accessor
@@ -172,6 +175,160 @@ static void check_shading_plan() {
     assert(rm_shading_grid(0x7fffffffu, 64u, 1 << 20, 1 << 11, 0u) == 0x7fffffffu);
 }
 
+// A call the host arithmetic must refuse: RM_ERR_INVALID_ARG and a text that says what
+template <class CALL>
+static void refused_with(CALL call, const char *word) {
+    rm_set_host_error("");
+    assert(call() == RM_ERR_INVALID_ARG);
+    assert(std::strstr(rm_last_error(nullptr), word) != nullptr);
+}
+
+// The three sequences: a slice is the same rows of the whole, the last row is 65535, nothing is touched for zero counts
+static void check_sequences() {
+    const double radii[2] = {1.5, 0.};
+    const rm_vec3 vel[3] = {{1., -2., 0.5}, {0., 0., 0.}, {-0., 3., 1e-300}};
+    const uint32_t whole = 40u, first = 7u, count = 13u;
+    std::vector<double> lens(whole * 4u), lights(whole * 2u * 3u), shapes(whole * 3u * 3u);
+    assert(rm_lens_sequence(0u, whole, lens.data()) == RM_OK);
+    assert(rm_light_sequence(0u, whole, radii, 2u, lights.data()) == RM_OK);
+    assert(rm_motion_sequence(0u, whole, vel, 3u, 0.75, shapes.data()) == RM_OK);
+    std::vector<double> a(count * 4u), b(count * 2u * 3u), c(count * 3u * 3u);
+    assert(rm_lens_sequence(first, count, a.data()) == RM_OK && std::memcmp(a.data(), &lens[first * 4u], a.size() * sizeof(double)) == 0);
+    assert(rm_light_sequence(first, count, radii, 2u, b.data()) == RM_OK && std::memcmp(b.data(), &lights[first * 6u], b.size() * sizeof(double)) == 0);
+    assert(rm_motion_sequence(first, count, vel, 3u, 0.75, c.data()) == RM_OK && std::memcmp(c.data(), &shapes[first * 9u], c.size() * sizeof(double)) == 0);
+    for (double x : lens) assert(std::isfinite(x));
+    // the range: row 65535 and first + count = 65536 pass, 65537 and a first that would wrap do not
+    const uint32_t most = RM_PROGRESSIVE_MAX_SAMPLES;
+    std::vector<double> tail(6u * 9u);
+    assert(rm_lens_sequence(most - 1u, 1u, tail.data()) == RM_OK && rm_lens_sequence(most - 6u, 6u, tail.data()) == RM_OK);
+    assert(rm_light_sequence(most - 1u, 1u, radii, 2u, tail.data()) == RM_OK && rm_light_sequence(most - 6u, 6u, radii, 2u, tail.data()) == RM_OK);
+    assert(rm_motion_sequence(most - 1u, 1u, vel, 3u, 1., tail.data()) == RM_OK && rm_motion_sequence(most - 6u, 6u, vel, 3u, 1., tail.data()) == RM_OK);
+    const uint32_t beyond[2][2] = {{most - 6u, 7u}, {0xFFFFFFFFu, 1u}};
+    for (const auto &r : beyond) {
+        refused_with([&]() { return rm_lens_sequence(r[0], r[1], tail.data()); }, "rm_lens_sequence: first + count");
+        refused_with([&]() { return rm_light_sequence(r[0], r[1], radii, 2u, tail.data()); }, "rm_light_sequence: first + count");
+        refused_with([&]() { return rm_motion_sequence(r[0], r[1], vel, 3u, 1., tail.data()); }, "rm_motion_sequence: first + count");
+    }
+    // zero counts: no pointer is looked at
+    assert(rm_lens_sequence(0u, 0u, nullptr) == RM_OK && rm_lens_sequence(most, 0u, nullptr) == RM_OK);
+    assert(rm_light_sequence(5u, 0u, nullptr, 2u, nullptr) == RM_OK && rm_light_sequence(5u, 3u, nullptr, 0u, nullptr) == RM_OK);
+    assert(rm_motion_sequence(5u, 0u, nullptr, 3u, NAN, nullptr) == RM_OK && rm_motion_sequence(5u, 3u, nullptr, 0u, NAN, nullptr) == RM_OK);
+    // every other refusal
+    refused_with([&]() { return rm_lens_sequence(0u, 1u, nullptr); }, "NULL table");
+    refused_with([&]() { return rm_light_sequence(0u, 1u, nullptr, 2u, tail.data()); }, "NULL radii");
+    refused_with([&]() { return rm_light_sequence(0u, 1u, radii, 2u, nullptr); }, "NULL offsets");
+    for (double bad : {-1e-300, (double)NAN, (double)INFINITY}) {
+        const double r[2] = {1., bad};
+        refused_with([&]() { return rm_light_sequence(0u, 1u, r, 2u, tail.data()); }, "radii[1]");
+        refused_with([&]() { return rm_motion_sequence(0u, 1u, vel, 3u, bad, tail.data()); }, "shutter");
+    }
+    refused_with([&]() { return rm_motion_sequence(0u, 1u, nullptr, 3u, 1., tail.data()); }, "NULL velocities");
+    refused_with([&]() { return rm_motion_sequence(0u, 1u, vel, 3u, 1., nullptr); }, "NULL offsets");
+    for (int axis = 0; axis < 3; axis++) {
+        rm_vec3 v[3] = {vel[0], vel[1], vel[2]};
+        (axis == 0 ? v[2].x : axis == 1 ? v[2].y : v[2].z) = axis == 1 ? (double)NAN : (double)INFINITY;
+        refused_with([&]() { return rm_motion_sequence(0u, 1u, v, 3u, 1., tail.data()); }, "velocities[2]");
+    }
+}
+
+// The frame identity: equal to itself, unequal after every single change
+static void check_identity() {
+    rm_params p{};
+    p.fov = 1.5; p.half_fov = 0.75; p.height = 32.; p.width = 64.; p.ratio = 2.;
+    p.frame_width = 64u; p.frame_height = 32u; p.max_depth = 3u; p.patch_size = 32u;
+    p.background = rm_vec3{0.1, 0.2, 0.3};
+    const rm_lens lens{0.4, 5., 8u, 0u};
+    const rm_vec3 camera{1., 2., 3.};
+    const rm_camera_basis basis{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
+    const double radii[2] = {1.5, 3.};
+    const rm_vec3 vel[2] = {{1., 0., 0.}, {0., 0., 0.}};
+    rm_sampling_rules rules;
+    rules.soft = true; rules.radii = radii; rules.n_lights = 2u;
+    rules.motion = true; rules.velocities = vel; rules.n_shapes = 2u; rules.shutter = 1.;
+    const rm_frame_identity base = rm_frame_identity_of(p, lens, camera, basis, false, 7u, rules);
+    assert(rm_same_frame(base, base) && rm_same_frame(base, rm_frame_identity_of(p, lens, camera, basis, false, 7u, rules)));
+    assert(base.radii.size() == 2u && base.velocities.size() == 2u);
+    int changes = 0;
+    auto differs = [&](const rm_frame_identity &other) {
+        assert(!rm_same_frame(base, other) && !rm_same_frame(other, base) && rm_same_frame(other, other));
+        changes++;
+    };
+    // every key field: the params', the lens', the camera, the basis, the oriented flag, the upload count
+    double rm_params::*const doubles[] = {&rm_params::fov, &rm_params::half_fov, &rm_params::height, &rm_params::width, &rm_params::ratio};
+    for (auto m : doubles) { rm_params q = p; q.*m += 0.25; differs(rm_frame_identity_of(q, lens, camera, basis, false, 7u, rules)); }
+    uint32_t rm_params::*const words[] = {&rm_params::frame_width, &rm_params::frame_height, &rm_params::max_depth};
+    for (auto m : words) { rm_params q = p; q.*m += 1u; differs(rm_frame_identity_of(q, lens, camera, basis, false, 7u, rules)); }
+    double rm_vec3::*const axes[] = {&rm_vec3::x, &rm_vec3::y, &rm_vec3::z};
+    for (auto m : axes) {
+        rm_params q = p; q.background.*m += 0.5; differs(rm_frame_identity_of(q, lens, camera, basis, false, 7u, rules));
+        rm_vec3 cam = camera; cam.*m += 0.5; differs(rm_frame_identity_of(p, lens, cam, basis, false, 7u, rules));
+        rm_camera_basis t = basis; t.right.*m += 0.5; differs(rm_frame_identity_of(p, lens, camera, t, false, 7u, rules));
+        t = basis; t.up.*m += 0.5; differs(rm_frame_identity_of(p, lens, camera, t, false, 7u, rules));
+        t = basis; t.forward.*m += 0.5; differs(rm_frame_identity_of(p, lens, camera, t, false, 7u, rules));
+    }
+    differs(rm_frame_identity_of(p, rm_lens{0.5, 5., 8u, 0u}, camera, basis, false, 7u, rules));
+    differs(rm_frame_identity_of(p, rm_lens{0.4, 6., 8u, 0u}, camera, basis, false, 7u, rules));
+    differs(rm_frame_identity_of(p, lens, camera, basis, true, 7u, rules));
+    differs(rm_frame_identity_of(p, lens, camera, basis, false, 8u, rules));
+    assert(changes == 8 + 15 + 4);
+    // ... what is not in the key: the samples a tick, the band, the flags
+    rm_params q = p; q.flags = 1u; q.patch_row_begin = 1u;
+    assert(rm_same_frame(base, rm_frame_identity_of(q, rm_lens{0.4, 5., 4u, 0u}, camera, basis, false, 7u, rules)));
+    // the rules: one radius, the radii's count, one velocity component, -0. for 0., the shutter
+    auto with = [&](const rm_sampling_rules &r) { return rm_frame_identity_of(p, lens, camera, basis, false, 7u, r); };
+    const double other_radii[2] = {1.5, 2.};
+    rm_sampling_rules r = rules; r.radii = other_radii; differs(with(r));
+    assert(!rm_same_radii(base, with(r)) && rm_same_radii(base, base));
+    r = rules; r.n_lights = 1u; differs(with(r));
+    for (auto m : axes) {
+        rm_vec3 v[2] = {vel[0], vel[1]};
+        v[1].*m = 1e-300;
+        r = rules; r.velocities = v; differs(with(r));
+        v[1].*m = -0.;
+        r = rules; r.velocities = v; differs(with(r));
+    }
+    r = rules; r.n_shapes = 1u; differs(with(r));
+    r = rules; r.shutter = 0.5; differs(with(r));
+    // "no radii" is not "zero lights' worth of radii", "no velocities" not "velocities of zero" (nor none of them)
+    rm_sampling_rules none, no_lights, still, no_shapes;
+    no_lights.soft = true;
+    const rm_vec3 zero[2] = {{0., 0., 0.}, {0., 0., 0.}};
+    still.motion = true; still.velocities = zero; still.n_shapes = 2u;
+    no_shapes.motion = true;
+    assert(rm_same_frame(with(none), with(none)) && !rm_same_frame(with(none), with(no_lights)) && rm_same_radii(with(none), with(no_lights)));
+    assert(!rm_same_frame(with(none), with(still)) && !rm_same_frame(with(none), with(no_shapes)) && !rm_same_frame(with(still), with(no_shapes)));
+}
+
+// The staging rule: point lights or radii, with and without motion, on scenes with and without lights and spheres
+static void check_staging() {
+    const double radii[2] = {1., 2.};
+    const rm_vec3 vel[5] = {};
+    for (uint32_t scene_lights : {0u, 2u})
+        for (uint32_t scene_spheres : {0u, 3u})
+            for (bool soft : {false, true})
+                for (bool motion : {false, true}) {
+                    const uint32_t scene_shapes = scene_spheres + 2u;  // (two shapes that are not spheres)
+                    rm_sampling_rules r;
+                    if (soft) { r.soft = true; r.radii = radii; r.n_lights = scene_lights; }
+                    if (motion) { r.motion = true; r.velocities = vel; r.n_shapes = scene_shapes; r.shutter = 1.; }
+                    const rm_staging a = rm_staging_of(RM_TICK_PROGRESSIVE, r, scene_lights, scene_spheres, scene_shapes);
+                    const rm_staging c = rm_staging_of(RM_TICK_CONVERGING, r, scene_lights, scene_spheres, scene_shapes);
+                    assert(a.light_columns == (soft || motion ? scene_lights : 0u) && c.light_columns == a.light_columns);
+                    assert(a.light_zeros == (motion && !soft) && c.light_zeros == a.light_zeros);
+                    assert(a.shape_columns == (motion ? scene_shapes : 0u));
+                    assert(c.shape_columns == (motion && scene_spheres > 0u ? scene_shapes : 0u));   // the one difference
+                    // the rows the rule asks for are what the fill functions write: not a double more
+                    std::vector<double> rows(3u * (a.light_columns + a.shape_columns) * 3u + 1u, 7.);
+                    double *end = rows.data() + 3u * a.light_columns * 3u;
+                    if (a.light_columns > 0u) assert(rm_fill_light_rows(r, a, 4u, 3u, rows.data()) == RM_OK);
+                    if (a.shape_columns > 0u) assert(rm_fill_shape_rows(r, 4u, 3u, end) == RM_OK);
+                    assert(rows.back() == 7.);
+                    for (size_t i = 0; i + 1u < rows.size(); i++) assert(rows[i] != 7. && (!a.light_zeros || rows[i] == 0.));
+                }
+    double lens[8];
+    assert(rm_fill_lens_rows(3u, 2u, lens) == RM_OK && lens[0] == 0.75 && lens[4] == 0.125);   // (rows 3 and 4 in base 2)
+}
+
 int main(int argc, char **argv) {
     assert(argc >= 3);
     const std::string cornell = argv[1], tmpdir = argv[2];
@@ -260,6 +417,9 @@ int main(int argc, char **argv) {
     check_hierarchy(1000, 2);
     check_hierarchy(64, 1);
     check_shading_plan();
+    check_sequences();
+    check_identity();
+    check_staging();
     char buf[8];
     assert(rm_format_status(buf, sizeof buf, 92, 1280, 800) > 7);   // truncated, NUL-terminated
     assert(buf[7] == '\0');

@@ -694,3 +694,56 @@ def test_the_tick_through_c_python_and_the_cpp_mirror(pkg, entry, ctx, Y, capsys
     assert [l for l in log.splitlines() if l.split()[0] in ("first", "done", "again", "still")] == \
         ["first 1024 1", "done %d %d %d %d" % (n_passes, cast, top, top), "again 0 %d" % n_passes, "still 1024 1"]
     assert np.fromfile(str(dump)).tobytes() == device[-1]["mean"].tobytes()
+
+
+# ---------------------------------------------------------------- 13. the two ticks beside each other, and a frame begun again
+def motion_ticks(pkg, Y, steps):
+    """The ticks `steps` names -- (kind, params, radii): "p" rm_render_progressive_motion, "c" rm_render_converging_motion with a
+    negative tolerance, so every pixel is listed -- on a context of their own, 4 samples each, none with `restart`
+    -> every tick's host_rgb."""
+    demo = workloads.product_scene(pkg, "demo")
+    v = MR.velocities(Y.kinds("demo"))
+    c = pkg.backend.Context(0)
+    try:
+        c.upload(demo.flatten())
+        out = []
+        for kind, p, radii in steps:
+            host = np.full((p.frame_height, p.frame_width, 3), NAN)
+            if kind == "p":
+                c.render_progressive_motion(p, v, MR.SHUTTER, LR.APERTURE, LR.FOCUS, 4, radii=radii, host_rgb=host)
+            else:
+                rep = c.render_converging_motion(p, v, MR.SHUTTER, LR.APERTURE, LR.FOCUS, 4, -1., 0, 64, radii=radii, host_rgb=host)[1]
+                assert rep.listed == p.frame_height * p.frame_width
+            assert np.isfinite(host).all() and host.any()
+            out.append(host)
+        return out
+    finally:
+        c.close()
+
+
+def test_the_two_motion_ticks_alternating_on_one_context_are_each_kinds_own_frames(pkg, Y):
+    """rm_ctx::progressive and rm_ctx::converging share nothing: three ticks of each, alternating on one context, give byte for
+    byte what the same three ticks give on a context that makes only that kind of call."""
+    p = pkg.backend.make_params(workloads.FOV, 32., 32., 2)
+    mixed = motion_ticks(pkg, Y, [(kind, p, None) for kind in "pcpcpc"])
+    for at, kind in enumerate("pc"):
+        alone = motion_ticks(pkg, Y, [(kind, p, None)] * 3)
+        assert alone[0].tobytes() != alone[2].tobytes()                 # (the frame goes on from tick to tick)
+        for k in range(3):
+            assert mixed[2 * k + at].tobytes() == alone[k].tobytes(), "tick %d of kind %s" % (k + 1, kind)
+
+
+def test_a_converging_frame_begun_again_by_other_radii_or_more_pixels_is_a_fresh_contexts(pkg, Y):
+    """The reset of rm_render_converging_motion's tick where the light table keeps its columns: other radii (the resident
+    prefix of the light sequence is computed again, in the buffer that stands) and then a taller frame (the six buffers are
+    replaced, all three prefixes stay or are computed again).  Each frame begun that way is, tick by tick and byte for byte, a
+    fresh context's."""
+    small = pkg.backend.make_params(workloads.FOV, 32., 32., 2)
+    tall = pkg.backend.make_params(workloads.FOV, 64., 32., 2)
+    frames = [(small, (1.5, 3.)), (small, (1.5, 2.)), (tall, (1.5, 2.))]
+    one = motion_ticks(pkg, Y, [("c", p, radii) for p, radii in frames for _ in range(2)])
+    assert one[1].tobytes() != one[3].tobytes()                         # (the radii are seen)
+    for at, (p, radii) in enumerate(frames[1:], 1):
+        fresh = motion_ticks(pkg, Y, [("c", p, radii)] * 2)
+        for k in range(2):
+            assert one[2 * at + k].tobytes() == fresh[k].tobytes(), "frame %d, tick %d" % (at + 1, k + 1)
