@@ -962,9 +962,10 @@ rm_status rm_render_progressive_soft(rm_ctx *ctx, const rm_params *params, const
  * converges to a picture blurred along the motion.  Additive to ABI version 5; a host detects them
  * by " motion" in rm_build_info().
  *
- * Spheres only.  The reference has no offset for spheres, so one addition per component defines a
- * moved sphere; polygon and triangle records are projected at upload, and moving them would not
- * reproduce the reference's hit / miss decisions bit for bit.
+ * Spheres only in these calls.  The reference has no offset for spheres, so one addition per
+ * component defines a moved sphere.  Polygons and meshes move in the calls of the next section,
+ * "moving shapes": the reference defines their offset itself and the device records hold the very
+ * quantities it moves, so that is bit for bit too; these calls keep refusing such a velocity.
  *
  * A shape offset table is [n_samples][n_shapes][3] doubles in world units, indexed by the shape's
  * index in the scene's shape list: the index rm_scene_offset_shape takes and rm_hit.shape reports.
@@ -1018,6 +1019,59 @@ rm_status rm_accumulate_motion_device(rm_ctx *ctx, const rm_params *params, cons
                                       uint32_t n_shapes, uint32_t n_before, void *device_sum, void *device_mean /* optional */,
                                       void *device_rgb8 /* optional */, void *hip_stream);
 rm_status rm_render_progressive_motion(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                       const double *radii /* NULL: point lights */, uint32_t n_lights,
+                                       const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart,
+                                       double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                       uint32_t *n_total /* optional */, rm_timing *timing /* optional */);
+
+/* ---- moving shapes: motion blur for spheres, polygons and meshes -------------------------------
+ * The moving spheres' calls obey a velocity on a sphere alone.  These obey one on any shape: the
+ * fourth member of the progressive family, beside plain, area lights and moving spheres.  Additive
+ * to ABI version 5; a host detects them by " moving-shapes" in rm_build_info().
+ *
+ * The shape offset table is the moving spheres': [n_samples][n_shapes][3] doubles in the order of
+ * the scene's shape list.  For sample row s and shape k:
+ *   sphere:   as in "moving spheres": C' = C + off[s][k].
+ *   polygon:  plane_point' = plane_point + off[s][k] and every vertex v' = v + off[s][k]
+ *             (polygon.rs:44-49); only x and y of a vertex are ever used (polygon.rs:54-56).  The
+ *             normal and the material are the scene's.
+ *   Obj:      every triangle gets center' = center + off[s][k] and v' = v + off[s][k]
+ *             (triangle.rs:19-24, obj.rs:24-29).  The normals and the per-triangle materials are
+ *             the scene's.
+ * Each is one addition per component, rounded once.  The moved record takes the stored one's place
+ * in everything the sample does with that primitive, at every ray step and for the reflected and
+ * refracted children too: the closest-hit test (a polygon's fifth and further vertices included)
+ * and every shadow test -- where two shadow rays share a walk, the plane numerator they share is
+ * formed from the moved point.  A hit's point is orig + dir * t and its normal the stored one.
+ * The hit tests form (p + off) - orig and (v + off) - a, what the reference forms after offset(),
+ * so a sample is the reference's render of the moved scene operation for operation.
+ *
+ * Rows of every shape are read, so the whole table is a precondition: a non-finite entry gives
+ * non-finite pixels, never a fault.  With every offset +0. or -0. a pass is byte for byte
+ * rm_accumulate_motion_device's for the same tables, for stored coordinates that are not -0.; with
+ * zero rows for every shape that is not a sphere it is byte for byte the moving spheres' pass with
+ * those sphere rows.
+ *
+ * Cost: the moving spheres' -- the flat walk whatever hierarchies the scene image holds, no cull,
+ * no occluder masks, no tile masks -- plus three per-lane loads a shape and walk and one addition
+ * at each use of a coordinate.
+ *
+ * rm_accumulate_moving_device has rm_accumulate_motion_device's argument list and checks, except
+ * that device_shape_offsets must not be NULL when the scene holds any shape.
+ *
+ * rm_render_progressive_moving has rm_render_progressive_motion's argument list and is the same
+ * tick on the same context-owned sum, mean, bytes and count N, with the same checks but for the
+ * refusal of a velocity on a shape that is not a sphere.  Its frames are not the moving spheres':
+ * switching between the two calls begins the frame again, equal velocities or not.  The tables are
+ * rm_lens_sequence's, rm_light_sequence's and rm_motion_sequence's rows [N, N + n_samples).
+ *
+ * Not here: moving shapes in converging frames, rotation or deformation.
+ */
+rm_status rm_accumulate_moving_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                      const void *device_light_offsets, uint32_t n_lights, const void *device_shape_offsets,
+                                      uint32_t n_shapes, uint32_t n_before, void *device_sum, void *device_mean /* optional */,
+                                      void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_render_progressive_moving(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
                                        const double *radii /* NULL: point lights */, uint32_t n_lights,
                                        const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart,
                                        double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,

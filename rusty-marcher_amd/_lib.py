@@ -229,6 +229,10 @@ SIGNATURES = {
                                               _VP, _VP]),
     "rm_render_progressive_motion": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), C.c_uint32, _P(rm_vec3), C.c_uint32,
                                                C.c_double, C.c_int, _P(C.c_double), _P(C.c_uint8), _P(C.c_uint32), _P(rm_timing)]),
+    "rm_accumulate_moving_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP,
+                                              _VP, _VP]),
+    "rm_render_progressive_moving": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), C.c_uint32, _P(rm_vec3), C.c_uint32,
+                                               C.c_double, C.c_int, _P(C.c_double), _P(C.c_uint8), _P(C.c_uint32), _P(rm_timing)]),
     "rm_converge_workspace": (C.c_int, [_P(rm_params), _P(C.c_size_t)]),
     "rm_accumulate_converging_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, C.c_uint32, C.c_int,
                                                   _P(rm_converge_frame), _VP]),

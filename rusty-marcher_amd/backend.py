@@ -801,6 +801,42 @@ class Context:
                                                        *host, C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
+    # ---- moving shapes (include/rusty_marcher_amd.h, "moving shapes") ----
+    def accumulate_moving_device(self, params, sum, aperture, focus, table, light_offsets, shape_offsets, n_before, mean=None, rgb8=None,
+                                 stream=None):
+        """rm_accumulate_moving_device: accumulate_motion_device in which every shape moves -- sample row s sees shape k of the
+        scene, sphere, polygon or mesh, moved by shape_offsets[s][k]: a polygon's plane point and vertices, every triangle's
+        centre and vertices of a mesh, the normals as uploaded.  The rows of every shape are read.  Arguments and result as
+        accumulate_motion_device's."""
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", lens.n_samples, sum.device)
+        shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", lens.n_samples, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), int(shape_offsets.shape[1])
+        _lib.check(self.L.rm_accumulate_moving_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                      C.c_void_p(light_offsets.data_ptr()) if n_lights > 0 else None, n_lights,
+                                                      C.c_void_p(shape_offsets.data_ptr()) if n_shapes > 0 else None, n_shapes, int(n_before),
+                                                      C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                      C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                      C.c_void_p(self._stream(stream))), self.ptr)
+        return table, light_offsets, shape_offsets
+
+    def render_progressive_moving(self, params, velocities, shutter, aperture, focus, n_samples, radii=None, restart=False, host_rgb=None,
+                                  host_rgb8=None):
+        """rm_render_progressive_moving: render_progressive_motion in which a velocity on any shape is obeyed -- spheres,
+        polygons and meshes move by velocities[k] while the shutter stands open.  Its frames are its own: a switch between this
+        call and render_progressive_motion begins the frame again.  -> (rm_timing, samples a pixel in the frame now)."""
+        lens = _lens(aperture, focus, n_samples)
+        v, shutter = _velocities(velocities), _shutter(shutter)
+        r = _radii(radii) if radii is not None else None
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing, total = _lib.rm_timing(), C.c_uint32(0)
+        _lib.check(self.L.rm_render_progressive_moving(self.ptr, C.byref(params), C.byref(lens),
+                                                       r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                       r.shape[0] if r is not None else 0,
+                                                       v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, 1 if restart else 0,
+                                                       *host, C.byref(total), C.byref(timing)), self.ptr)
+        return timing, total.value
+
     # ---- converging frames (include/rusty_marcher_amd.h, "converging frames") ----
     def converge_workspace(self, params):
         """rm_converge_workspace: bytes of device memory the list of accumulate_converging_device needs for `params`."""

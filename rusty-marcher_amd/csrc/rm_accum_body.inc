@@ -1,5 +1,6 @@
 // rm_accum_body.inc -- the body the kernels of the progressive frames share: rm_accum.hip's (lights where the scene image says),
-// rm_soft.hip's (lights moved by the lane's row of an offset table) and rm_motion.hip's (spheres moved as well).  Included
+// rm_soft.hip's (lights moved by the lane's row of an offset table), rm_motion.hip's (spheres moved as well) and
+// rm_motion_shapes.hip's (every shape moved).  Included
 // behind rm_radiance_step.inc.
 //
 // `lights_of(s)`: the rule that says where the lights of table row s stand (rm_trace.inc, StoredLights), asked once a lane

@@ -64,8 +64,8 @@ static rm_status check_offset_tables(rm_ctx *ctx, const char *who, const char *l
 }
 
 // What a tick checks of its sampling rules (behind check_accum: a scene is resident): the counts, the numbers, and that only
-// spheres move
-static rm_status check_rules(rm_ctx *ctx, const char *who, const rm_sampling_rules &r) {
+// spheres move -- but in the moving shapes' tick (any_shape; rm_motion_shapes_host.inc), where every shape may
+static rm_status check_rules(rm_ctx *ctx, const char *who, const rm_sampling_rules &r, bool any_shape = false) {
     if (r.soft) {
         if (rm_status lst = check_soft_lights(ctx, who, r.n_lights)) return lst;
         if (rm_status rst = host_refusal(ctx, rm_check_radii(who, r.radii, r.n_lights))) return rst;
@@ -73,7 +73,7 @@ static rm_status check_rules(rm_ctx *ctx, const char *who, const rm_sampling_rul
     if (!r.motion) return RM_OK;
     if (rm_status sst = check_motion_shapes(ctx, who, r.n_shapes)) return sst;
     if (rm_status vst = host_refusal(ctx, rm_check_velocities(who, r.velocities, r.n_shapes, r.shutter))) return vst;
-    for (uint32_t k = 0; k < r.n_shapes; k++) {
+    for (uint32_t k = 0; k < r.n_shapes && !any_shape; k++) {
         const rm_vec3 &v = r.velocities[k];
         if (resident_shape(ctx, k).kind != RM_SHAPE_SPHERE && (v.x != 0. || v.y != 0. || v.z != 0.)) {
             char buf[192];

@@ -29,6 +29,7 @@
 #include "rm_accum.hpp"
 #include "rm_soft.hpp"
 #include "rm_motion.hpp"
+#include "rm_motion_shapes.hpp"
 #include "rm_converge.hpp"
 #include "rm_converge_motion.hpp"
 
@@ -333,7 +334,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1122,5 +1123,6 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_accum_host.inc"
 #include "rm_soft_host.inc"
 #include "rm_motion_host.inc"
+#include "rm_motion_shapes_host.inc"
 #include "rm_converge_host.inc"
 #include "rm_converge_motion_host.inc"

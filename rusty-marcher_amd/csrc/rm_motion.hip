@@ -25,7 +25,7 @@
 //   - the glass words' dead sides: the render kernel's, radiance_steps does not read them.
 //   - ties between equal distances: decided by the list key of a pid (closer, prim_key), not by a position.
 //   - closest_hit, any_hit and any_hit2 refuse at compile time to walk a hierarchy or cull with a rule that moves spheres.
-// Polygon and triangle records are pre-projected at upload and are not moved.
+// Polygon and triangle records are not moved here: rm_motion_shapes.hip moves them, with one more rule.
 //
 // Every lane holds a valid row (s < n_samples, idle lanes too) and every device sphere's map word is a shape of the scene
 // (< n_shapes, the host checked the count), so the fetch needs no predicate; surface_at asks for sphere 0 in lanes without a

@@ -8,7 +8,8 @@
 // buffers the context owns (sum, mean, bytes: not the resident frame, not the lens frame), the count of samples in the sum and
 // the identity of the frame the sum belongs to (rm_sampling.hpp).  rm_render_progressive_soft is that with radii in the rules
 // and a slice of rm_light_sequence staged, rm_render_progressive_motion with velocities and a shutter as well and a slice of
-// rm_motion_sequence: which tables a tick stages is rm_staging_of's rule.
+// rm_motion_sequence: which tables a tick stages is rm_staging_of's rule.  rm_render_progressive_moving
+// (rm_motion_shapes_host.inc, behind this file) is the fourth: the motion tick with every shape free to move.
 
 // The launch; offsets: NULL where the scene has no lights; shape_offsets: NULL where it has no spheres.
 static rm_status launch_motion(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets) {
@@ -20,6 +21,9 @@ static rm_status launch_motion(rm_ctx *ctx, const accum_call &c, const void *off
     a.n_shapes = resident_shape_count(ctx);
     return launch_shading(ctx, shade_family{"moving spheres", rm_motion_kernel}, a.S.A.L.max_depth, lens_extent(ctx, a.S.A.L), a, c.stream);
 }
+
+// A launch with launch_motion's arguments: the moving shapes' tick (rm_motion_shapes_host.inc) hands the tick below its own
+using motion_launch = rm_status (*)(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets);
 
 // A staged slice of an offset sequence: host side and device side, grown on demand
 struct rm_staged_slice {
@@ -60,13 +64,16 @@ static rm_status stage_slice(rm_ctx *ctx, rm_staged_slice &s, size_t doubles, FI
     return RM_OK;
 }
 
-// The tick of the three calls; `rules` says which: checked here, the tables they ask for staged, the launch by them.
+// The tick of the four calls; `rules` says which, and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
+// which a velocity on any shape is obeyed; key.motion = 2 keeps its frames apart from the moving spheres') from the moving
+// spheres': checked here, the tables they ask for staged, the launch by them.
 static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, const rm_sampling_rules &rules,
-                                            int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
+                                            int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing,
+                                            motion_launch any_shape = nullptr) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
     const auto t_begin = std::chrono::steady_clock::now();
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
-    if (rm_status rst = check_rules(ctx, who, rules)) return rst;
+    if (rm_status rst = check_rules(ctx, who, rules, any_shape != nullptr)) return rst;
     const uint32_t rows = refine_rows(p), ns = lens->n_samples;
     const size_t pixels = (size_t)rows * p->frame_width;
     double kernel_ms = 0.;
@@ -74,6 +81,7 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
         if (!ctx->progressive) ctx->progressive = new rm_progressive();
         rm_progressive &g = *ctx->progressive;
         rm_frame_identity id = rm_frame_identity_of(*p, *lens, ctx->camera, ctx->basis, ctx->oriented, ctx->upload_copies, rules);
+        if (any_shape) id.key.motion = 2u;
         const uint32_t n_before = !restart && g.have_key && rm_same_frame(g.id, id) ? g.n : 0u;
         const bool saturated = n_before + ns > RM_PROGRESSIVE_MAX_SAMPLES;     // (then n_before > 0: the frame stands)
         RM_HIP(ctx, hipSetDevice(ctx->device));
@@ -95,6 +103,7 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
             const accum_call call{p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream};
             const void *lights = staged.light_columns > 0u ? g.lights.d : nullptr, *shapes = staged.shape_columns > 0u ? g.shapes.d : nullptr;
             auto launch = [&]() {
+                if (any_shape) return any_shape(ctx, call, lights, shapes);
                 return rules.motion ? launch_motion(ctx, call, lights, shapes) : rules.soft ? launch_soft(ctx, call, lights) : launch_accum(ctx, call);
             };
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;

@@ -12,7 +12,7 @@
 // How a lane comes by its ray is the including kernel's business; sample_direction below is the one way to form a sample's.
 //
 // Also here, once, what the including kernels share beside the step: their view of the scene (global_scene_view, rm_query.hip's
-// too), the display byte of a mean (to_byte) and the rules of the moved lights (OffsetLights) and spheres (OffsetSpheres).
+// too), the display byte of a mean (to_byte) and the rules of the moved lights (OffsetLights), spheres (OffsetSpheres) and shapes (OffsetShapes).
 
 namespace rmradiance {
 
@@ -61,6 +61,53 @@ struct OffsetSpheres {
         return SphereRec{c.x, c.y, c.z, s.r2};
     }
     __device__ __forceinline__ V3 centre(const double *sp, uint32_t i) const { return at(sp[0], sp[1], sp[2], i); }
+    using Planar = StoredPlanar;                                         // polygons and triangles stand still
+    __device__ __forceinline__ Planar planar() const { return Planar(); }
+};
+
+// ... and every shape moved (the moving shapes, rm_motion_shapes.hip): the spheres as OffsetSpheres moves them, and a polygon or
+// a triangle by the row's entry of its shape -- for a triangle that is its Obj.  polygon.rs:44-49 and triangle.rs:19-24 add the
+// offset to the plane point (the centre) and to every vertex and leave the normal alone; the records hold those same quantities
+// (x and y of a vertex: the inside test reads no z), so record + offset, rounded once a component, is the reference's moved
+// primitive.  The records stay the wave's (scalar operands): a Planar holds only the lane's three offsets of the shape the
+// walk is at, and the hit tests form record + offset at each use (StoredPlanar of rm_trace.inc is the rule without).  The pid
+// of polygon g is n_spheres + g, of triangle k n_spheres + n_polygons + k; the map word is wave-uniform in the walks, so
+// whether the shape changed is a scalar branch: the triangles of a mesh are consecutive and fetch their offset once.
+struct OffsetShapes {
+    static constexpr bool moves = true;
+    const double *row;                                                   // n_shapes x 3 doubles
+    const uint32_t *pid_map;                                             // 2 words a pid; word 0: the shape
+    uint32_t n_spheres, n_polygons;
+    __device__ __forceinline__ V3 at(double cx, double cy, double cz, uint32_t i) const {
+        const double *o = row + 3u * pid_map[2u * i];
+        return mk(cx + o[0], cy + o[1], cz + o[2]);
+    }
+    __device__ __forceinline__ SphereRec operator()(const SphereRec &s, uint32_t i) const {
+        const V3 c = at(s.cx, s.cy, s.cz, i);
+        return SphereRec{c.x, c.y, c.z, s.r2};
+    }
+    __device__ __forceinline__ V3 centre(const double *sp, uint32_t i) const { return at(sp[0], sp[1], sp[2], i); }
+    struct Planar {
+        const double *row;
+        const uint32_t *pid_map;
+        uint32_t n_spheres, n_polygons;
+        uint32_t shape;                                                  // whose offsets these are; ~0: none yet
+        double ox, oy, oz;
+        __device__ __forceinline__ void seek(uint32_t pid) {
+            const uint32_t k = pid_map[2u * pid];
+            if (k != shape) {
+                const double *o = row + 3u * k;
+                ox = o[0]; oy = o[1]; oz = o[2];
+                shape = k;
+            }
+        }
+        __device__ __forceinline__ const Planar &polygon(uint32_t g) { seek(n_spheres + g); return *this; }
+        __device__ __forceinline__ const Planar &triangle(uint32_t k) { seek(n_spheres + n_polygons + k); return *this; }
+        __device__ __forceinline__ double x(double v) const { return v + ox; }
+        __device__ __forceinline__ double y(double v) const { return v + oy; }
+        __device__ __forceinline__ double z(double v) const { return v + oz; }
+    };
+    __device__ __forceinline__ Planar planar() const { return Planar{row, pid_map, n_spheres, n_polygons, ~0u, 0., 0., 0.}; }
 };
 
 // The un-normalised direction of the sample (sx, sy): renderer.rs:128-135 at a real-valued position, the host's

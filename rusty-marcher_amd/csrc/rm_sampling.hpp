@@ -42,7 +42,7 @@ struct rm_progressive_key {
     rm_camera_basis basis;
     uint64_t copies;
     uint32_t soft, n_lights;                 // frames with radii: 1 and the radii's count (their bytes: rm_frame_identity::radii); else 0, 0
-    uint32_t motion, n_shapes;               // frames with velocities: 1 and their count (their bytes: rm_frame_identity::velocities)
+    uint32_t motion, n_shapes;               // frames with velocities: 1 (2: the moving shapes' tick sets it) and their count (bytes: rm_frame_identity::velocities)
     double shutter;                          // and the shutter; else 0, 0, 0
 };
 

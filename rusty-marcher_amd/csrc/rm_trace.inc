@@ -262,10 +262,25 @@ __device__ __forceinline__ SphereRec load_sphere(const double *__restrict__ S, c
 // the walks (a record fetched by a wave-uniform index), `centre` the normal (the lane's own hit): one rule forms both, so the
 // normal sees the centre the hit test saw.  Nothing else in those five reads a sphere's position but the hierarchy's boxes, the
 // bundle cull and the occluder masks, which hold for the stored centres: such a kernel runs without the three.
+//
+// Where a planar primitive stands, in the same way: a walk asks the rule for a `Planar` (planar()), points it at the polygon or
+// the triangle it is about to test (polygon(g), triangle(k): device indices; they return the Planar as it then stands, which
+// the walk hands to the hit test as it is) and the hit tests read every coordinate of the record through it -- x, y, z of the
+// plane point or the centre, x and y of a vertex, the pool's vertices too.  StoredPlanar is the identity: the record as the
+// scene image says, and what every kernel but the moving shapes' (rm_motion_shapes.hip) walks with.
+struct StoredPlanar {
+    __device__ __forceinline__ StoredPlanar polygon(uint32_t) const { return StoredPlanar(); }
+    __device__ __forceinline__ StoredPlanar triangle(uint32_t) const { return StoredPlanar(); }
+    __device__ __forceinline__ double x(double v) const { return v; }
+    __device__ __forceinline__ double y(double v) const { return v; }
+    __device__ __forceinline__ double z(double v) const { return v; }
+};
 struct StoredSpheres {
     static constexpr bool moves = false;
+    using Planar = StoredPlanar;
     __device__ __forceinline__ SphereRec operator()(const SphereRec &s, uint32_t) const { return s; }
     __device__ __forceinline__ V3 centre(const double *sp, uint32_t) const { return mk(sp[0], sp[1], sp[2]); }
+    __device__ __forceinline__ Planar planar() const { return Planar(); }
 };
 __device__ __forceinline__ PolyRec load_polygon(const double *__restrict__ S, const rm_dev_header &H, uint32_t i) {
     const double *pg = S + H.off_polygons + RM_POLYGON_WORDS * i;
@@ -307,8 +322,11 @@ __device__ __forceinline__ void sphere_setup(const SphereRec &s, V3 o, V3 d, dou
 __device__ __forceinline__ double plane_num(double px, double py, double pz, double nx, double ny, double nz, V3 o) {
     return dot(mk(px - o.x, py - o.y, pz - o.z), mk(nx, ny, nz));
 }
+// `at`: where the polygon stands (StoredPlanar: as the record says); a caller that forms `num` itself forms it from at's point.
+template <class AT = StoredPlanar>
 __device__ __forceinline__ bool polygon_hit_num(const double *__restrict__ S, const rm_dev_header &H, const PolyRec &g,
-                                                const Vert2 (&q)[4], double num, V3 o, V3 d, bool on, double &dist, V3 &p) {
+                                                const Vert2 (&q)[4], double num, V3 o, V3 d, bool on, double &dist, V3 &p,
+                                                const AT at = AT()) {
     const V3 n = mk(g.nx, g.ny, g.nz);
     const double dotprod = dot(d, n);
     // :66 parallel, :71-76 `dist = num / dotprod; if dist < 0 -> None`.  The quotient is
@@ -320,20 +338,20 @@ __device__ __forceinline__ bool polygon_hit_num(const double *__restrict__ S, co
     dist = num / dotprod;
     alive = alive & !(dist < 0.);
     p = o + scaled(d, dist);
-    const double x0 = q[0].x - p.x, y0 = q[0].y - p.y;
-    const double x1 = q[1].x - p.x, y1 = q[1].y - p.y;
-    const double x2 = q[2].x - p.x, y2 = q[2].y - p.y;
+    const double x0 = at.x(q[0].x) - p.x, y0 = at.y(q[0].y) - p.y;
+    const double x1 = at.x(q[1].x) - p.x, y1 = at.y(q[1].y) - p.y;
+    const double x2 = at.x(q[2].x) - p.x, y2 = at.y(q[2].y) - p.y;
     alive = alive & (x0 * y1 - y0 * x1 > 0.);
     if (!__any(alive)) return false;                                  // the whole wave is outside edge 0
     alive = alive & (x1 * y2 - y1 * x2 > 0.);
     if (g.nv == 3u) {
         alive = alive & (x2 * y0 - y2 * x0 > 0.);
     } else {
-        double ax = q[3].x - p.x, ay = q[3].y - p.y;
+        double ax = at.x(q[3].x) - p.x, ay = at.y(q[3].y) - p.y;
         alive = alive & (x2 * ay - y2 * ax > 0.);
         for (uint32_t e = 4; e < g.nv; e++) {                         // pentagons and up
             const Vert2 v = load_vertex(S, H, g.first + e);
-            const double bx = v.x - p.x, by = v.y - p.y;
+            const double bx = at.x(v.x) - p.x, by = at.y(v.y) - p.y;
             alive = alive & (ax * by - ay * bx > 0.);
             ax = bx; ay = by;
         }
@@ -342,13 +360,16 @@ __device__ __forceinline__ bool polygon_hit_num(const double *__restrict__ S, co
     return alive;
 }
 
+template <class AT = StoredPlanar>
 __device__ __forceinline__ bool polygon_hit(const double *__restrict__ S, const rm_dev_header &H, const PolyRec &g,
-                                            const Vert2 (&q)[4], V3 o, V3 d, bool on, double &dist, V3 &p) {
-    return polygon_hit_num(S, H, g, q, plane_num(g.px, g.py, g.pz, g.nx, g.ny, g.nz, o), o, d, on, dist, p);
+                                            const Vert2 (&q)[4], V3 o, V3 d, bool on, double &dist, V3 &p, const AT at = AT()) {
+    return polygon_hit_num(S, H, g, q, plane_num(at.x(g.px), at.y(g.py), at.z(g.pz), g.nx, g.ny, g.nz, o), o, d, on, dist, p, at);
 }
 
-// triangle.rs:49-83
-__device__ __forceinline__ bool triangle_hit_num(const TriRec &t, double num, V3 o, V3 d, bool on, double &dist, V3 &p) {
+// triangle.rs:49-83; `at` as polygon_hit_num's
+template <class AT = StoredPlanar>
+__device__ __forceinline__ bool triangle_hit_num(const TriRec &t, double num, V3 o, V3 d, bool on, double &dist, V3 &p,
+                                                 const AT at = AT()) {
     const V3 n = mk(t.nx, t.ny, t.nz);
     const double dotprod = dot(d, n);
     // :57 parallel, :62-67 going away -- same early sign test as polygon_hit
@@ -358,17 +379,18 @@ __device__ __forceinline__ bool triangle_hit_num(const TriRec &t, double num, V3
     dist = num / dotprod;
     alive = alive & !(dist < 0.);
     p = o + scaled(d, dist);
-    const double ax = t.ax - p.x, ay = t.ay - p.y;
-    const double bx = t.bx - p.x, by = t.by - p.y;
-    const double cx = t.ex - p.x, cy = t.ey - p.y;
+    const double ax = at.x(t.ax) - p.x, ay = at.y(t.ay) - p.y;
+    const double bx = at.x(t.bx) - p.x, by = at.y(t.by) - p.y;
+    const double cx = at.x(t.ex) - p.x, cy = at.y(t.ey) - p.y;
     alive = alive & (ax * by - ay * bx > 0.);
     if (!__any(alive)) return false;
     alive = alive & (bx * cy - by * cx > 0.);
     alive = alive & (cx * ay - cy * ax > 0.);
     return alive;
 }
-__device__ __forceinline__ bool triangle_hit(const TriRec &t, V3 o, V3 d, bool on, double &dist, V3 &p) {
-    return triangle_hit_num(t, plane_num(t.cx, t.cy, t.cz, t.nx, t.ny, t.nz, o), o, d, on, dist, p);
+template <class AT = StoredPlanar>
+__device__ __forceinline__ bool triangle_hit(const TriRec &t, V3 o, V3 d, bool on, double &dist, V3 &p, const AT at = AT()) {
+    return triangle_hit_num(t, plane_num(at.x(t.cx), at.y(t.cy), at.z(t.cz), t.nx, t.ny, t.nz, o), o, d, on, dist, p, at);
 }
 
 // ---- ray bundles: which primitives can the rays of this wave reach at all? ---------------
@@ -717,12 +739,12 @@ __device__ __forceinline__ void closest_sphere(const SceneView &sc, ClosestState
     closest_update(c, closer<ORDERED_WALK>(sc, valid, c.hit, dist, c.best, pid, c.best_pid), dist, t, pid);
 }
 
-template <bool ORDERED_WALK>
-__device__ __forceinline__ void closest_polygon(const SceneView &sc, ClosestState &c, uint32_t g, V3 o, V3 d, bool on) {
+template <bool ORDERED_WALK, class AT = StoredPlanar>
+__device__ __forceinline__ void closest_polygon(const SceneView &sc, ClosestState &c, uint32_t g, V3 o, V3 d, bool on, const AT at = AT()) {
     const PolyRec pg = load_polygon(sc.G, sc.H, g);
     double dist;
     V3 p;
-    const bool valid = polygon_hit(sc.G, sc.H, pg, pg.q, o, d, on, dist, p);
+    const bool valid = polygon_hit(sc.G, sc.H, pg, pg.q, o, d, on, dist, p, at);
     if (!__any(valid)) return;
 #if RM_FAST
     const double dh = dist;
@@ -735,12 +757,12 @@ __device__ __forceinline__ void closest_polygon(const SceneView &sc, ClosestStat
 }
 
 // obj.rs:193-210: closest triangle, strict `<`
-template <bool ORDERED_WALK>
+template <bool ORDERED_WALK, class AT = StoredPlanar>
 __device__ __forceinline__ void closest_triangle(const SceneView &sc, ClosestState &c, const TriRec &t, uint32_t k, V3 o,
-                                                 V3 d, bool on) {
+                                                 V3 d, bool on, const AT at = AT()) {
     double dist;
     V3 p;
-    const bool valid = triangle_hit(t, o, d, on, dist, p);
+    const bool valid = triangle_hit(t, o, d, on, dist, p, at);
     if (!__any(valid)) return;
 #if RM_FAST
     const double dh = dist;
@@ -842,7 +864,8 @@ __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, boo
     }
     for (; i < H.n_spheres; i++) closest_sphere<true>(sc, c, spheres(load_sphere(S, H, i), i), i, o, d, on);
 
-    for (uint32_t g = 0; g < H.n_polygons; g++) closest_polygon<true>(sc, c, g, o, d, on);
+    typename SPHERES::Planar at = spheres.planar();
+    for (uint32_t g = 0; g < H.n_polygons; g++) closest_polygon<true>(sc, c, g, o, d, on, at.polygon(g));
 
     uint32_t k = 0;
     if (BVH && H.off_bvh_triangles) {
@@ -855,10 +878,10 @@ __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, boo
     }
     for (; k + 2u <= H.n_triangles; k += 2u) {
         const TriRec t0 = load_triangle(S, H, k), t1 = load_triangle(S, H, k + 1u);
-        closest_triangle<true>(sc, c, t0, k, o, d, on);
-        closest_triangle<true>(sc, c, t1, k + 1u, o, d, on);
+        closest_triangle<true>(sc, c, t0, k, o, d, on, at.triangle(k));
+        closest_triangle<true>(sc, c, t1, k + 1u, o, d, on, at.triangle(k + 1u));
     }
-    for (; k < H.n_triangles; k++) closest_triangle<true>(sc, c, load_triangle(S, H, k), k, o, d, on);
+    for (; k < H.n_triangles; k++) closest_triangle<true>(sc, c, load_triangle(S, H, k), k, o, d, on, at.triangle(k));
 
     out.t = c.best_t;
     out.pid = c.best_pid;
@@ -918,23 +941,26 @@ __device__ __forceinline__ void any_hit2(const SceneView &sc, V3 o, V3 d0, V3 d1
         if (__all(occ0 & occ1)) { out0 = occ0; out1 = occ1; return; }
     }
     for (; i < H.n_spheres; i++) sphere(spheres(load_sphere(S, H, i), i));
+    typename SPHERES::Planar at = spheres.planar();
     for (uint32_t g = 0; g < H.n_polygons; g++) {
         if (__all(occ0 & occ1)) break;
         const PolyRec pg = load_polygon(S, H, g);
-        const double num = plane_num(pg.px, pg.py, pg.pz, pg.nx, pg.ny, pg.nz, o);
+        at.polygon(g);
+        const double num = plane_num(at.x(pg.px), at.y(pg.py), at.z(pg.pz), pg.nx, pg.ny, pg.nz, o);
         double dist;
         V3 p;
-        occ0 = occ0 | polygon_hit_num(S, H, pg, pg.q, num, o, d0, !occ0, dist, p);
-        occ1 = occ1 | polygon_hit_num(S, H, pg, pg.q, num, o, d1, !occ1, dist, p);
+        occ0 = occ0 | polygon_hit_num(S, H, pg, pg.q, num, o, d0, !occ0, dist, p, at);
+        occ1 = occ1 | polygon_hit_num(S, H, pg, pg.q, num, o, d1, !occ1, dist, p, at);
     }
     for (uint32_t k = 0; k < H.n_triangles; k++) {
         if (__all(occ0 & occ1)) break;
         const TriRec t = load_triangle(S, H, k);
-        const double num = plane_num(t.cx, t.cy, t.cz, t.nx, t.ny, t.nz, o);
+        at.triangle(k);
+        const double num = plane_num(at.x(t.cx), at.y(t.cy), at.z(t.cz), t.nx, t.ny, t.nz, o);
         double dist;
         V3 p;
-        occ0 = occ0 | triangle_hit_num(t, num, o, d0, !occ0, dist, p);
-        occ1 = occ1 | triangle_hit_num(t, num, o, d1, !occ1, dist, p);
+        occ0 = occ0 | triangle_hit_num(t, num, o, d0, !occ0, dist, p, at);
+        occ1 = occ1 | triangle_hit_num(t, num, o, d1, !occ1, dist, p, at);
     }
     out0 = occ0; out1 = occ1;
 }
@@ -1067,11 +1093,12 @@ __device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool de
     for (; i < H.n_spheres; i++) occ = occ | shadow_sphere(spheres(load_sphere(S, H, i), i), o, d, occ);
     if (__all(occ)) return occ;
 
+    typename SPHERES::Planar at = spheres.planar();
     for (uint32_t g = 0; g < H.n_polygons; g++) {
         const PolyRec pg = load_polygon(S, H, g);
         double dist;
         V3 p;
-        occ = occ | polygon_hit(S, H, pg, pg.q, o, d, !occ, dist, p);
+        occ = occ | polygon_hit(S, H, pg, pg.q, o, d, !occ, dist, p, at.polygon(g));
         if (__all(occ)) return occ;
     }
 
@@ -1090,14 +1117,14 @@ __device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool de
         const TriRec t0 = load_triangle(S, H, k), t1 = load_triangle(S, H, k + 1u);
         double dist;
         V3 p;
-        occ = occ | triangle_hit(t0, o, d, !occ, dist, p);
-        occ = occ | triangle_hit(t1, o, d, !occ, dist, p);
+        occ = occ | triangle_hit(t0, o, d, !occ, dist, p, at.triangle(k));
+        occ = occ | triangle_hit(t1, o, d, !occ, dist, p, at.triangle(k + 1u));
         if (__all(occ)) return occ;
     }
     for (; k < H.n_triangles; k++) {
         double dist;
         V3 p;
-        occ = occ | triangle_hit(load_triangle(S, H, k), o, d, !occ, dist, p);
+        occ = occ | triangle_hit(load_triangle(S, H, k), o, d, !occ, dist, p, at.triangle(k));
     }
     return occ;
 }

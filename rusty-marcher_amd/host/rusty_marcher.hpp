@@ -472,6 +472,20 @@ struct Renderer {
     std::string render_progressive_motion(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const std::vector<Vec3f> &velocities,
                                           double shutter, uint32_t n_samples, const std::vector<double> &radii = {}, double aperture = 0.,
                                           double focus = 1., bool restart = false) {
+        return tick_with_velocities(false, frame, sc, velocities, shutter, n_samples, radii, aperture, focus, restart);
+    }
+    // render_progressive_motion in which every shape moves (rm_render_progressive_moving): a velocity on a polygon or a mesh is
+    // obeyed -- the plane point and the vertices, every triangle's centre and vertices move as the reference's offset() moves them,
+    // the normals stay.  The frame is not render_progressive_motion's: a switch between the two begins it again.
+    std::string render_progressive_moving(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const std::vector<Vec3f> &velocities,
+                                          double shutter, uint32_t n_samples, const std::vector<double> &radii = {}, double aperture = 0.,
+                                          double focus = 1., bool restart = false) {
+        return tick_with_velocities(true, frame, sc, velocities, shutter, n_samples, radii, aperture, focus, restart);
+    }
+    // The tick of the two calls above; any_shape: the second
+    std::string tick_with_velocities(bool any_shape, framebuffer::FrameBuffer &frame, const scene::Scene &sc,
+                                     const std::vector<Vec3f> &velocities, double shutter, uint32_t n_samples, const std::vector<double> &radii,
+                                     double aperture, double focus, bool restart) {
         const auto t0 = std::chrono::steady_clock::now();
         const rm_params p = prepare(frame.width, frame.height, sc);
         const rm_lens lens{aperture, focus, n_samples, 0u};
@@ -479,8 +493,11 @@ struct Renderer {
         std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
         std::vector<rm_vec3> v;
         for (const Vec3f &e : velocities) v.push_back(e.c());
-        check(rm_render_progressive_motion(ctx_, &p, &lens, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), v.data(),
-                                           (uint32_t)v.size(), shutter, restart ? 1 : 0, flat.data(), nullptr, &last_samples, &last_timing),
+        const double *r = radii.empty() ? nullptr : radii.data();
+        check(any_shape ? rm_render_progressive_moving(ctx_, &p, &lens, r, (uint32_t)radii.size(), v.data(), (uint32_t)v.size(), shutter,
+                                                       restart ? 1 : 0, flat.data(), nullptr, &last_samples, &last_timing)
+                        : rm_render_progressive_motion(ctx_, &p, &lens, r, (uint32_t)radii.size(), v.data(), (uint32_t)v.size(), shutter,
+                                                       restart ? 1 : 0, flat.data(), nullptr, &last_samples, &last_timing),
               ctx_);
         for (size_t y = 0; y < rows; y++)
             for (size_t x = 0; x < frame.width; x++) {

@@ -200,6 +200,30 @@ class Renderer:
             left -= step
         return message
 
+    def render_progressive_moving(self, frame, scene, velocities, shutter, n_samples, light_radii=None, aperture=0., focus=1., restart=False):
+        """render_progressive_motion in which every shape moves (rm_render_progressive_moving): shape k of the scene -- a sphere,
+        a polygon or a mesh -- moves by velocities[k], one Vec3f or None a shape, while the shutter stands open for `shutter`.
+        A polygon's plane point and vertices and a mesh's triangles are moved as the reference's offset() moves them; the
+        normals stay.  The frame is not render_progressive_motion's: a switch between the two begins it again."""
+        backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        v = backend._velocities(velocities, len(scene.shapes))
+        backend._shutter(shutter)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        return self._tick(frame, scene, lambda ctx, p: ctx.render_progressive_moving(p, v, shutter, aperture, focus, n_samples, radii, restart,
+                                                                                      host_rgb=frame.buffer))
+
+    def render_moving_shapes(self, frame, scene, velocities, shutter, n_samples):
+        """One frame with motion blur of every shape: a restarted render_progressive_moving ticked in slices of at most 64 until
+        the frame holds n_samples samples a pixel, through a pinhole, point lights.  Prints and returns what the last tick does."""
+        if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= backend.PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("n_samples must be an integer in 1..%d, got %r" % (backend.PROGRESSIVE_MAX_SAMPLES, n_samples))
+        left, message = int(n_samples), None
+        while left > 0:
+            step = min(left, 64)
+            message = self.render_progressive_moving(frame, scene, velocities, shutter, step, restart=left == n_samples)
+            left -= step
+        return message
+
     def render_converging(self, frame, scene, tolerance, n_samples, min_samples=16, max_samples=1024, light_radii=None, aperture=0., focus=1.,
                           restart=False):
         """A tick of a converging frame (rm_render_converging): render_progressive -- with area lights where light_radii is

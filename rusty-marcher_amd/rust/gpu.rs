@@ -310,6 +310,8 @@ extern "C" {
     fn rm_motion_sequence(first: u32, count: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, offsets: *mut f64) -> c_int;
     fn rm_accumulate_motion_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_progressive_motion(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_accumulate_moving_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_progressive_moving(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
     fn rm_converge_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
     fn rm_accumulate_converging_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_offsets: *const c_void, n_lights: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_render_converging(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
@@ -799,6 +801,94 @@ impl Gpu {
         check(
             unsafe {
                 rm_accumulate_motion_device(self.ctx, &p, &lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// `render_progressive_motion` in which every shape moves: a velocity on a polygon or a mesh is obeyed -- the plane point and
+    /// the vertices, every triangle's centre and vertices move as the reference's `offset()` moves them, the normals stay.  The
+    /// frame is not `render_progressive_motion`'s: a switch between the two begins it again.
+    pub fn render_progressive_moving(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        radii: Option<&[f64]>,
+        velocities: &[Vec3f],
+        shutter: f64,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let v: Vec<RmVec3> = velocities.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect();
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut total: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_progressive_moving(self.ctx, &p, &lens, radii_ptr, n_lights, v.as_ptr(), v.len() as u32, shutter, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut total, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), total)
+    }
+
+    /// The device call under `render_progressive_moving`: `accumulate_motion` in which the rows of every shape are read and move
+    /// it, sphere, polygon or mesh.  `device_shape_offsets` must not be null when the scene holds any shape.
+    pub fn accumulate_moving(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_moving_device(self.ctx, &p, &lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes, n_before, device_sum, device_mean, device_rgb8, hip_stream)
             },
             self.ctx,
         );
