@@ -1247,6 +1247,68 @@ rm_status rm_render_converging_motion(rm_ctx *ctx, const rm_params *params, cons
                                       double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
                                       rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
 
+/* ---- converging frames with moving shapes: every shape blurs, noisy pixels only ----------------
+ * The moving shapes (above) blur polygons and meshes in progressive frames, which sample every
+ * pixel in every pass; the converging frames with moving spheres sample the noisy pixels alone but
+ * move spheres only.  These calls do both: a moving floor quad or mesh leaves its band of slow
+ * pixels, and only the band goes on being sampled.  Additive to ABI version 5; a host detects them
+ * by " converge-moving" in rm_build_info().
+ *
+ * A pass is rm_accumulate_converging_motion_device's word for word -- select, the rows a listed
+ * pixel casts, the light offsets, fold, mean, bytes, list and mask -- with the moving shapes' one
+ * rule in place of the moving spheres':
+ *   - the lane that casts sample s of a listed pixel with count n holds table row r = n + s;
+ *   - for that lane shape k of the scene stands at its record plus shape_offsets[r][k], one
+ *     addition a component, rounded once: a sphere's centre as in the moving spheres; a polygon's
+ *     plane point and every vertex, the pool vertices of a polygon with more than four included;
+ *     an Obj's every triangle, centre and vertices;
+ *   - normals and materials stay as stored;
+ *   - the moved record is used in the closest-hit walk, in both shadow walks and for the children;
+ *   - the shape offset table is [table_rows][n_shapes][3] doubles in the order of the scene's shape
+ *     list, a prefix of rm_motion_sequence in the tick.  Rows of every shape are read, so the whole
+ *     table is a precondition whenever the scene holds any shape; it may be NULL only for a scene
+ *     with no shape.
+ *
+ * Three consequences:
+ *   - zero offsets: with every shape offset +0. or -0. a pass writes
+ *     rm_accumulate_converging_motion_device's bytes -- sum, stats, count, mean, bytes, mask, and
+ *     the list as a set -- for coordinates that are not -0.; with rows of zero for everything but
+ *     the spheres it writes that call's bytes for those sphere rows;
+ *   - own count: the fold stays a left fold in table order, so a pixel with count c holds byte for
+ *     byte the sum, the mean and the display bytes rm_accumulate_moving_device leaves after c rows
+ *     of the same three tables, however the passes were sliced;
+ *   - negative tolerance: with tolerance < 0 a run of passes is the plain moving-shapes run byte
+ *     for byte in sum, mean and bytes.
+ *
+ * Cost: the flat walk of the moving spheres, which a mesh pays in full, and the additions of the
+ * rule at every polygon and triangle test.
+ *
+ * rm_accumulate_converging_moving_device is asynchronous on hip_stream, neither reads nor writes
+ * render state and keeps all of its state in the caller's buffers.  Its argument list and checks
+ * are rm_accumulate_converging_motion_device's, and as rm_accumulate_moving_device it refuses a
+ * NULL device_shape_offsets whenever n_shapes > 0.  A refused call names the offender in
+ * rm_last_error and touches no buffer.  The tables' contents are a precondition: a non-finite
+ * offset gives unspecified pixels, never a fault.
+ *
+ * rm_render_converging_moving is rm_render_converging_motion's tick, argument for argument, on the
+ * same context-owned state, in which a velocity on any shape is obeyed.  Its frames are its own:
+ * a switch between this call and rm_render_converging_motion with equal velocities, or
+ * rm_render_converging, begins the frame again.  It keeps a shape table whenever the scene holds a
+ * shape (rm_render_converging_motion keeps none for a scene without spheres).  Checks:
+ * rm_render_converging_motion's without the refusal of a velocity on a shape that is not a sphere;
+ * the older calls' refusals stay as they are.
+ */
+rm_status rm_accumulate_converging_moving_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                                 const rm_converge *converge, const void *device_table, uint32_t table_rows,
+                                                 const void *device_light_offsets, uint32_t n_lights,
+                                                 const void *device_shape_offsets, uint32_t n_shapes, int fresh,
+                                                 const rm_converge_frame *buffers, void *hip_stream);
+rm_status rm_render_converging_moving(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                                      const double *radii /* NULL: point lights */, uint32_t n_lights,
+                                      const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart,
+                                      double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                      rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

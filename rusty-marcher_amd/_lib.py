@@ -243,6 +243,11 @@ SIGNATURES = {
     "rm_render_converging_motion": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, _P(rm_vec3),
                                               C.c_uint32, C.c_double, C.c_int, _P(C.c_double), _P(C.c_uint8), _P(rm_converge_report),
                                               _P(rm_timing)]),
+    "rm_accumulate_converging_moving_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, C.c_uint32, _VP,
+                                                         C.c_uint32, C.c_int, _P(rm_converge_frame), _VP]),
+    "rm_render_converging_moving": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, _P(rm_vec3),
+                                              C.c_uint32, C.c_double, C.c_int, _P(C.c_double), _P(C.c_uint8), _P(rm_converge_report),
+                                              _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -929,6 +929,46 @@ class Context:
                                                       *host, C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
+    # ---- converging frames with moving shapes (include/rusty_marcher_amd.h, "converging frames with moving shapes") ----
+    def accumulate_converging_moving_device(self, params, sum, stats, count, aperture, focus, n_samples, table, light_offsets, shape_offsets,
+                                            tolerance, min_samples, max_samples, fresh, mean=None, rgb8=None, mask=None, workspace=None,
+                                            stream=None):
+        """rm_accumulate_converging_moving_device: accumulate_converging_motion_device in which every shape moves -- the sample
+        that is row r of the tables sees shape k of the scene, sphere, polygon or mesh, moved by shape_offsets[r][k]: a polygon's
+        plane point and vertices, every triangle's centre and vertices of a mesh, the normals as uploaded.  The rows of every
+        shape are read.  Arguments and result as accumulate_converging_motion_device's."""
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
+        rows = int(table.shape[0])
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", rows, sum.device)
+        shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", rows, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), int(shape_offsets.shape[1])
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        _lib.check(self.L.rm_accumulate_converging_moving_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), rows,
+                                                                 vp(light_offsets) if n_lights > 0 else None, n_lights,
+                                                                 vp(shape_offsets) if n_shapes > 0 else None, n_shapes, 1 if fresh else 0,
+                                                                 C.byref(frame), C.c_void_p(self._stream(stream))), self.ptr)
+        return workspace
+
+    def render_converging_moving(self, params, velocities, shutter, aperture, focus, n_samples, tolerance, min_samples, max_samples, radii=None,
+                                 restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_converging_moving: render_converging_motion in which a velocity on any shape is obeyed -- spheres, polygons
+        and meshes move by velocities[k] while the shutter stands open.  Its frames are its own: a switch between this call and
+        render_converging_motion or render_converging begins the frame again.  -> (rm_timing, rm_converge_report)."""
+        lens = _lens(aperture, focus, n_samples)
+        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
+        v, shutter = _velocities(velocities), _shutter(shutter)
+        r = _radii(radii) if radii is not None else None
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing, report = _lib.rm_timing(), _lib.rm_converge_report()
+        _lib.check(self.L.rm_render_converging_moving(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
+                                                      r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                      r.shape[0] if r is not None else 0,
+                                                      v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, 1 if restart else 0,
+                                                      *host, C.byref(report), C.byref(timing)), self.ptr)
+        return timing, report
+
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole
         patch rows), as DeviceHits of [frame_height][frame_width].  `out`: a float64 tensor of shape

@@ -1,5 +1,6 @@
 // rm_converge_body.inc -- the body the shade kernels of the converging frames share: rm_converge.hip's (lights where the scene
-// image says, or moved by the sample's row of an offset table) and rm_converge_motion.hip's (spheres moved as well).  Statements,
+// image says, or moved by the sample's row of an offset table), rm_converge_motion.hip's (spheres moved as well) and
+// rm_converge_moving.hip's (every shape moved).  Statements,
 // not a function: a kernel includes this file as the rest of its body, behind rm_radiance_step.inc, with these names in scope --
 //
 //   BVH, POW, STACK      the compile-time arguments of radiance_steps
@@ -7,7 +8,7 @@
 //   a                    the launch's ConvergeArgs (rm_converge.hpp)
 //   bstack, sums         the workgroup's LDS: 64 words and 64 x 3 doubles
 //   lights_of(r)         the rule that says where the lights of table row r stand (rm_trace.inc: StoredLights, OffsetLights)
-//   spheres_of(r)        the same for the spheres (StoredSpheres, OffsetSpheres)
+//   spheres_of(r)        the same for the spheres (StoredSpheres, OffsetSpheres) or for every shape (OffsetShapes)
 //
 // -- the parameters of rm_accum_body.inc's accum_shade, with one difference: both rules are asked inside the loop over the
 // groups, once a lane and group, with the lane's own row r = count[pixel] + sample.  r < table_rows in every lane, idle ones

@@ -12,7 +12,7 @@ namespace rmdev {
 
 struct ConvergeMotionArgs {
     ConvergeArgs C;                          // the converging frames' own block: select, rays, fold, buffers and light offsets are its
-    const double *shape_offsets;             // [table_rows][n_shapes][3]; not read where the scene has no spheres
+    const double *shape_offsets;             // [table_rows][n_shapes][3]; not read where the scene has no spheres (rm_converge_moving.hip: no shapes)
     const uint32_t *pid_map;                 // the resident image's, 2 words a pid: word 0 is the shape of a device primitive
     uint32_t n_shapes, _pad;                 // the scene's shape count: the length of a row
 };

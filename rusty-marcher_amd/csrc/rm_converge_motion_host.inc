@@ -10,6 +10,8 @@
 // of the lens and the light sequence, a pass total and a frame identity of its own (rm_ctx::converging) -- nothing of
 // rm_render_progressive's.  rm_render_converging_motion is the same tick on the same state with a third resident prefix, the
 // shape offsets, and the velocities and the shutter in the identity: which tables a tick keeps is rm_staging_of's rule.
+// rm_render_converging_moving (rm_converge_moving_host.inc, behind this file) is the third: the motion tick with every shape
+// free to move.
 
 // The three steps on `stream`; everything was checked, rows > 0.  offsets: NULL where the scene has no lights; shape_offsets:
 // NULL where it has no spheres.
@@ -98,14 +100,22 @@ static rm_status converging_extend(rm_ctx *ctx, rm_converging &g, rm_resident_pr
     return RM_OK;
 }
 
-// The tick of both calls; `rules` says which: checked here, the prefixes they ask for kept resident, the launch by them.
+// A launch with launch_converge_motion's arguments: the moving shapes' tick (rm_converge_moving_host.inc) hands the tick below its own
+using converge_motion_launch = rm_status (*)(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                             uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
+                                             const rm_converge_frame *b, hipStream_t stream);
+
+// The tick of the three calls; `rules` says which, and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
+// which a velocity on any shape is obeyed and a shape table is kept whenever the scene holds a shape; key.motion = 2 keeps its
+// frames apart from the moving spheres') from the moving spheres': checked here, the prefixes they ask for kept resident, the
+// launch by them.
 static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, const rm_converge *c,
                                            const rm_sampling_rules &rules, int restart, double *host_rgb, uint8_t *host_rgb8,
-                                           rm_converge_report *report, rm_timing *timing) {
+                                           rm_converge_report *report, rm_timing *timing, converge_motion_launch any_shape = nullptr) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
     const auto t_begin = std::chrono::steady_clock::now();
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
-    if (rm_status rst = check_rules(ctx, who, rules)) return rst;
+    if (rm_status rst = check_rules(ctx, who, rules, any_shape != nullptr)) return rst;
     if (rm_status vst = check_converge(ctx, who, lens, c, RM_PROGRESSIVE_MAX_SAMPLES)) return vst;
     const uint32_t rows = refine_rows(p), ns = lens->n_samples;
     const size_t pixels = (size_t)rows * p->frame_width;
@@ -115,8 +125,10 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
         if (!ctx->converging) ctx->converging = new rm_converging();
         rm_converging &g = *ctx->converging;
         rm_frame_identity id = rm_frame_identity_of(*p, *lens, ctx->camera, ctx->basis, ctx->oriented, ctx->upload_copies, rules);
+        if (any_shape) id.key.motion = 2u;
         const bool same = !restart && g.have_key && rm_same_frame(g.id, id);
-        const rm_staging staged = rm_staging_of(RM_TICK_CONVERGING, rules, ctx->image.H.n_lights, ctx->image.H.n_spheres, resident_shape_count(ctx));
+        const rm_staging staged = rm_staging_of(any_shape ? RM_TICK_CONVERGING_MOVING : RM_TICK_CONVERGING, rules, ctx->image.H.n_lights,
+                                                ctx->image.H.n_spheres, resident_shape_count(ctx));
         // a finished picture: the pass before this one, with the same rule, listed nothing -- so would this one
         const bool finished = same && g.passes > 0u && g.listed == 0u && g.last_ns == ns && std::memcmp(&g.last, c, sizeof *c) == 0;
         RM_HIP(ctx, hipSetDevice(ctx->device));
@@ -159,6 +171,9 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
             if (offsets) resident = std::min(resident, g.lights.rows);
             if (shapes) resident = std::min(resident, g.shapes.rows);
             auto launch = [&]() {
+                if (any_shape)
+                    return any_shape(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, shapes ? g.shapes.d : nullptr,
+                                     g.n == 0u, &b, ctx->stream);
                 if (rules.motion)
                     return launch_converge_motion(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr,
                                                   shapes ? g.shapes.d : nullptr, g.n == 0u, &b, ctx->stream);

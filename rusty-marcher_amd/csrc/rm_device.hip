@@ -32,6 +32,7 @@
 #include "rm_motion_shapes.hpp"
 #include "rm_converge.hpp"
 #include "rm_converge_motion.hpp"
+#include "rm_converge_moving.hpp"
 
 using namespace rmdev;
 
@@ -229,7 +230,7 @@ struct rm_ctx {
     // progressive frames (rm_motion_host.inc): made by the first rm_render_progressive, _soft or _motion
     rm_progressive *progressive = nullptr;
 
-    // converging frames (rm_converge_motion_host.inc): made by the first rm_render_converging or rm_render_converging_motion; shares nothing with `progressive`
+    // converging frames (rm_converge_motion_host.inc): made by the first rm_render_converging, rm_render_converging_motion or rm_render_converging_moving; shares nothing with `progressive`
     rm_converging *converging = nullptr;
 
     // post-process scratch
@@ -334,7 +335,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes converge-moving converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1126,3 +1127,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_motion_shapes_host.inc"
 #include "rm_converge_host.inc"
 #include "rm_converge_motion_host.inc"
+#include "rm_converge_moving_host.inc"

@@ -107,7 +107,7 @@ rm_staging rm_staging_of(rm_tick_kind kind, const rm_sampling_rules &rules, uint
     rm_staging s;
     s.light_columns = rules.motion ? scene_lights : rules.soft ? rules.n_lights : 0u;
     s.light_zeros = rules.motion && !rules.soft;
-    s.shape_columns = rules.motion && (kind == RM_TICK_PROGRESSIVE || scene_spheres > 0u) ? scene_shapes : 0u;
+    s.shape_columns = rules.motion && (kind != RM_TICK_CONVERGING || scene_spheres > 0u) ? scene_shapes : 0u;
     return s;
 }
 

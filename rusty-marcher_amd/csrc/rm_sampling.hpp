@@ -61,8 +61,9 @@ bool rm_same_frame(const rm_frame_identity &a, const rm_frame_identity &b);
 
 // The offset tables a tick stages beside the lens table: a motion tick's kernel reads a row for every light of the scene --
 // zeros where the lights are points -- and for every shape; a soft tick's for every radius.  The converging tick stages no shape
-// table for a scene without spheres, the progressive one does.
-enum rm_tick_kind { RM_TICK_PROGRESSIVE, RM_TICK_CONVERGING };
+// table for a scene without spheres, the progressive one does; the converging tick of the moving shapes, whose kernel reads a
+// row of polygons and meshes as well, stages one whenever the scene holds a shape.
+enum rm_tick_kind { RM_TICK_PROGRESSIVE, RM_TICK_CONVERGING, RM_TICK_CONVERGING_MOVING };
 struct rm_staging {
     uint32_t light_columns;                  // 0: no light table
     bool light_zeros;

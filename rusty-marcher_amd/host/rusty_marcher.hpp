@@ -538,14 +538,33 @@ struct Renderer {
                                                 double shutter, const rm_converge &converge, uint32_t n_samples,
                                                 const std::vector<double> &radii = {}, double aperture = 0., double focus = 1.,
                                                 bool restart = false) {
+        return converging_tick_with_velocities(false, frame, sc, velocities, shutter, converge, n_samples, radii, aperture, focus, restart);
+    }
+    // render_converging_motion in which every shape moves (rm_render_converging_moving): a velocity on a polygon or a mesh is obeyed
+    // -- the plane point and the vertices, every triangle's centre and vertices move as the reference's offset() moves them, the
+    // normals stay.  The frame is not render_converging_motion's: a switch between the two begins it again.
+    rm_converge_report render_converging_moving(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const std::vector<Vec3f> &velocities,
+                                                double shutter, const rm_converge &converge, uint32_t n_samples,
+                                                const std::vector<double> &radii = {}, double aperture = 0., double focus = 1.,
+                                                bool restart = false) {
+        return converging_tick_with_velocities(true, frame, sc, velocities, shutter, converge, n_samples, radii, aperture, focus, restart);
+    }
+    // The tick of the two calls above; any_shape: the second
+    rm_converge_report converging_tick_with_velocities(bool any_shape, framebuffer::FrameBuffer &frame, const scene::Scene &sc,
+                                                       const std::vector<Vec3f> &velocities, double shutter, const rm_converge &converge,
+                                                       uint32_t n_samples, const std::vector<double> &radii, double aperture, double focus,
+                                                       bool restart) {
         const rm_params p = prepare(frame.width, frame.height, sc);
         const rm_lens lens{aperture, focus, n_samples, 0u};
         const size_t rows = frame.height - frame.height % 32;
         std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
         std::vector<rm_vec3> v;
         for (const Vec3f &e : velocities) v.push_back(e.c());
-        check(rm_render_converging_motion(ctx_, &p, &lens, &converge, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), v.data(),
-                                          (uint32_t)v.size(), shutter, restart ? 1 : 0, flat.data(), nullptr, &last_report, &last_timing),
+        const double *r = radii.empty() ? nullptr : radii.data();
+        check(any_shape ? rm_render_converging_moving(ctx_, &p, &lens, &converge, r, (uint32_t)radii.size(), v.data(), (uint32_t)v.size(), shutter,
+                                                      restart ? 1 : 0, flat.data(), nullptr, &last_report, &last_timing)
+                        : rm_render_converging_motion(ctx_, &p, &lens, &converge, r, (uint32_t)radii.size(), v.data(), (uint32_t)v.size(), shutter,
+                                                      restart ? 1 : 0, flat.data(), nullptr, &last_report, &last_timing),
               ctx_);
         last_samples = last_report.max_count;
         for (size_t y = 0; y < rows; y++)

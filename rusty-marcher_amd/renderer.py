@@ -24,7 +24,7 @@ class Renderer:
         self.last_timing = None
         self.last_refined = None                                           # render_antialiased: pixels it refined
         self.last_samples = None                                           # render_progressive: samples a pixel in its frame
-        self.last_report = None                                            # render_converging, render_converging_motion: the last tick's rm_converge_report
+        self.last_report = None                                            # render_converging, render_converging_motion, render_converging_moving: the last tick's rm_converge_report
 
     def render(self, frame, scene):
         t0 = time.perf_counter()
@@ -287,6 +287,40 @@ class Renderer:
                                                aperture, focus, restart=True)
         while report.listed > 0:
             report = self.render_converging_motion(frame, scene, velocities, shutter, tolerance, n_samples, min_samples, max_samples, light_radii,
+                                                   aperture, focus)
+        return report
+
+    def render_converging_moving(self, frame, scene, velocities, shutter, tolerance, n_samples, min_samples=16, max_samples=1024,
+                                 light_radii=None, aperture=0., focus=1., restart=False):
+        """render_converging_motion in which every shape moves (rm_render_converging_moving): shape k of the scene -- a sphere, a
+        polygon or a mesh -- moves by velocities[k], one Vec3f or None a shape, while the shutter stands open for `shutter`.  A
+        polygon's plane point and vertices and a mesh's triangles are moved as the reference's offset() moves them; the normals
+        stay.  The frame is not render_converging_motion's: a switch between the two begins it again.  Returns the tick's
+        report, as render_converging does."""
+        backend._converge(tolerance, min_samples, max_samples, backend._lens(aperture, focus, n_samples).n_samples)
+        v = backend._velocities(velocities, len(scene.shapes))
+        backend._shutter(shutter)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        got = []
+
+        def call(ctx, p):
+            timing, report = ctx.render_converging_moving(p, v, shutter, aperture, focus, n_samples, tolerance, min_samples, max_samples, radii,
+                                                          restart, host_rgb=frame.buffer)
+            got.append(report)
+            return timing, report.max_count
+
+        self._tick(frame, scene, call)
+        self.last_report = got[0]
+        return got[0]
+
+    def render_converged_moving(self, frame, scene, velocities, shutter, tolerance, n_samples, min_samples=16, max_samples=1024,
+                                light_radii=None, aperture=0., focus=1.):
+        """A finished picture with motion blur of every shape: a restarted render_converging_moving ticked until a tick lists
+        nothing.  -> the last tick's report."""
+        report = self.render_converging_moving(frame, scene, velocities, shutter, tolerance, n_samples, min_samples, max_samples, light_radii,
+                                               aperture, focus, restart=True)
+        while report.listed > 0:
+            report = self.render_converging_moving(frame, scene, velocities, shutter, tolerance, n_samples, min_samples, max_samples, light_radii,
                                                    aperture, focus)
         return report
 

@@ -317,6 +317,8 @@ extern "C" {
     fn rm_render_converging(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_accumulate_converging_motion_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_render_converging_motion(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
+    fn rm_accumulate_converging_moving_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_converging_moving(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -1084,6 +1086,95 @@ impl Gpu {
         check(
             unsafe {
                 rm_accumulate_converging_motion_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, if fresh { 1 } else { 0 }, &buffers, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// `render_converging_motion` in which every shape moves: a velocity on a polygon or a mesh is obeyed -- the plane point and
+    /// the vertices, every triangle's centre and vertices move as the reference's `offset()` moves them, the normals stay.  The
+    /// frame is not `render_converging_motion`'s: a switch between the two begins it again.
+    pub fn render_converging_moving(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        converge: RmConverge,
+        radii: Option<&[f64]>,
+        velocities: &[Vec3f],
+        shutter: f64,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, RmConvergeReport) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let v: Vec<RmVec3> = velocities.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect();
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut report = RmConvergeReport::default();
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_converging_moving(self.ctx, &p, &lens, &converge, radii_ptr, n_lights, v.as_ptr(), v.len() as u32, shutter, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut report, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), report)
+    }
+
+    /// The device call under `render_converging_moving`: `accumulate_converging_motion` in which the row of every shape is read
+    /// -- sphere, polygon or mesh -- so `device_shape_offsets` may be null only for a scene with no shape.
+    pub fn accumulate_converging_moving(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_moving_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, if fresh { 1 } else { 0 }, &buffers, hip_stream)
             },
             self.ctx,
         );
