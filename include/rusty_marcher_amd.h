@@ -460,7 +460,11 @@ rm_status rm_comm_info(rm_ctx *ctx, int *rank, int *world, int *n_communicators)
  *     entry points check it, and that every component of origin and direction is finite:
  *     RM_ERR_INVALID_ARG naming the first bad ray in rm_last_error, nothing computed.  For the
  *     device entry points it is a precondition: a bad ray gets an unspecified answer for
- *     that ray, never a fault.
+ *     that ray, never a fault.  Every admitted ray gets the reference's answer, but only rays
+ *     with |d.d - 1| <= 1e-14 (a direction normalised in doubles) are walked through the
+ *     scene's hierarchy: a group of 64 consecutive rays that holds any other one -- unit only
+ *     to float precision, say -- tests every primitive for all 64 (the same for the ranged
+ *     and the radiance rays below).  Normalise in doubles where speed matters.
  *   - Occlusion is intersect_shape_set exactly: a hit ANYWHERE along the ray, t in
  *     [0, inf) -- the reference has no maximum distance, so a shadow ray aimed at a light
  *     counts as blocked by a shape BEHIND the light.  (The ranged queries below bound the ray:

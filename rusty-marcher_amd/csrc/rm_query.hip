@@ -34,6 +34,8 @@ using namespace rmdev_strict;
 namespace rmquery {
 
 using rmradiance::global_scene_view;
+using rmradiance::off_unit;
+using rmradiance::complete_walk_view;
 
 // One rm_hit: the point and normal of surface_at (sphere.rs:58, polygon.rs:95, triangle.rs:80), the
 // pid mapped back to Scene.shapes.  Every field of a miss is 0.
@@ -55,7 +57,7 @@ __device__ __forceinline__ void store_hit(const Args &q, const SceneView &sc, rm
 template <bool BVH, bool OCCLUSION>
 __global__ __launch_bounds__(64) void rm_query_rays_kernel(const double *__restrict__ scene_blob, QueryArgs q) {
     __shared__ uint32_t bstack[64];
-    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
+    const SceneView stored = global_scene_view(scene_blob, q.H, bstack);
     const size_t i = (size_t)blockIdx.x * 64u + (threadIdx.x & 63u);     // (64-bit: 60 M rays x 72 B is past 4 GB)
     const bool on = i < (size_t)q.n_rays;
     V3 o = mk(0., 0., 0.), d = mk(0., 0., -1.);                          // (a tail lane holds a harmless ray it never reports)
@@ -64,6 +66,8 @@ __global__ __launch_bounds__(64) void rm_query_rays_kernel(const double *__restr
         o = mk(ro.x, ro.y, ro.z);
         d = mk(rd.x, rd.y, rd.z);
     }
+    // a caller's ray may be off unit length within the assert: its wave takes the complete walk (rm_radiance_step.inc)
+    const SceneView sc = BVH ? complete_walk_view(stored, __any(on & off_unit(d))) : stored;
     if (OCCLUSION) {
         // (through / rho feed the shadow cull only, which these kernels do not carry)
         const bool occ = any_hit<BVH, false, false>(sc, o, d, !on, o, 0.);
@@ -110,7 +114,8 @@ __global__ __launch_bounds__(64) void rm_query_pixels_kernel(const double *__res
 struct Range { double lo, hi; };
 // Closed; written so that a parameter that is not a number lies in every range, as it passes the reference's `t < 0`.
 __device__ __forceinline__ bool in_range(double t, const Range &r) { return !(t < r.lo) & !(t > r.hi); }
-// Where a box may still be entered: the margin of closest_hit's prune_at (|d| = 1 +- 1e-16; +inf stays +inf).
+// Where a box may still be entered: the margin of closest_hit's prune_at (for rays unit within RM_UNIT_SLACK: a wave that
+// holds another walks without boxes; +inf stays +inf).
 __device__ __forceinline__ double range_cap(const Range &r) { return r.hi * (1. + 1e-7) + 1e-12; }
 
 // sphere.rs:43-52 with the range: the near root if it lies in the range, else the far one if that does.
@@ -334,7 +339,7 @@ __device__ __forceinline__ V3 normalized_norm(V3 a, double &norm) {
 template <bool BVH, int KIND>
 __global__ __launch_bounds__(64) void rm_ranged_kernel_t(const double *__restrict__ scene_blob, RangedArgs q) {
     __shared__ uint32_t bstack[64];
-    const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
+    const SceneView stored = global_scene_view(scene_blob, q.H, bstack);
     const size_t i = (size_t)blockIdx.x * 64u + (threadIdx.x & 63u);
     const bool on = i < (size_t)q.n;
     V3 o = mk(0., 0., 0.), d = mk(0., 0., -1.);
@@ -347,6 +352,9 @@ __global__ __launch_bounds__(64) void rm_ranged_kernel_t(const double *__restric
             d = mk(rd.x, rd.y, rd.z);
             r = Range{rr.t_min, rr.t_max};
         }
+        // a caller's ray may be off unit length within the assert: neither the boxes nor the cap of its range (a ray parameter
+        // against the reference's t) hold for it, and its wave takes the complete walk (rm_radiance_step.inc)
+        const SceneView sc = BVH ? complete_walk_view(stored, __any(on & off_unit(d))) : stored;
         if (KIND == RM_RANGED_OCCLUDED) {
             const bool occ = any_hit_ranged<BVH>(sc, o, d, !on, r);
             if (on) q.out[i] = occ ? 1u : 0u;
@@ -357,6 +365,7 @@ __global__ __launch_bounds__(64) void rm_ranged_kernel_t(const double *__restric
             if (on) store_hit(q, sc, q.hits + ((size_t)blockIdx.x * 64u + (threadIdx.x & 63u)), o, d, h, got);
         }
     } else if (KIND == RM_RANGED_SEGMENTS) {
+        const SceneView &sc = stored;                                     // (rays normalised here)
         // from[i] along normalized(to[i] - from[i]), the range [skin, L - skin]; an empty range sees
         bool empty = false;
         if (on) {
@@ -370,6 +379,7 @@ __global__ __launch_bounds__(64) void rm_ranged_kernel_t(const double *__restric
         const bool occ = any_hit_ranged<BVH>(sc, o, d, !on | empty, r);
         if (on) q.out[i] = (empty | !occ) ? 1u : 0u;
     } else {
+        const SceneView &sc = stored;
         // renderer.rs:166-174 for point i / n_lights and light i % n_lights
         if (on) {
             const size_t pt = i / q.n_lights;

@@ -16,7 +16,10 @@
 // vote and predicated inside (where<false> of rm_trace.inc, as the render's kernels with the bundle cull have it), and a lane
 // without a ray walks along with its `on` off.  Lanes past the last answer are such lanes from the start.
 //
-// Three things differ from the render on purpose:
+// Four things differ from the render on purpose:
+//   ray length        a caller's direction is unit only within the reference's assert, and the hierarchy's boxes and pruning
+//                     distance hold for unit rays: a step whose wave holds a ray that is not takes the complete walk
+//                     (rm_radiance_step.inc, complete_walk_view).
 //   viewer direction  direct_lighting takes normalize(origin - point) (renderer.rs:149).  The render hands shade_direct -dir,
 //                     sound for its unit rays; a caller's direction is unit only within the reference's assert and reflect()
 //                     does not renormalise (optics.rs:4-6), so here it is neg(normalized(dir)) at every step.  Everything
@@ -64,7 +67,8 @@ __global__ __launch_bounds__(64) void rm_radiance_kernel_t(const double *__restr
         }
     }
 
-    const V3 acc = radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth);   // rm_radiance_step.inc
+    // (ADMIT: a caller's ray may be off unit length within the assert; the sample rays are normalised and pass its vote)
+    const V3 acc = radiance_steps<BVH, POW, STACK, StoredLights, StoredSpheres, true>(sc, orig, dir, on, bg, q.max_depth);   // rm_radiance_step.inc
 
     // (the index formed again rather than held across the ray steps)
     const size_t at = (size_t)blockIdx.x * 64u + (threadIdx.x & 63u);

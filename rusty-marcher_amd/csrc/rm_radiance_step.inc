@@ -30,6 +30,24 @@ __device__ __forceinline__ SceneView global_scene_view(const double *__restrict_
     return sc;
 }
 
+// A caller's direction is admitted with |d.d - 1| < 1e-4 (include/rusty_marcher_amd.h), and the reference's sphere rule
+// (sphere.rs:27-45: tca = L.d, d2 = L.L - tca^2) is a geometric test only where d.d = 1: with d.d = 1 + e a sphere answers as
+// one of r^2 + e tca^2, and its t is not the parameter the slab test works in.  The hierarchy's boxes hold the true sphere
+// and the pruning distance compares the two, so neither is valid for such a ray: a wave that holds one takes the complete
+// walk -- the flat loops over the primitives in leaf order, ties by the list-order keys -- which is what this view selects
+// (closest_hit, any_hit and their ranged forms enter a hierarchy only where the header names one).  Wave-uniform: `any_off_unit`
+// is a vote.  RM_UNIT_SLACK: normalising in doubles leaves |d.d - 1| below 1e-15; within 1e-14 the boxes' margin of 2e-7 r
+// still holds for every sphere wider than 1.6e-4 of its distance (3e-5 for a ray unit to rounding), and the pruning margin
+// of 1e-7 is far off.
+#define RM_UNIT_SLACK 1e-14
+__device__ __forceinline__ bool off_unit(V3 d) { return __builtin_fabs(dot(d, d) - 1.) > RM_UNIT_SLACK; }
+__device__ __forceinline__ SceneView complete_walk_view(const SceneView &sc, bool any_off_unit) {
+    SceneView v = sc;
+    v.H.off_bvh_spheres = any_off_unit ? 0u : sc.H.off_bvh_spheres;
+    v.H.off_bvh_triangles = any_off_unit ? 0u : sc.H.off_bvh_triangles;
+    return v;
+}
+
 __device__ __forceinline__ uint8_t to_byte(double v) {                   // framebuffer.rs:80-82, the render epilogue's rule
     return (uint8_t)(255. * __builtin_fmin(__builtin_fmax(v, 0.), 1.));
 }
@@ -125,8 +143,10 @@ __device__ __forceinline__ V3 sample_direction(const A &q, bool oriented, double
 // What comes back along the lane's ray (orig, dir), cast as a primary ray (n_recursion = 1) with the cap max_depth >= 1; zero
 // for a lane whose `on` is off.  Called by whole waves.  `lights`: where the lane's lights stand at every step of its ray, the
 // children's included (rm_trace.inc, StoredLights: as the scene image says).  `spheres`: where the lane's spheres stand, in the
-// same way (StoredSpheres).
-template <bool BVH, int POW, int STACK, class LIGHTS = StoredLights, class SPHERES = StoredSpheres>
+// same way (StoredSpheres).  ADMIT: the rays are the caller's own (rm_radiance_rays): a step whose wave holds a ray that is
+// not unit -- the caller's, or a child of it: reflect() keeps the length (optics.rs:4-6) -- finds its closest hit by the
+// complete walk (complete_walk_view above).  The shadow rays are normalised and keep the hierarchy.
+template <bool BVH, int POW, int STACK, class LIGHTS = StoredLights, class SPHERES = StoredSpheres, bool ADMIT = false>
 __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 dir, bool on, const V3 bg, const uint32_t max_depth,
                                              const LIGHTS &lights = LIGHTS(), const SPHERES &spheres = SPHERES()) {
     double weight = 1.;
@@ -139,7 +159,11 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
 
     while (__any(on)) {                                                  // one ray step; the loop itself is wave-uniform
         Hit h{0., 0u};
-        const bool got = closest_hit<BVH, false, false>(sc, orig, dir, on, h, false, 0ull, spheres) & on;
+        // (two calls rather than one on `ADMIT && BVH ? complete_walk_view(...) : sc`: the conditional copies the view in every
+        // instantiation, and the objects of the families that do not admit -- refine, lens, accumulate, converge -- then differ)
+        bool got;
+        if (ADMIT && BVH) got = closest_hit<BVH, false, false>(complete_walk_view(sc, __any(on & off_unit(dir))), orig, dir, on, h, false, 0ull, spheres) & on;
+        else got = closest_hit<BVH, false, false>(sc, orig, dir, on, h, false, 0ull, spheres) & on;
         // what this step adds to the lane's answer: weight x (background + direct light) on a hit (renderer.rs:272-275),
         // weight x background where a child leaves the scene (:302-303), nothing where the caller's ray does (:305), + the
         // children beyond the cap (:262-264).  Lanes without a ray add zero.

@@ -837,8 +837,11 @@ __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, boo
 
     RayBox rb{};
     if (BVH) rb = ray_box(o, d);
-    // a box entered beyond the lane's best hit cannot improve it (margin: |d| = 1 +- 1e-16
-    // and, in the strict flavour, hits are ordered by |p - o|^2 rather than t)
+    // a box entered beyond the lane's best hit cannot improve it.  best_t is the reference's t = tca -+ thc, the box's entry a
+    // ray parameter: the two agree only as far as d.d = 1.  The margin covers the rays a kernel forms itself (normalised:
+    // |d.d - 1| < 1e-15) and, in the strict flavour, hits ordered by |p - o|^2 rather than t; it does NOT cover a caller's
+    // ray, admitted with |d.d - 1| < 1e-4 -- the kernels that take those walk without the hierarchy where a wave holds one
+    // (rm_radiance_step.inc, complete_walk_view).
     auto prune_at = [&]() { return c.hit ? c.best_t * (1. + 1e-7) + 1e-12 : __builtin_inf(); };
     auto off_lane = [&]() { return !on; };
 

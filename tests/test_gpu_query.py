@@ -535,7 +535,7 @@ def test_refusals(pkg, ctx):
             with pytest.raises(pkg.BackendError) as e:
                 call(oo, dd)
             assert e.value.status == B.RM_ERR_INVALID_ARG and "ray 2" in str(e.value)
-    ctx.intersect(np.zeros((1, 3)), np.array([[0., 0., -1.00004]]))                    # within the assert: answered
+    ctx.intersect(np.zeros((1, 3)), np.array([[0., 0., -1.00004]]))                    # within the assert: answered (and held to the oracle: tests/test_gpu_hierarchy_walk.py)
     # pixels outside the frame; the frame width need not be a multiple of 32 for a pick, it must for the buffer
     for x, y in ((320, 0), (0, 240), (10**6, 10**6)):
         with pytest.raises(pkg.BackendError) as e:
