@@ -142,7 +142,11 @@ typedef struct rm_params {
  * RM_FLAG_FAST_FP (opt-in, ~20 % faster): fused multiply-add, 1/sqrt by Newton iteration,
  * hits ordered by ray parameter.  Values move by ~1e-12; decisions can differ from the
  * reference ONLY at such exact-incidence pixels (the demo scene has a handful per frame
- * for some camera positions: its triangle has small-integer coordinates). */
+ * for some camera positions: its triangle has small-integer coordinates).
+ * The contract, as the tests hold it: a fast frame differs from the reference (by 1e-9 or
+ * more on a channel) only at pixels whose reference colour itself changes under a
+ * perturbation of at most 16 ulps of the primary ray's unit direction (exact zeros kept),
+ * and there it shows one of those colours -- never anything else. */
 #define RM_FLAG_FAST_FP 2u
 /* rm_render_device_u8 only: device_rgb8 holds just the OWNED patch rows, packed -- the
  * k-th owned patch row occupies byte rows [32k, 32k + 32) of a [n_owned*32][frame_width][3]

@@ -5,7 +5,7 @@ numpy exactly as the header states it -- d.c = (bx * right.c + by * up.c) + forw
 (renderer.rs:128-135) forms for the pixel, every operation rounded once -- normalised by orc_normalized and cast by
 orc_cast_ray(eye, dir, scene, (0.1, 0.1, 0.1), 1, max_depth).  A few lines of C compiled here (`orc_camera`) drive the oracle
 for a frame's rays on several threads.  Strict flavour: every channel of every pixel within TIGHT = 1e-9.  Fast flavour: the
-rule of tests/test_gpu_parity.py (FAST_TIE_PIXELS), copied.  Rows from height - height % 32 on are not rendered
+rule of tests/tie_reference.py (compare_fast): the same bound but at certified ties, and no tie where none is named.  Rows from height - height % 32 on are not rendered
 (renderer.rs:53) and must stay untouched."""
 import ctypes as C
 import os
@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import tie_reference as TR
 import workloads
 
 pytestmark = pytest.mark.gpu
@@ -21,8 +22,6 @@ pytestmark = pytest.mark.gpu
 TIGHT = 1e-9
 RM_FLAG_FAST_FP = 2
 RM_FLAG_U8_COMPACT = 4
-# fast flavour only: pixels whose decision may legitimately differ (exact-incidence ties) -- tests/test_gpu_parity.py
-FAST_TIE_PIXELS = lambda n_px: max(8, n_px // 50000)
 LIT_FLOOR = 0.05                      # share of the oracle's own frame that is not sky: no view passes vacuously
 
 CAMERA_C = r"""
@@ -197,16 +196,15 @@ def device_frame(ctx, p, sentinel=-1.):
     return dev.cpu().numpy()
 
 
-def compare(gpu, ref, label, tol=TIGHT):
-    """tests/test_gpu_parity.py compare(): strict -- every channel within tol; fast -- the same bound but for at most
-    FAST_TIE_PIXELS pixels.  Returns (worst delta among the pixels held to the bound, tie pixels seen)."""
+def compare(gpu, ref, label, tol=TIGHT, tie=None):
+    """strict -- every channel within tol; fast -- tests/tie_reference.py compare_fast: the same bound but at the certified
+    ties of `tie` (a tie_reference.Tie; None: the frame may differ nowhere).  Returns (worst delta among the pixels held to
+    the bound, differing pixels seen)."""
     d = np.abs(gpu - ref)
     if _FLAGS["value"] & RM_FLAG_FAST_FP:
-        bad = d.reshape(-1, 3).max(axis=1) >= tol
-        allowed = FAST_TIE_PIXELS(bad.size)
-        print("%s: fast flavour, %d tie pixels (allowed %d)" % (label, int(bad.sum()), allowed))
-        assert int(bad.sum()) <= allowed, "%s: %d pixels differ (fast flavour allows %d ties)" % (label, int(bad.sum()), allowed)
-        return (float(d.reshape(-1, 3)[~bad].max()) if (~bad).any() else 0.), int(bad.sum())
+        worst, n_bad = TR.compare_fast(gpu, ref, tol, tie, label)
+        print("%s: fast flavour, %d differing pixels" % (label, n_bad))
+        return worst, n_bad
     worst = float(d.max())
     print("%s: strict flavour, max |delta| %.3e" % (label, worst))
     assert worst < tol, "%s: max |delta| %.3e (channels above 1e-12: %d)" % (label, worst, int((d > 1e-12).sum()))

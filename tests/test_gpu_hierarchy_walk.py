@@ -354,8 +354,8 @@ def guarded_frame(ctx, p):
 @WHICH
 def test_deep_tree_render(pkg, contexts, chains, orc, which, flavour, camera):
     """rm_render_device, 64 x 64, depth 3 and 6.  Measured on an MI355X: strict within 5.6e-16 of the oracle on the
-    sphere chain and 5.7e-15 on the mesh chain; the fast flavour within 9.9e-13, no tie pixel (tests/test_gpu_parity.py
-    FAST_TIE_PIXELS allows some)."""
+    sphere chain and 5.7e-15 on the mesh chain; the fast flavour within 9.9e-13, no differing pixel (none is
+    allowed: tests/tie_reference.py compare_fast with no ties named)."""
     import render_matrix as RM
     ch = chains(which)
     load(pkg, contexts, ch)

@@ -6,8 +6,8 @@ tests/test_render_matrix.py.
 A case is a row (flavour, camera, group, edges, order) and loops over the seven depths and the two powerings: 14 launches
 through rm_render_device into a caller-owned buffer that holds a sentinel beforehand.  Before each launch rm_kernel_name
 must name the instantiation the cell claims.  Strict flavour: every channel of every pixel within TIGHT = 1e-9 of the
-oracle.  Fast flavour: the rule of tests/test_gpu_parity.py's compare() -- the same bound, with at most FAST_TIE_PIXELS
-pixels outside it.  Two launches that differ only in a knob no answer may depend on (the dispatch order, the cull's edge
+oracle.  Fast flavour: the rule of tests/tie_reference.py's compare_fast -- the same bound but at certified ties, and these
+frames name none: no pixel may differ.  Two launches that differ only in a knob no answer may depend on (the dispatch order, the cull's edge
 test, the tile-level feedback), within one flavour and camera, must be equal bit for bit.  The contexts are made under the
 rows' environments (the knobs are read at rm_init), each once, in this one process."""
 import os
@@ -19,6 +19,7 @@ import pytest
 import radiance_reference as RR
 import render_matrix as RM
 import test_gpu_parity as GP
+import tie_reference as TR
 
 pytestmark = pytest.mark.gpu
 
@@ -90,15 +91,12 @@ def device_frame(ctx, p):
     return dev.cpu().numpy()
 
 
-def compare(gpu, ref, fast, label):
-    """tests/test_gpu_parity.py compare() -> (largest deviation among the pixels held to the bound, tie pixels)."""
+def compare(gpu, ref, fast, label, tie=None):
+    """-> (largest deviation among the pixels held to the bound, differing pixels); fast: tests/tie_reference.py compare_fast,
+    the differing pixels certified by `tie` (a tie_reference.Tie; None: none may differ)."""
     d = np.abs(gpu - ref)
     if fast:
-        bad = d.reshape(-1, 3).max(axis=1) >= TIGHT
-        allowed = GP.FAST_TIE_PIXELS(bad.size)
-        assert int(bad.sum()) <= allowed, "%s: %d pixels differ (fast flavour allows %d ties): %s" % (
-            label, int(bad.sum()), allowed, [(int(i) % RM.W, int(i) // RM.W) for i in np.flatnonzero(bad)[:32]])
-        return (float(d.reshape(-1, 3)[~bad].max()) if (~bad).any() else 0.), int(bad.sum())
+        return TR.compare_fast(gpu, ref, TIGHT, tie, label)
     worst = float(d.max())
     assert worst < TIGHT, "%s: max |delta| %.3e (channels above 1e-12: %d)" % (label, worst, int((d > 1e-12).sum()))
     return worst, 0
