@@ -1317,6 +1317,101 @@ rm_status rm_render_converging_moving(rm_ctx *ctx, const rm_params *params, cons
                                       double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
                                       rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
 
+/* ---- moving camera: shutter blur of the view, in progressive and in converging frames ----------
+ * The sampled frames give every sample a lens point, light positions and shape positions of its
+ * own; these calls give it a camera of its own as well: the sixth and seventh members of the
+ * family.  Additive to ABI version 5; a host detects them by " moving-camera" in rm_build_info().
+ *
+ * A camera table is [rows][12] doubles: (off.x, off.y, off.z, right.xyz, up.xyz, forward.xyz).  The
+ * sample that is row r of the tables sees the camera at cam'.c = cam.c + off[r].c -- one addition,
+ * rounded once, cam the context's position -- with the row's own basis: absolute, not an offset.
+ * Steps 1-4 of the thin-lens camera take cam' and the row's basis in place of the context's, word
+ * for word:
+ *   D = (bx*right + by*up) + forward      always the oriented formula, whatever the context's
+ *                                         oriented flag says;
+ *   F.c = cam'.c + D.c*focus;   O.c = cam'.c + ((au*right.c) + (av*up.c));
+ *   aperture == 0 keeps origin cam' and direction normalized(D).
+ * Step 5 and everything after it is the member's underneath: the light rule, the shape rule, fold,
+ * mean, bytes, stats and count.  A static scene keeps its hierarchy: no box, pid map or record
+ * depends on where a ray starts.
+ *
+ * Consequences:
+ *   - with every off +0. or -0. and every basis row equal to the basis of an ORIENTED context, a
+ *     pass is byte for byte the underlying pass -- rm_accumulate_soft_device where no shape table is
+ *     given, rm_accumulate_moving_device where one is, rm_accumulate_converging_device (with
+ *     offsets) and rm_accumulate_converging_moving_device for the converging calls -- for camera
+ *     coordinates that are not -0.;
+ *   - under a context that is not oriented the pass still uses the oriented formula with the rows
+ *     as given.  Against the fixed view's pass it may differ in the sign of a zero direction
+ *     component (by is -0 on the row sy = height/2, and (bx*0 + by*1) + 0 is +0), so that
+ *     comparison holds to the parity bound, not to bytes;
+ *   - with every row holding the same off and the same basis B, a pass is byte for byte the
+ *     underlying pass of a context whose camera was set to fl(cam + off) by rm_camera_update and to
+ *     B by rm_camera_orient.
+ *
+ * rm_camera_motion: velocity in world units a unit of time; yaw, pitch and roll in radians a unit
+ * of time, about the axes and with the signs of rm_camera_basis_turn.
+ *
+ * rm_camera_sequence is host arithmetic only.  Row s: t = shutter * phi_17(s), the same instant
+ * rm_motion_sequence gives row s, so the camera and the shapes of a sample share it; off =
+ * velocity.c * t; the basis is rm_camera_basis_turn(basis, yaw*t, pitch*t, roll*t).  Where all
+ * three rates compare equal to 0 every row holds `basis` byte for byte, with no
+ * re-orthonormalisation: a camera that only translates keeps the context's basis exactly.
+ * Refusals are rm_motion_sequence's, a non-finite motion, and a basis rm_camera_basis_check
+ * refuses; a refused call writes nothing.
+ *
+ * rm_accumulate_camera_device has rm_accumulate_moving_device's checks.  device_camera_rows must
+ * not be NULL.  device_shape_offsets == NULL is allowed: no shape moves, n_shapes is not looked at
+ * and the launch takes the static scene's kernels.  The tables' contents are a precondition: a
+ * non-finite entry gives unspecified pixels (a ray that is not a number hits nothing), never a
+ * fault; nothing read from a camera row forms an address.  rm_accumulate_converging_camera_device is rm_accumulate_converging_moving_device's
+ * list plus device_camera_rows of table_rows rows, and allows a NULL shape table likewise.  The
+ * lane that casts sample s of a listed pixel with count n holds row r = n + s of all four tables;
+ * the select rule is unchanged.  So a pixel with count c holds byte for byte what
+ * rm_accumulate_camera_device leaves after c rows, however the passes were sliced.
+ *
+ * The ticks are rm_render_progressive_moving's and rm_render_converging_moving's on the same
+ * context-owned state, with `motion` (not NULL, six finite numbers) and a staged slice, or a fourth
+ * resident prefix, of rm_camera_sequence, whose `basis` is what rm_camera_get reports.  The key is
+ * extended by the bytes of *motion and the shutter, and the frames are their own: a switch to or
+ * from any sibling tick begins the frame again.  velocities == NULL: no shape moves, no shape
+ * table is kept and the static scene's kernels run; velocities given, zeros included, are the
+ * moving shapes' rules.  Saturation, rows == 0, refusals that change neither N nor key, timing and
+ * report are the siblings'.
+ *
+ * Cost: the member's underneath plus twelve per-lane loads and three additions a group of rays.
+ * Not here: camera paths that are not linear within the shutter (the device calls take any table).
+ */
+typedef struct rm_camera_motion {
+    rm_vec3 velocity;
+    double  yaw, pitch, roll;
+} rm_camera_motion;        /* 48 bytes */
+
+rm_status rm_camera_sequence(uint32_t first, uint32_t count, const rm_camera_motion *motion, const rm_camera_basis *basis,
+                             double shutter, double *rows);
+rm_status rm_accumulate_camera_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                      const void *device_camera_rows, const void *device_light_offsets, uint32_t n_lights,
+                                      const void *device_shape_offsets /* NULL: no shape moves */, uint32_t n_shapes,
+                                      uint32_t n_before, void *device_sum, void *device_mean /* optional */,
+                                      void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_accumulate_converging_camera_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                                 const rm_converge *converge, const void *device_table, uint32_t table_rows,
+                                                 const void *device_camera_rows, const void *device_light_offsets,
+                                                 uint32_t n_lights, const void *device_shape_offsets /* NULL: no shape moves */,
+                                                 uint32_t n_shapes, int fresh, const rm_converge_frame *buffers, void *hip_stream);
+rm_status rm_render_progressive_camera(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                       const double *radii /* NULL: point lights */, uint32_t n_lights,
+                                       const rm_vec3 *velocities /* NULL: no shape moves */, uint32_t n_shapes, double shutter,
+                                       const rm_camera_motion *motion, int restart,
+                                       double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                       uint32_t *n_total /* optional */, rm_timing *timing /* optional */);
+rm_status rm_render_converging_camera(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                                      const double *radii /* NULL: point lights */, uint32_t n_lights,
+                                      const rm_vec3 *velocities /* NULL: no shape moves */, uint32_t n_shapes, double shutter,
+                                      const rm_camera_motion *motion, int restart,
+                                      double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                      rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

@@ -130,6 +130,11 @@ class rm_camera_basis(C.Structure):
     _fields_ = [("right", rm_vec3), ("up", rm_vec3), ("forward", rm_vec3)]
 
 
+class rm_camera_motion(C.Structure):
+    """How the camera moves while the shutter stands open: velocity, and yaw, pitch and roll rates in radians (48 bytes)."""
+    _fields_ = [("velocity", rm_vec3), ("yaw", C.c_double), ("pitch", C.c_double), ("roll", C.c_double)]
+
+
 _P = C.POINTER
 _VP = C.c_void_p
 
@@ -248,6 +253,17 @@ SIGNATURES = {
     "rm_render_converging_moving": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, _P(rm_vec3),
                                               C.c_uint32, C.c_double, C.c_int, _P(C.c_double), _P(C.c_uint8), _P(rm_converge_report),
                                               _P(rm_timing)]),
+    "rm_camera_sequence": (C.c_int, [C.c_uint32, C.c_uint32, _P(rm_camera_motion), _P(rm_camera_basis), C.c_double, _P(C.c_double)]),
+    "rm_accumulate_camera_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP,
+                                              _VP, _VP]),
+    "rm_accumulate_converging_camera_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, _VP, C.c_uint32,
+                                                         _VP, C.c_uint32, C.c_int, _P(rm_converge_frame), _VP]),
+    "rm_render_progressive_camera": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), C.c_uint32, _P(rm_vec3), C.c_uint32,
+                                               C.c_double, _P(rm_camera_motion), C.c_int, _P(C.c_double), _P(C.c_uint8), _P(C.c_uint32),
+                                               _P(rm_timing)]),
+    "rm_render_converging_camera": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, _P(rm_vec3),
+                                              C.c_uint32, C.c_double, _P(rm_camera_motion), C.c_int, _P(C.c_double), _P(C.c_uint8),
+                                              _P(rm_converge_report), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -139,6 +139,34 @@ def _shutter(shutter):
     return float(shutter)
 
 
+def _camera_motion(velocity, turn):
+    """rm_camera_motion of a camera's velocity (three finite numbers) and its yaw, pitch and roll rates (three more)."""
+    try:
+        v = (velocity.x, velocity.y, velocity.z) if hasattr(velocity, "x") else tuple(float(c) for c in velocity)
+        t = tuple(float(c) for c in turn)
+    except (TypeError, ValueError):
+        raise ValueError("camera velocity and turn must be vectors of three numbers, got %r and %r" % (velocity, turn))
+    if len(v) != 3 or len(t) != 3 or not np.isfinite(v + t).all():
+        raise ValueError("camera velocity and turn must be three finite numbers each, got %r and %r" % (velocity, turn))
+    return _lib.rm_camera_motion(_lib.rm_vec3(*(float(c) for c in v)), *t)
+
+
+def _camera_rows_tensor(rows, n_rows, device):
+    """A camera table as a contiguous float64 tensor (n_rows, 12) on `device`: a tensor is checked, an array is checked (finite)
+    and copied over."""
+    torch = _torch()
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[0] != n_rows or rows.shape[1] != 12 or not rows.is_contiguous():
+            raise ValueError("camera_rows must be a contiguous float64 torch tensor of shape (%d, 12)" % n_rows)
+        if rows.device != device:
+            raise ValueError("camera_rows must live on %s, not %s" % (device, rows.device))
+        return rows
+    r = np.ascontiguousarray(rows, dtype=np.float64)
+    if r.ndim != 2 or r.shape[0] != n_rows or r.shape[1] != 12 or not np.isfinite(r).all():
+        raise ValueError("camera_rows must be a finite float64 array of shape (%d, 12), got %s" % (n_rows, r.shape))
+    return torch.from_numpy(r).to(device)
+
+
 def _sequence_rows(first, count):
     """first and count of a sequence call: non-negative integers with first + count <= RM_PROGRESSIVE_MAX_SAMPLES."""
     for name, v in (("first", first), ("count", count)):
@@ -969,6 +997,96 @@ class Context:
                                                       *host, C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
+    # ---- moving camera (include/rusty_marcher_amd.h, "moving camera") ----
+    def camera_sequence(self, first, count, velocity, shutter, turn=(0., 0., 0.), basis=None):
+        """camera_sequence of this module with the basis the context renders with where none is given."""
+        return camera_sequence(first, count, velocity, shutter, turn, self.camera()[1] if basis is None else basis)
+
+    def accumulate_camera_device(self, params, sum, aperture, focus, table, camera_rows, light_offsets, shape_offsets, n_before, mean=None,
+                                 rgb8=None, stream=None):
+        """rm_accumulate_camera_device: accumulate_moving_device in which the camera moves as well -- sample row s sees the scene
+        from the context's camera + camera_rows[s][0:3] along the basis camera_rows[s][3:12] (right, up, forward).  camera_rows:
+        (n_samples, 12); shape_offsets: None where no shape moves -- the scene keeps its hierarchy then.  Tables as
+        accumulate_moving_device's.  -> (the table's tensor, the camera rows', the light offsets', the shape offsets' or None)."""
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        camera_rows = _camera_rows_tensor(camera_rows, lens.n_samples, sum.device)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", lens.n_samples, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), 0
+        if shape_offsets is not None:
+            shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", lens.n_samples, sum.device)
+            n_shapes = int(shape_offsets.shape[1])
+        _lib.check(self.L.rm_accumulate_camera_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                      C.c_void_p(camera_rows.data_ptr()),
+                                                      C.c_void_p(light_offsets.data_ptr()) if n_lights > 0 else None, n_lights,
+                                                      C.c_void_p(shape_offsets.data_ptr()) if n_shapes > 0 else None, n_shapes, int(n_before),
+                                                      C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                      C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                      C.c_void_p(self._stream(stream))), self.ptr)
+        return table, camera_rows, light_offsets, shape_offsets
+
+    def render_progressive_camera(self, params, camera_velocity, shutter, aperture, focus, n_samples, turn=(0., 0., 0.), velocities=None,
+                                  radii=None, restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_progressive_camera: render_progressive_moving with a camera that moves by camera_velocity and turns by
+        `turn` = (yaw, pitch, roll) rates while the shutter stands open.  velocities: None where no shape moves.  Its frames are
+        its own: a switch to or from any other tick begins the frame again.  -> (rm_timing, samples a pixel in the frame now)."""
+        lens = _lens(aperture, focus, n_samples)
+        motion, shutter = _camera_motion(camera_velocity, turn), _shutter(shutter)
+        v = _velocities(velocities) if velocities is not None else None
+        r = _radii(radii) if radii is not None else None
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing, total = _lib.rm_timing(), C.c_uint32(0)
+        _lib.check(self.L.rm_render_progressive_camera(self.ptr, C.byref(params), C.byref(lens),
+                                                       r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                       r.shape[0] if r is not None else 0,
+                                                       v.ctypes.data_as(C.POINTER(_lib.rm_vec3)) if v is not None else None,
+                                                       v.shape[0] if v is not None else 0, shutter, C.byref(motion), 1 if restart else 0,
+                                                       *host, C.byref(total), C.byref(timing)), self.ptr)
+        return timing, total.value
+
+    # ---- converging frames with a moving camera (include/rusty_marcher_amd.h, "moving camera") ----
+    def accumulate_converging_camera_device(self, params, sum, stats, count, aperture, focus, n_samples, table, camera_rows, light_offsets,
+                                            shape_offsets, tolerance, min_samples, max_samples, fresh, mean=None, rgb8=None, mask=None,
+                                            workspace=None, stream=None):
+        """rm_accumulate_converging_camera_device: accumulate_converging_moving_device in which the camera moves as well -- the
+        sample that is row r of the tables sees the scene from the camera of camera_rows[r], (rows, 12).  shape_offsets: None
+        where no shape moves.  -> the workspace, as accumulate_converging_device."""
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
+        rows = int(table.shape[0])
+        camera_rows = _camera_rows_tensor(camera_rows, rows, sum.device)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", rows, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), 0
+        if shape_offsets is not None:
+            shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", rows, sum.device)
+            n_shapes = int(shape_offsets.shape[1])
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        _lib.check(self.L.rm_accumulate_converging_camera_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), rows,
+                                                                 vp(camera_rows), vp(light_offsets) if n_lights > 0 else None, n_lights,
+                                                                 vp(shape_offsets) if n_shapes > 0 else None, n_shapes, 1 if fresh else 0,
+                                                                 C.byref(frame), C.c_void_p(self._stream(stream))), self.ptr)
+        return workspace
+
+    def render_converging_camera(self, params, camera_velocity, shutter, aperture, focus, n_samples, tolerance, min_samples, max_samples,
+                                 turn=(0., 0., 0.), velocities=None, radii=None, restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_converging_camera: render_converging_moving with a camera that moves by camera_velocity and turns by `turn`
+        while the shutter stands open.  velocities: None where no shape moves.  Its frames are its own.
+        -> (rm_timing, rm_converge_report)."""
+        lens = _lens(aperture, focus, n_samples)
+        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
+        motion, shutter = _camera_motion(camera_velocity, turn), _shutter(shutter)
+        v = _velocities(velocities) if velocities is not None else None
+        r = _radii(radii) if radii is not None else None
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing, report = _lib.rm_timing(), _lib.rm_converge_report()
+        _lib.check(self.L.rm_render_converging_camera(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
+                                                      r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                      r.shape[0] if r is not None else 0,
+                                                      v.ctypes.data_as(C.POINTER(_lib.rm_vec3)) if v is not None else None,
+                                                      v.shape[0] if v is not None else 0, shutter, C.byref(motion), 1 if restart else 0,
+                                                      *host, C.byref(report), C.byref(timing)), self.ptr)
+        return timing, report
+
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole
         patch rows), as DeviceHits of [frame_height][frame_width].  `out`: a float64 tensor of shape
@@ -1111,3 +1229,16 @@ def basis_turn(basis, yaw=0., pitch=0., roll=0.):
     out = _lib.rm_camera_basis()
     _lib.check(_lib.lib().rm_camera_basis_turn(C.byref(_lib.camera_basis(basis)), float(yaw), float(pitch), float(roll), C.byref(out)))
     return out
+
+
+# ---- the moving camera's host arithmetic (no GPU, no context) ----
+def camera_sequence(first, count, velocity, shutter, turn=(0., 0., 0.), basis=FIXED_VIEW):
+    """rm_camera_sequence: rows first .. first + count - 1 of the library's camera sequence, (count, 12) float64 rows (offset,
+    right, up, forward): row s moves the camera by velocity times the row's time within the shutter -- rm_motion_sequence's time
+    for that row -- and turns `basis` by turn = (yaw, pitch, roll) rates times it.  Rates of zero keep the basis byte for byte."""
+    first, count = _sequence_rows(first, count)
+    motion, shutter = _camera_motion(velocity, turn), _shutter(shutter)
+    rows = np.zeros((int(count), 12), dtype=np.float64)
+    _lib.check(_lib.lib().rm_camera_sequence(int(first), int(count), C.byref(motion), C.byref(_lib.camera_basis(basis)), shutter,
+                                             rows.ctypes.data_as(C.POINTER(C.c_double))))
+    return rows

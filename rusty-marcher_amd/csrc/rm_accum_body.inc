@@ -1,7 +1,8 @@
 // rm_accum_body.inc -- the body the kernels of the progressive frames share: rm_accum.hip's (lights where the scene image says),
 // rm_soft.hip's (lights moved by the lane's row of an offset table), rm_motion.hip's (spheres moved as well) and
 // rm_motion_shapes.hip's (every shape moved).  Included
-// behind rm_radiance_step.inc.
+// behind rm_radiance_step.inc.  rm_camera.hip's kernels (the camera moved as well) include it behind rm_camera_ray.inc with
+// RM_CAMERA_ROWS defined, which no other unit does: every other unit sees the tokens it always saw.
 //
 // `lights_of(s)`: the rule that says where the lights of table row s stand (rm_trace.inc, StoredLights), asked once a lane
 // before the loop over the groups; `spheres_of(s)`: the same for the spheres (StoredSpheres where none is given).  `bstack` (64 words) and `sums` (64 x 3 doubles) are the workgroup's LDS.
@@ -16,6 +17,9 @@ struct stored_spheres_of {
 
 template <bool BVH, int POW, int STACK, class LIGHTS_OF, class SPHERES_OF = stored_spheres_of>
 __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blob, const AccumArgs &a, uint32_t *bstack, double *sums,
+#ifdef RM_CAMERA_ROWS
+                                            const double *__restrict__ camera_rows,   // [n_samples][12]: rmcamera::camera_row_ray
+#endif
                                             LIGHTS_OF lights_of, SPHERES_OF spheres_of = SPHERES_OF()) {
     const LensArgs &q = a.L;
     const SceneView sc = global_scene_view(scene_blob, q.H, bstack);
@@ -30,9 +34,11 @@ __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blo
     const auto lights = lights_of(s);
     const auto spheres = spheres_of(s);
     const V3 bg = mk(q.bg_x, q.bg_y, q.bg_z);
+#ifndef RM_CAMERA_ROWS
     const V3 cam = mk(q.cam_x, q.cam_y, q.cam_z);
     const V3 lens = mk(q.cam_x + ((au * q.cam_rx) + (av * q.cam_ux)), q.cam_y + ((au * q.cam_ry) + (av * q.cam_uy)),
                        q.cam_z + ((au * q.cam_rz) + (av * q.cam_uz)));
+#endif
     const bool pinhole = q.aperture == 0.;                               // wave-uniform
     const bool resume = a.n_before > 0u;                                 // wave-uniform
     const double div = (double)(a.n_before + ns);                        // (at most 65536: the host checked)
@@ -44,6 +50,11 @@ __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blo
         V3 orig = mk(0., 0., 0.), dir = mk(0., 0., -1.);                 // (a lane without a sample holds a harmless ray it never casts)
         if (on) {
             const double sx = (double)(pix % q.frame_width) + dx, sy = (double)(pix / q.frame_width) + dy;
+#ifdef RM_CAMERA_ROWS
+            // the row is fetched here, a group at a time, not in front of the loop: twelve values alive across the ray walk
+            // cost a wave a SIMD (rm_camera.hip, the head of the file)
+            rmcamera::camera_row_ray(q, camera_rows + 12u * s, sx, sy, au, av, pinhole, orig, dir);
+#else
             const V3 D = sample_direction(q, q.oriented != 0u, sx, sy);
             if (pinhole) {
                 orig = cam;
@@ -53,6 +64,7 @@ __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blo
                 orig = lens;
                 dir = normalized(F - lens);
             }
+#endif
         }
         const V3 acc = q.max_depth == 0u ? bg : radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights, spheres);
         sums[lane * 3u] = acc.x; sums[lane * 3u + 1u] = acc.y; sums[lane * 3u + 2u] = acc.z;

@@ -70,6 +70,11 @@ static rm_status check_rules(rm_ctx *ctx, const char *who, const rm_sampling_rul
         if (rm_status lst = check_soft_lights(ctx, who, r.n_lights)) return lst;
         if (rm_status rst = host_refusal(ctx, rm_check_radii(who, r.radii, r.n_lights))) return rst;
     }
+    if (r.camera) {                                                        // (the moving camera's ticks: a shutter without velocities too)
+        if (rm_status mst = host_refusal(ctx, rm_check_camera_motion(who, r.camera))) return mst;
+        if (!r.motion)
+            if (rm_status sst = host_refusal(ctx, rm_check_velocities(who, nullptr, 0u, r.shutter))) return sst;
+    }
     if (!r.motion) return RM_OK;
     if (rm_status sst = check_motion_shapes(ctx, who, r.n_shapes)) return sst;
     if (rm_status vst = host_refusal(ctx, rm_check_velocities(who, r.velocities, r.n_shapes, r.shutter))) return vst;

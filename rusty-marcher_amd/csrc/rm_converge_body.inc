@@ -9,6 +9,8 @@
 //   bstack, sums         the workgroup's LDS: 64 words and 64 x 3 doubles
 //   lights_of(r)         the rule that says where the lights of table row r stand (rm_trace.inc: StoredLights, OffsetLights)
 //   spheres_of(r)        the same for the spheres (StoredSpheres, OffsetSpheres) or for every shape (OffsetShapes)
+//   camera_rows          rm_converge_camera.hip alone, which defines RM_CAMERA_ROWS and includes rm_camera_ray.inc: the camera
+//                        table, [table_rows][12].  No other unit defines the symbol: each sees the tokens it always saw.
 //
 // -- the parameters of rm_accum_body.inc's accum_shade, with one difference: both rules are asked inside the loop over the
 // groups, once a lane and group, with the lane's own row r = count[pixel] + sample.  r < table_rows in every lane, idle ones
@@ -31,7 +33,9 @@
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t slot = lane / ns, s = lane % ns;                      // the lane's list entry within the group, its sample of that pixel
     const V3 bg = mk(q.bg_x, q.bg_y, q.bg_z);
+#ifndef RM_CAMERA_ROWS
     const V3 cam = mk(q.cam_x, q.cam_y, q.cam_z);
+#endif
     const bool pinhole = q.aperture == 0.;                               // wave-uniform
 
     for (uint32_t g = blockIdx.x; (unsigned long long)g * P < listed; g += gridDim.x) {
@@ -46,6 +50,9 @@
         V3 orig = mk(0., 0., 0.), dir = mk(0., 0., -1.);                 // (a lane without a sample holds a harmless ray it never casts)
         if (on) {
             const double sx = (double)(pix % q.frame_width) + row[0], sy = (double)(pix / q.frame_width) + row[1];
+#ifdef RM_CAMERA_ROWS
+            rmcamera::camera_row_ray(q, camera_rows + 12u * (size_t)r, sx, sy, q.aperture * row[2], q.aperture * row[3], pinhole, orig, dir);
+#else
             const V3 D = sample_direction(q, q.oriented != 0u, sx, sy);
             if (pinhole) {
                 orig = cam;
@@ -58,6 +65,7 @@
                 orig = lens;
                 dir = normalized(F - lens);
             }
+#endif
         }
         V3 acc = bg;
         if (q.max_depth != 0u)                                           // wave-uniform

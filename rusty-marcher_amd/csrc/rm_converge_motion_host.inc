@@ -26,7 +26,14 @@ static rm_status launch_converge_motion(rm_ctx *ctx, const rm_params *p, const r
     return launch_converge_with(ctx, shade_family{"converging with moving spheres", rm_converge_motion_kernel}, m, m.C, stream);
 }
 
-// A resident prefix of a sequence: rows [0, rows) of `columns` doubles each (the lens table: 4; an offset table: 3 a light or shape)
+// The moving camera's three steps (rm_camera_host.inc, behind this file): launch_converge_moving's with the camera's rows;
+// shape_offsets NULL: no shape moves
+static rm_status launch_converge_camera(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                        uint32_t table_rows, const void *offsets, const void *shape_offsets, const void *camera_rows, int fresh,
+                                        const rm_converge_frame *b, hipStream_t stream);
+
+// A resident prefix of a sequence: rows [0, rows) of `columns` doubles each (the lens table: 4; an offset table: 3 a light or
+// shape; the camera table: 12)
 struct rm_resident_prefix {
     void *d = nullptr;
     uint32_t room = 0, rows = 0;             // rows d has room for / holds
@@ -36,6 +43,7 @@ struct rm_resident_prefix {
 // The converging state of a context (rm_ctx::converging; made on the first call, released by rm_destroy)
 struct rm_converging {
     rm_resident_prefix table{nullptr, 0u, 0u, 4u}, lights, shapes;   // of rm_lens_sequence, of rm_light_sequence (or zeros) and of rm_motion_sequence
+    rm_resident_prefix camera;                       // ... and of rm_camera_sequence (the moving camera's tick)
     bool lights_zero = false;                        // `lights` holds zeros: a motion tick's point lights (else rm_light_sequence of id.radii)
     void *d_sum = nullptr, *d_stats = nullptr, *d_count = nullptr, *d_ws = nullptr, *d_mean = nullptr, *d_rgb8 = nullptr;
     size_t pixels = 0;                               // the six buffers have room for that many
@@ -52,7 +60,7 @@ struct rm_converging {
 static void converging_destroy(rm_ctx *ctx, bool device_ok) {
     rm_converging *g = ctx->converging;
     if (!g) return;
-    for (void *b : {g->table.d, g->lights.d, g->shapes.d, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8})
+    for (void *b : {g->table.d, g->lights.d, g->shapes.d, g->camera.d, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8})
         if (b && device_ok) (void)hipFree(b);
     delete g;
     ctx->converging = nullptr;
@@ -105,7 +113,8 @@ using converge_motion_launch = rm_status (*)(rm_ctx *ctx, const rm_params *p, co
                                              uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
                                              const rm_converge_frame *b, hipStream_t stream);
 
-// The tick of the three calls; `rules` says which, and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
+// The tick of the four calls; `rules` says which (rules.camera: the moving camera's, rm_camera_host.inc, which keeps a prefix of
+// rm_camera_sequence as well and launches its own kernels), and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
 // which a velocity on any shape is obeyed and a shape table is kept whenever the scene holds a shape; key.motion = 2 keeps its
 // frames apart from the moving spheres') from the moving spheres': checked here, the prefixes they ask for kept resident, the
 // launch by them.
@@ -141,6 +150,8 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                 const bool lights_stay = g.lights_zero == staged.light_zeros && (staged.light_zeros || rm_same_radii(g.id, id));
                 if (!lights_stay) g.lights.rows = 0u;
                 g.shapes.rows = 0u;
+                g.camera.rows = 0u;                                        // (a function of the motion, the shutter and the basis)
+                if (rm_status rst = converging_recolumn(ctx, g.camera, rules.camera ? 12u : 0u)) return rst;
                 if (rm_status rst = converging_recolumn(ctx, g.lights, staged.light_columns * 3u)) return rst;
                 if (rm_status rst = converging_recolumn(ctx, g.shapes, staged.shape_columns * 3u)) return rst;
                 g.lights_zero = staged.light_zeros;
@@ -165,12 +176,23 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                         return rm_fill_shape_rows(rules, first, count, out);
                     }))
                     return est;
+            if (rules.camera) {
+                const rm_camera_basis basis = reported_basis(ctx);
+                if (rm_status est = converging_extend(ctx, g, g.camera, need, [&](uint32_t first, uint32_t count, double *out) {
+                        return host_refusal(ctx, rm_camera_sequence(first, count, rules.camera, &basis, rules.shutter, out));
+                    }))
+                    return est;
+            }
             const rm_converge_frame b{g.d_sum, g.d_stats, g.d_count, g.d_ws, g.d_mean, g.d_rgb8, nullptr};
             // (the kernel is told what is resident -- at least `need` rows of every sequence -- so its clamp guards the buffers' end)
             uint32_t resident = g.table.rows;
             if (offsets) resident = std::min(resident, g.lights.rows);
             if (shapes) resident = std::min(resident, g.shapes.rows);
+            if (rules.camera) resident = std::min(resident, g.camera.rows);
             auto launch = [&]() {
+                if (rules.camera)
+                    return launch_converge_camera(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, shapes ? g.shapes.d : nullptr,
+                                                  g.camera.d, g.n == 0u, &b, ctx->stream);
                 if (any_shape)
                     return any_shape(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, shapes ? g.shapes.d : nullptr,
                                      g.n == 0u, &b, ctx->stream);

@@ -33,6 +33,8 @@
 #include "rm_converge.hpp"
 #include "rm_converge_motion.hpp"
 #include "rm_converge_moving.hpp"
+#include "rm_camera.hpp"
+#include "rm_converge_camera.hpp"
 
 using namespace rmdev;
 
@@ -335,7 +337,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes converge-moving converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera converge-moving converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1128,3 +1130,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_converge_host.inc"
 #include "rm_converge_motion_host.inc"
 #include "rm_converge_moving_host.inc"
+#include "rm_camera_host.inc"

@@ -25,6 +25,16 @@ static rm_status launch_motion(rm_ctx *ctx, const accum_call &c, const void *off
 // A launch with launch_motion's arguments: the moving shapes' tick (rm_motion_shapes_host.inc) hands the tick below its own
 using motion_launch = rm_status (*)(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets);
 
+// The moving camera's launch (rm_camera_host.inc, behind this file): launch_moving's with the camera's rows; shape_offsets NULL:
+// no shape moves
+static rm_status launch_camera(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets, const void *camera_rows);
+
+// The basis rm_camera_get reports: the context's where it is oriented, else the fixed view's
+static rm_camera_basis reported_basis(const rm_ctx *ctx) {
+    const rm_camera_basis fixed{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
+    return ctx->oriented ? ctx->basis : fixed;
+}
+
 // A staged slice of an offset sequence: host side and device side, grown on demand
 struct rm_staged_slice {
     std::vector<double> host;
@@ -42,12 +52,13 @@ struct rm_progressive {
     rm_frame_identity id;                    // the frame the sum belongs to
     uint32_t n = 0;                          // samples a pixel in the sum
     rm_staged_slice lights, shapes;          // the slices of rm_light_sequence (or zeros) and of rm_motion_sequence
+    rm_staged_slice camera;                  // ... and of rm_camera_sequence (the moving camera's tick)
 };
 
 static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
     rm_progressive *g = ctx->progressive;
     if (!g) return;
-    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->lights.d, g->shapes.d})
+    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->lights.d, g->shapes.d, g->camera.d})
         if (b && device_ok) (void)hipFree(b);
     delete g;
     ctx->progressive = nullptr;
@@ -64,7 +75,8 @@ static rm_status stage_slice(rm_ctx *ctx, rm_staged_slice &s, size_t doubles, FI
     return RM_OK;
 }
 
-// The tick of the four calls; `rules` says which, and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
+// The tick of the five calls; `rules` says which (rules.camera: the moving camera's, rm_camera_host.inc, which stages a slice
+// of rm_camera_sequence as well and launches its own kernels), and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
 // which a velocity on any shape is obeyed; key.motion = 2 keeps its frames apart from the moving spheres') from the moving
 // spheres': checked here, the tables they ask for staged, the launch by them.
 static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const rm_params *p, const rm_lens *lens, const rm_sampling_rules &rules,
@@ -100,9 +112,17 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
             if (rm_status sst = stage_slice(ctx, g.shapes, (size_t)ns * staged.shape_columns * 3u,
                                             [&](double *out) { return rm_fill_shape_rows(rules, n_before, ns, out); }))
                 return sst;
+            if (rules.camera) {
+                const rm_camera_basis basis = reported_basis(ctx);
+                if (rm_status sst = stage_slice(ctx, g.camera, (size_t)ns * 12u, [&](double *out) {
+                        return host_refusal(ctx, rm_camera_sequence(n_before, ns, rules.camera, &basis, rules.shutter, out));
+                    }))
+                    return sst;
+            }
             const accum_call call{p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream};
             const void *lights = staged.light_columns > 0u ? g.lights.d : nullptr, *shapes = staged.shape_columns > 0u ? g.shapes.d : nullptr;
             auto launch = [&]() {
+                if (rules.camera) return launch_camera(ctx, call, lights, shapes, g.camera.d);
                 if (any_shape) return any_shape(ctx, call, lights, shapes);
                 return rules.motion ? launch_motion(ctx, call, lights, shapes) : rules.soft ? launch_soft(ctx, call, lights) : launch_accum(ctx, call);
             };

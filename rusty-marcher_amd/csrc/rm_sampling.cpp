@@ -89,6 +89,11 @@ rm_frame_identity rm_frame_identity_of(const rm_params &p, const rm_lens &lens, 
         key.motion = 1u; key.n_shapes = rules.n_shapes; key.shutter = rules.shutter;
         id.velocities.assign(rules.velocities, rules.velocities + rules.n_shapes);
     }
+    if (rules.camera) {
+        key.camera_moves = 1u;
+        key.camera_motion = *rules.camera;
+        key.shutter = rules.shutter;                                           // (with or without velocities)
+    }
     return id;
 }
 
@@ -105,8 +110,9 @@ bool rm_same_frame(const rm_frame_identity &a, const rm_frame_identity &b) {
 
 rm_staging rm_staging_of(rm_tick_kind kind, const rm_sampling_rules &rules, uint32_t scene_lights, uint32_t scene_spheres, uint32_t scene_shapes) {
     rm_staging s;
-    s.light_columns = rules.motion ? scene_lights : rules.soft ? rules.n_lights : 0u;
-    s.light_zeros = rules.motion && !rules.soft;
+    const bool every_light = rules.motion || rules.camera != nullptr;       // kernels that read a row for every light of the scene
+    s.light_columns = every_light ? scene_lights : rules.soft ? rules.n_lights : 0u;
+    s.light_zeros = every_light && !rules.soft;
     s.shape_columns = rules.motion && (kind != RM_TICK_CONVERGING || scene_spheres > 0u) ? scene_shapes : 0u;
     return s;
 }
@@ -120,6 +126,8 @@ rm_status rm_fill_light_rows(const rm_sampling_rules &rules, const rm_staging &s
 rm_status rm_fill_shape_rows(const rm_sampling_rules &rules, uint32_t first, uint32_t count, double *out) {
     return rm_motion_sequence(first, count, rules.velocities, rules.n_shapes, rules.shutter, out);
 }
+
+double rm_shutter_time(uint32_t s, double shutter) { return shutter * radical_inverse(s, 17u); }   // (row 0: 0, the scene as uploaded)
 
 extern "C" {
 
@@ -174,7 +182,7 @@ rm_status rm_motion_sequence(uint32_t first, uint32_t count, const rm_vec3 *velo
     if (rm_status vst = rm_check_velocities(who, velocities, n_shapes, shutter)) return vst;
     if (!offsets) return refuse(std::string(who) + ": NULL offsets");
     for (uint32_t k = 0; k < count; k++) {
-        const double t = shutter * radical_inverse(first + k, 17u);      // (row 0: t = 0, the scene as uploaded)
+        const double t = rm_shutter_time(first + k, shutter);
         for (uint32_t j = 0; j < n_shapes; j++) {
             double *o = offsets + ((size_t)k * n_shapes + j) * 3u;
             o[0] = velocities[j].x * t;

@@ -30,6 +30,9 @@ struct rm_sampling_rules {
     const rm_vec3 *velocities = nullptr;
     uint32_t n_shapes = 0;
     double shutter = 0.;
+    // camera: the moving camera's ticks (rm_camera_host.inc), whose frames are their own: the motion's bytes join the key.  The
+    // shutter is the one above, with velocities (motion) or without
+    const rm_camera_motion *camera = nullptr;
 };
 
 // The view a sum belongs to, byte for byte (no padding: doubles and pairs of words)
@@ -44,6 +47,8 @@ struct rm_progressive_key {
     uint32_t soft, n_lights;                 // frames with radii: 1 and the radii's count (their bytes: rm_frame_identity::radii); else 0, 0
     uint32_t motion, n_shapes;               // frames with velocities: 1 (2: the moving shapes' tick sets it) and their count (bytes: rm_frame_identity::velocities)
     double shutter;                          // and the shutter; else 0, 0, 0
+    uint32_t camera_moves, _pad;             // frames of the moving camera's ticks: 1 and the bytes of their rm_camera_motion; else zeros
+    rm_camera_motion camera_motion;
 };
 
 // The frame a tick samples: the key and, beside it, copies of the radii and the velocities it was begun with
@@ -59,8 +64,8 @@ rm_frame_identity rm_frame_identity_of(const rm_params &p, const rm_lens &lens, 
 bool rm_same_radii(const rm_frame_identity &a, const rm_frame_identity &b);
 bool rm_same_frame(const rm_frame_identity &a, const rm_frame_identity &b);
 
-// The offset tables a tick stages beside the lens table: a motion tick's kernel reads a row for every light of the scene --
-// zeros where the lights are points -- and for every shape; a soft tick's for every radius.  The converging tick stages no shape
+// The offset tables a tick stages beside the lens table: a motion tick's kernel, and a moving camera's, reads a row for every
+// light of the scene -- zeros where the lights are points -- and, with velocities, for every shape; a soft tick's for every radius.  The converging tick stages no shape
 // table for a scene without spheres, the progressive one does; the converging tick of the moving shapes, whose kernel reads a
 // row of polygons and meshes as well, stages one whenever the scene holds a shape.
 enum rm_tick_kind { RM_TICK_PROGRESSIVE, RM_TICK_CONVERGING, RM_TICK_CONVERGING_MOVING };
@@ -76,6 +81,12 @@ rm_staging rm_staging_of(rm_tick_kind kind, const rm_sampling_rules &rules, uint
 inline rm_status rm_fill_lens_rows(uint32_t first, uint32_t count, double *out) { return rm_lens_sequence(first, count, out); }
 rm_status rm_fill_light_rows(const rm_sampling_rules &rules, const rm_staging &staged, uint32_t first, uint32_t count, double *out);
 rm_status rm_fill_shape_rows(const rm_sampling_rules &rules, uint32_t first, uint32_t count, double *out);
+
+// The instant of table row s within a shutter: shutter x phi_17(s), what rm_motion_sequence gives the row -- and
+// rm_camera_sequence (rm_camera_motion.cpp), so that the camera and the shapes of a sample share it
+double rm_shutter_time(uint32_t s, double shutter);
+// A camera motion is six finite numbers (rm_camera_motion.cpp)
+rm_status rm_check_camera_motion(const char *who, const rm_camera_motion *motion);
 
 #pragma GCC visibility pop
 

@@ -574,6 +574,55 @@ struct Renderer {
             }
         return last_report;
     }
+    // render_progressive_moving with a moving camera (rm_render_progressive_camera): the camera moves by motion.velocity and turns by
+    // motion's rates while the shutter stands open for `shutter`, and every sample sees the scene from a camera of its own.
+    // velocities: empty where no shape moves -- the scene keeps its hierarchy then.  The frame is the call's own: a switch to or from
+    // another progressive call begins it again, and so does a changed motion or shutter.
+    std::string render_progressive_camera(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const rm_camera_motion &motion, double shutter,
+                                          uint32_t n_samples, const std::vector<Vec3f> &velocities = {}, const std::vector<double> &radii = {},
+                                          double aperture = 0., double focus = 1., bool restart = false) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        std::vector<rm_vec3> v;
+        for (const Vec3f &e : velocities) v.push_back(e.c());
+        check(rm_render_progressive_camera(ctx_, &p, &lens, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(),
+                                           v.empty() ? nullptr : v.data(), (uint32_t)v.size(), shutter, &motion, restart ? 1 : 0, flat.data(),
+                                           nullptr, &last_samples, &last_timing),
+              ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
+    // render_converging_moving with a moving camera (rm_render_converging_camera): motion and velocities as
+    // render_progressive_camera's; only the pixels still noisy go on being sampled.  The frame is the call's own.
+    rm_converge_report render_converging_camera(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const rm_camera_motion &motion,
+                                                double shutter, const rm_converge &converge, uint32_t n_samples,
+                                                const std::vector<Vec3f> &velocities = {}, const std::vector<double> &radii = {},
+                                                double aperture = 0., double focus = 1., bool restart = false) {
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        std::vector<rm_vec3> v;
+        for (const Vec3f &e : velocities) v.push_back(e.c());
+        check(rm_render_converging_camera(ctx_, &p, &lens, &converge, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(),
+                                          v.empty() ? nullptr : v.data(), (uint32_t)v.size(), shutter, &motion, restart ? 1 : 0, flat.data(),
+                                          nullptr, &last_report, &last_timing),
+              ctx_);
+        last_samples = last_report.max_count;
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return last_report;
+    }
     // The oriented camera: the view direction of every later render / render_display / pick (nullptr: the reference's fixed
     // view, down -z with +y up).  It stays with the context; the position is the scene's camera, as before.
     void orient(const rm_camera_basis *basis) { check(rm_camera_orient(context(), basis), ctx_); }

@@ -324,6 +324,67 @@ class Renderer:
                                                    aperture, focus)
         return report
 
+    def render_progressive_camera(self, frame, scene, camera_velocity, shutter, n_samples, turn=(0., 0., 0.), velocities=None,
+                                  light_radii=None, aperture=0., focus=1., restart=False):
+        """render_progressive_moving with a moving camera (rm_render_progressive_camera): the camera moves by camera_velocity
+        and turns by `turn` = (yaw, pitch, roll) in radians, both a unit of time, while the shutter stands open for `shutter`,
+        and every sample sees the scene from a camera of its own, so the frame converges to a view blurred along the camera's
+        motion.  velocities: one Vec3f or None a shape, or None where no shape moves -- the scene keeps its hierarchy then.  The
+        frame is the call's own: a switch to or from another progressive call begins it again, and so does a changed velocity,
+        turn or shutter."""
+        backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        backend._camera_motion(camera_velocity, turn)
+        v = backend._velocities(velocities, len(scene.shapes)) if velocities is not None else None
+        backend._shutter(shutter)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        return self._tick(frame, scene, lambda ctx, p: ctx.render_progressive_camera(p, camera_velocity, shutter, aperture, focus, n_samples, turn,
+                                                                                      v, radii, restart, host_rgb=frame.buffer))
+
+    def render_camera_blur(self, frame, scene, camera_velocity, shutter, n_samples, turn=(0., 0., 0.)):
+        """One frame with the blur of a moving camera: a restarted render_progressive_camera ticked in slices of at most 64 until
+        the frame holds n_samples samples a pixel, through a pinhole, point lights, shapes standing still.  Prints and returns
+        what the last tick does."""
+        if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= backend.PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("n_samples must be an integer in 1..%d, got %r" % (backend.PROGRESSIVE_MAX_SAMPLES, n_samples))
+        left, message = int(n_samples), None
+        while left > 0:
+            step = min(left, 64)
+            message = self.render_progressive_camera(frame, scene, camera_velocity, shutter, step, turn, restart=left == n_samples)
+            left -= step
+        return message
+
+    def render_converging_camera(self, frame, scene, camera_velocity, shutter, tolerance, n_samples, turn=(0., 0., 0.), velocities=None,
+                                 min_samples=16, max_samples=1024, light_radii=None, aperture=0., focus=1., restart=False):
+        """render_converging_moving with a moving camera (rm_render_converging_camera): camera_velocity, turn and velocities as
+        render_progressive_camera's.  The frame is the call's own.  Returns the tick's report, as render_converging does."""
+        backend._converge(tolerance, min_samples, max_samples, backend._lens(aperture, focus, n_samples).n_samples)
+        backend._camera_motion(camera_velocity, turn)
+        v = backend._velocities(velocities, len(scene.shapes)) if velocities is not None else None
+        backend._shutter(shutter)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        got = []
+
+        def call(ctx, p):
+            timing, report = ctx.render_converging_camera(p, camera_velocity, shutter, aperture, focus, n_samples, tolerance, min_samples,
+                                                          max_samples, turn, v, radii, restart, host_rgb=frame.buffer)
+            got.append(report)
+            return timing, report.max_count
+
+        self._tick(frame, scene, call)
+        self.last_report = got[0]
+        return got[0]
+
+    def render_converged_camera(self, frame, scene, camera_velocity, shutter, tolerance, n_samples, turn=(0., 0., 0.), velocities=None,
+                                min_samples=16, max_samples=1024, light_radii=None, aperture=0., focus=1.):
+        """A finished picture with the blur of a moving camera: a restarted render_converging_camera ticked until a tick lists
+        nothing.  -> the last tick's report."""
+        report = self.render_converging_camera(frame, scene, camera_velocity, shutter, tolerance, n_samples, turn, velocities, min_samples,
+                                               max_samples, light_radii, aperture, focus, restart=True)
+        while report.listed > 0:
+            report = self.render_converging_camera(frame, scene, camera_velocity, shutter, tolerance, n_samples, turn, velocities, min_samples,
+                                                   max_samples, light_radii, aperture, focus)
+        return report
+
     def _tick(self, frame, scene, call):
         """What the progressive renders share: the prints and the return value of render(); call(ctx, params) ->
         (rm_timing, samples a pixel in the frame)."""

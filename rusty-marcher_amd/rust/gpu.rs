@@ -195,6 +195,17 @@ pub struct RmConvergeReport {
     pub _pad: u32,
 }
 
+/// `rm_camera_motion`: how the camera moves while the shutter stands open -- world units a unit of time, and yaw, pitch and roll
+/// in radians a unit of time about the axes and with the signs of `basis_turn` (48 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmCameraMotion {
+    pub velocity: RmVec3,
+    pub yaw: f64,
+    pub pitch: f64,
+    pub roll: f64,
+}
+
 /// `rm_lights_visible`'s modes: the decision direct_lighting takes / the shadow ray ended at the light.
 pub const RM_LIGHTS_AS_RENDERED: u32 = 0;
 pub const RM_LIGHTS_CLIPPED: u32 = 1;
@@ -318,6 +329,11 @@ extern "C" {
     fn rm_accumulate_converging_motion_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_render_converging_motion(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_accumulate_converging_moving_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_camera_sequence(first: u32, count: u32, motion: *const RmCameraMotion, basis: *const RmCameraBasis, shutter: f64, rows: *mut f64) -> c_int;
+    fn rm_accumulate_camera_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_accumulate_converging_camera_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_progressive_camera(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, motion: *const RmCameraMotion, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_render_converging_camera(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, motion: *const RmCameraMotion, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_render_converging_moving(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
@@ -1175,6 +1191,207 @@ impl Gpu {
         check(
             unsafe {
                 rm_accumulate_converging_moving_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, if fresh { 1 } else { 0 }, &buffers, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// `render_progressive_moving` with a moving camera: the camera moves by `motion.velocity` and turns by the rates of `motion`
+    /// while the shutter stands open for `shutter`, and every sample sees the scene from a camera of its own.  `velocities`:
+    /// `None` where no shape moves -- the scene keeps its hierarchy then.  The frame is the call's own: a switch to or from
+    /// another progressive call begins it again, and so does a changed motion or shutter.
+    pub fn render_progressive_camera(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        radii: Option<&[f64]>,
+        velocities: Option<&[Vec3f]>,
+        shutter: f64,
+        motion: RmCameraMotion,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let v: Option<Vec<RmVec3>> = velocities.map(|vs| vs.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect());
+        let (v_ptr, n_shapes) = match v {
+            Some(ref v) => (v.as_ptr(), v.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut total: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_progressive_camera(self.ctx, &p, &lens, radii_ptr, n_lights, v_ptr, n_shapes, shutter, &motion, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut total, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), total)
+    }
+
+    /// The device call under `render_progressive_camera`: `accumulate_moving` with `device_camera_rows`, `n_samples` x 12 f64 --
+    /// rows of `camera_sequence`, or any of the caller's making -- whose row s is the camera of sample s.  A null
+    /// `device_shape_offsets` says that no shape moves.
+    pub fn accumulate_camera(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_camera_rows: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_camera_device(self.ctx, &p, &lens, device_table, device_camera_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// Rows `first .. first + count` of the library's camera sequence: twelve f64 a row -- the offset, right, up, forward -- for a
+    /// camera that moves by `motion` from `basis` while the shutter stands open for `shutter`.  Row s is at the time
+    /// `motion_sequence` gives row s.
+    pub fn camera_sequence(first: u32, count: u32, motion: RmCameraMotion, basis: RmCameraBasis, shutter: f64) -> Vec<f64> {
+        let n = 12 * count as usize;
+        let mut rows = vec![0f64; n + 1]; // (+ 1: never a dangling pointer)
+        check(unsafe { rm_camera_sequence(first, count, &motion, &basis, shutter, rows.as_mut_ptr()) }, ptr::null());
+        rows.truncate(n);
+        rows
+    }
+
+    /// `render_converging_moving` with a moving camera: `motion` and `velocities` as `render_progressive_camera`'s; only the
+    /// pixels still noisy go on being sampled.  The frame is the call's own.
+    pub fn render_converging_camera(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        converge: RmConverge,
+        radii: Option<&[f64]>,
+        velocities: Option<&[Vec3f]>,
+        shutter: f64,
+        motion: RmCameraMotion,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, RmConvergeReport) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let v: Option<Vec<RmVec3>> = velocities.map(|vs| vs.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect());
+        let (v_ptr, n_shapes) = match v {
+            Some(ref v) => (v.as_ptr(), v.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut report = RmConvergeReport::default();
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_converging_camera(self.ctx, &p, &lens, &converge, radii_ptr, n_lights, v_ptr, n_shapes, shutter, &motion, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut report, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), report)
+    }
+
+    /// The device call under `render_converging_camera`: `accumulate_converging_moving` with `device_camera_rows`, `table_rows` x
+    /// 12 f64.  A null `device_shape_offsets` says that no shape moves.
+    pub fn accumulate_converging_camera(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_camera_rows: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_camera_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_camera_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, if fresh { 1 } else { 0 }, &buffers, hip_stream)
             },
             self.ctx,
         );
