@@ -1412,6 +1412,67 @@ rm_status rm_render_converging_camera(rm_ctx *ctx, const rm_params *params, cons
                                       double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
                                       rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
 
+/* ---- swept hierarchies: motion blur that keeps the scene's hierarchies ----------------------------
+ * The moving shapes' passes walk flat: a hierarchy's boxes hold for the uploaded positions only.
+ * A swept hierarchy is the resident scene image with the boxes of its sphere and triangle
+ * hierarchies refitted, so that each bounds its primitives at every position their shapes can take
+ * within given per-shape offset extents.  The topology -- child refs, leaf order, pid map, list-order
+ * keys -- is the image's.  The passes below walk it with the moving shapes' rule applied inside the
+ * leaves; the hierarchy only decides which primitives are tested, so a swept pass leaves byte for
+ * byte what its flat sibling leaves.  Additive to ABI version 5; a host detects them by
+ * " swept-hierarchy" in rm_build_info().
+ *
+ * Extents: lo and hi, [n_shapes][3] doubles each in the order of the scene's shape list, promise
+ *   lo[k].c <= shape_offsets[r][k].c <= hi[k].c    for every row r any pass with this handle reads.
+ * They must be finite with lo <= hi; anything else is refused and the shape named.  The extents of a
+ * polygon are checked and not otherwise used: polygons have no hierarchy and are walked flat.
+ * rm_swept_extents gives the per-shape componentwise minimum and maximum of a host table of `rows`
+ * rows (rows >= 1).  rm_swept_motion_extents gives the extents of rm_motion_sequence's rows, all of
+ * them: row s holds fl(v.c * t) with 0 <= t <= shutter, so lo.c = min(0, fl(v.c * shutter)) and
+ * hi.c = max(0, fl(v.c * shutter)).  Both are host arithmetic only.
+ *
+ * Contract: a table row outside the extents a handle was built with gives unspecified pixels -- a
+ * box may miss its primitive, and the shape be missed for that sample.  It is never a fault: nothing
+ * read from a row or a box forms an address.
+ *
+ * rm_swept_build refits the resident image and uploads the result (it waits for the copy).  n_shapes
+ * must be the resident scene's count.  For a scene whose image holds no hierarchy it succeeds, and
+ * the passes walk flat.  The handle belongs to the context and to the scene as it stands: after an
+ * upload that changes the resident image it is stale, and only rm_swept_free takes it.
+ * rm_swept_free waits for the device, so no pass is still walking the handle's boxes when they go;
+ * NULL is allowed.  rm_destroy releases the handles nobody freed.
+ *
+ * rm_accumulate_swept_device has rm_accumulate_moving_device's argument list and checks, and
+ * rm_accumulate_converging_swept_device rm_accumulate_converging_moving_device's, plus the handle
+ * behind n_shapes.  Both refuse a NULL handle, one that is not this context's (or was freed), and one built
+ * before the scene last changed; a refused call names the offender in rm_last_error and touches no buffer.  Both are
+ * asynchronous on the caller's stream and keep no state of their own, as their siblings.
+ *
+ * The ticks rm_render_progressive_moving and rm_render_converging_moving keep their signatures,
+ * frames, keys and bytes.  Where the resident image holds a hierarchy they build a swept hierarchy
+ * from rm_swept_motion_extents of their velocities and shutter and launch the swept kernels; they
+ * build it again when the scene, a velocity or the shutter changes -- what begins the frame again
+ * anyway.  RM_SWEPT_BVH=0 in the environment of rm_init makes them walk flat as before.
+ *
+ * Staying flat: the moving spheres' calls (..._motion) and the moving camera's calls given
+ * velocities.  Not here either: the bundle cull and occluder masks under motion, rotation.
+ */
+typedef struct rm_swept rm_swept;   /* a swept hierarchy of the resident scene (opaque) */
+
+rm_status rm_swept_extents(const double *table, uint32_t rows, uint32_t n_shapes, double *lo, double *hi);
+rm_status rm_swept_motion_extents(const rm_vec3 *velocities, uint32_t n_shapes, double shutter, double *lo, double *hi);
+rm_status rm_swept_build(rm_ctx *ctx, const double *lo, const double *hi, uint32_t n_shapes, rm_swept **out);
+void      rm_swept_free(rm_ctx *ctx, rm_swept *swept);
+rm_status rm_accumulate_swept_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                     const void *device_light_offsets, uint32_t n_lights, const void *device_shape_offsets,
+                                     uint32_t n_shapes, const rm_swept *swept, uint32_t n_before, void *device_sum,
+                                     void *device_mean /* optional */, void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_accumulate_converging_swept_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                                const rm_converge *converge, const void *device_table, uint32_t table_rows,
+                                                const void *device_light_offsets, uint32_t n_lights,
+                                                const void *device_shape_offsets, uint32_t n_shapes, const rm_swept *swept,
+                                                int fresh, const rm_converge_frame *buffers, void *hip_stream);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

@@ -264,6 +264,14 @@ SIGNATURES = {
     "rm_render_converging_camera": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, _P(rm_vec3),
                                               C.c_uint32, C.c_double, _P(rm_camera_motion), C.c_int, _P(C.c_double), _P(C.c_uint8),
                                               _P(rm_converge_report), _P(rm_timing)]),
+    "rm_swept_extents": (C.c_int, [_P(C.c_double), C.c_uint32, C.c_uint32, _P(C.c_double), _P(C.c_double)]),
+    "rm_swept_motion_extents": (C.c_int, [_P(rm_vec3), C.c_uint32, C.c_double, _P(C.c_double), _P(C.c_double)]),
+    "rm_swept_build": (C.c_int, [_VP, _P(C.c_double), _P(C.c_double), C.c_uint32, _P(_VP)]),
+    "rm_swept_free": (None, [_VP, _VP]),
+    "rm_accumulate_swept_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP,
+                                             _VP, _VP]),
+    "rm_accumulate_converging_swept_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, C.c_uint32, _VP,
+                                                        C.c_uint32, _VP, C.c_int, _P(rm_converge_frame), _VP]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

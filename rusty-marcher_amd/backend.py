@@ -189,6 +189,15 @@ def _host_outputs(params, host_rgb, host_rgb8):
     return out
 
 
+def _extents(lo, hi):
+    """The per-shape offset extents of a swept hierarchy as two C-contiguous float64 arrays (n_shapes, 3); their numbers are the
+    library's to check (it names the shape)."""
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+    if lo.ndim != 2 or lo.shape[1] != 3 or hi.shape != lo.shape:
+        raise ValueError("lo and hi must both have the shape (n_shapes, 3), got %s and %s" % (lo.shape, hi.shape))
+    return lo, hi
+
+
 def _offset_tensor(offsets, name, what, n_samples, device):
     """A light or shape offset table as a contiguous float64 tensor (n_samples, n, 3) on `device`: a tensor is checked, an array is
     checked (finite) and copied over."""
@@ -297,6 +306,18 @@ def _device_hits(raw):
 def _torch():
     import torch
     return torch
+
+
+class Swept:
+    """A swept hierarchy of a context's uploaded scene (Context.swept).  close() releases it (waits for the device)."""
+
+    def __init__(self, ctx, ptr):
+        self.ctx, self.ptr = ctx, ptr
+
+    def close(self):
+        if self.ptr is not None and self.ctx.ptr is not None:
+            self.ctx.L.rm_swept_free(self.ctx.ptr, self.ptr)
+        self.ptr = None
 
 
 class Context:
@@ -865,6 +886,76 @@ class Context:
                                                        *host, C.byref(total), C.byref(timing)), self.ptr)
         return timing, total.value
 
+    # ---- swept hierarchies (include/rusty_marcher_amd.h, "swept hierarchies") ----
+    def swept(self, lo, hi):
+        """rm_swept_build: a swept hierarchy of the uploaded scene -- its hierarchies' boxes refitted to bound every primitive at
+        every offset within lo[k] .. hi[k] of its shape k.  lo, hi: (n_shapes, 3), finite, lo <= hi.  -> a Swept handle, stale
+        once another scene is uploaded; close() it, or leave it to the context."""
+        lo, hi = _extents(lo, hi)
+        h = C.c_void_p()
+        _lib.check(self.L.rm_swept_build(self.ptr, lo.ctypes.data_as(C.POINTER(C.c_double)), hi.ctypes.data_as(C.POINTER(C.c_double)),
+                                         lo.shape[0], C.byref(h)), self.ptr)
+        return Swept(self, h)
+
+    def _swept_for(self, swept, shape_offsets):
+        """The handle a swept pass walks: the caller's, or one built from the table's own extents (amin / amax over its rows, on
+        the device)."""
+        if swept is not None:
+            if not isinstance(swept, Swept) or swept.ctx is not self or swept.ptr is None:
+                raise ValueError("swept must be an open Swept handle of this context")
+            return swept
+        if shape_offsets.shape[1] == 0:
+            return self.swept(np.zeros((0, 3)), np.zeros((0, 3)))
+        return self.swept(shape_offsets.amin(dim=0).cpu().numpy(), shape_offsets.amax(dim=0).cpu().numpy())
+
+    def accumulate_swept_device(self, params, sum, aperture, focus, table, light_offsets, shape_offsets, n_before, mean=None, rgb8=None,
+                                stream=None, swept=None):
+        """rm_accumulate_swept_device: accumulate_moving_device through a swept hierarchy -- the same bytes, with the scene's
+        hierarchies walked where it has any.  swept: a handle of Context.swept whose extents hold every row of shape_offsets;
+        None builds one from the table itself.  Arguments and result as accumulate_moving_device's."""
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", lens.n_samples, sum.device)
+        shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", lens.n_samples, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), int(shape_offsets.shape[1])
+        handle = self._swept_for(swept, shape_offsets)
+        try:
+            _lib.check(self.L.rm_accumulate_swept_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                         C.c_void_p(light_offsets.data_ptr()) if n_lights > 0 else None, n_lights,
+                                                         C.c_void_p(shape_offsets.data_ptr()) if n_shapes > 0 else None, n_shapes, handle.ptr,
+                                                         int(n_before), C.c_void_p(sum.data_ptr()),
+                                                         C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                         C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                         C.c_void_p(self._stream(stream))), self.ptr)
+        finally:
+            if swept is None:
+                handle.close()                                  # (waits for the device: the pass is through)
+        return table, light_offsets, shape_offsets
+
+    def accumulate_converging_swept_device(self, params, sum, stats, count, aperture, focus, n_samples, table, light_offsets, shape_offsets,
+                                           tolerance, min_samples, max_samples, fresh, mean=None, rgb8=None, mask=None, workspace=None,
+                                           stream=None, swept=None):
+        """rm_accumulate_converging_swept_device: accumulate_converging_moving_device through a swept hierarchy -- the same
+        bytes, lists and counts.  swept: as accumulate_swept_device's.  Arguments and result as
+        accumulate_converging_moving_device's."""
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
+        rows = int(table.shape[0])
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", rows, sum.device)
+        shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", rows, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), int(shape_offsets.shape[1])
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        handle = self._swept_for(swept, shape_offsets)
+        try:
+            _lib.check(self.L.rm_accumulate_converging_swept_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), rows,
+                                                                    vp(light_offsets) if n_lights > 0 else None, n_lights,
+                                                                    vp(shape_offsets) if n_shapes > 0 else None, n_shapes, handle.ptr,
+                                                                    1 if fresh else 0, C.byref(frame), C.c_void_p(self._stream(stream))), self.ptr)
+        finally:
+            if swept is None:
+                handle.close()
+        return workspace
+
     # ---- converging frames (include/rusty_marcher_amd.h, "converging frames") ----
     def converge_workspace(self, params):
         """rm_converge_workspace: bytes of device memory the list of accumulate_converging_device needs for `params`."""
@@ -1242,3 +1333,25 @@ def camera_sequence(first, count, velocity, shutter, turn=(0., 0., 0.), basis=FI
     _lib.check(_lib.lib().rm_camera_sequence(int(first), int(count), C.byref(motion), C.byref(_lib.camera_basis(basis)), shutter,
                                              rows.ctypes.data_as(C.POINTER(C.c_double))))
     return rows
+
+
+def swept_extents(table):
+    """rm_swept_extents: the per-shape componentwise minimum and maximum of a host shape offset table (rows, n_shapes, 3) ->
+    (lo, hi), each (n_shapes, 3).  Host arithmetic: needs neither a context nor a GPU."""
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    if t.ndim != 3 or t.shape[2] != 3:
+        raise ValueError("table must have the shape (rows, n_shapes, 3), got %s" % (t.shape,))
+    lo, hi = np.zeros(t.shape[1:]), np.zeros(t.shape[1:])
+    D = C.POINTER(C.c_double)
+    _lib.check(_lib.lib().rm_swept_extents(t.ctypes.data_as(D), t.shape[0], t.shape[1], lo.ctypes.data_as(D), hi.ctypes.data_as(D)), None)
+    return lo, hi
+
+
+def swept_motion_extents(velocities, shutter):
+    """rm_swept_motion_extents: the extents that hold every row of motion_sequence(velocities, shutter) -> (lo, hi)."""
+    v, shutter = _velocities(velocities), _shutter(shutter)
+    lo, hi = np.zeros((v.shape[0], 3)), np.zeros((v.shape[0], 3))
+    D = C.POINTER(C.c_double)
+    _lib.check(_lib.lib().rm_swept_motion_extents(v.ctypes.data_as(C.POINTER(_lib.rm_vec3)), v.shape[0], shutter, lo.ctypes.data_as(D),
+                                                  hi.ctypes.data_as(D)), None)
+    return lo, hi

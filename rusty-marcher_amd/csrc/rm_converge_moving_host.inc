@@ -21,6 +21,12 @@ static rm_status launch_converge_moving(rm_ctx *ctx, const rm_params *p, const r
     return launch_converge_with(ctx, shade_family{"converging with moving shapes", rm_converge_moving_kernel}, m, m.C, stream);
 }
 
+// The ticks' hierarchy (rm_swept_host.inc, behind this file): the launch that walks it where tick_swept_prepare made it ready --
+// launch_converge_moving where not
+static rm_status launch_converge_moving_tick(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                             uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
+                                             const rm_converge_frame *b, hipStream_t stream);
+
 extern "C" {
 
 rm_status rm_accumulate_converging_moving_device(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c,
@@ -48,10 +54,13 @@ rm_status rm_accumulate_converging_moving_device(rm_ctx *ctx, const rm_params *p
 rm_status rm_render_converging_moving(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
                                       const double *radii, uint32_t n_lights, const rm_vec3 *velocities, uint32_t n_shapes, double shutter,
                                       int restart, double *host_rgb, uint8_t *host_rgb8, rm_converge_report *report, rm_timing *timing) {
-    return guarded(ctx, "rm_render_converging_moving", [&]() {
-        return rm_render_converging_impl(ctx, "rm_render_converging_moving", params, lens, converge,
-                                         rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb, host_rgb8, report,
-                                         timing, launch_converge_moving);
+    return guarded(ctx, "rm_render_converging_moving", [&]() -> rm_status {
+        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_converging_moving", velocities, n_shapes, shutter)) return pst;
+        const rm_status st = rm_render_converging_impl(ctx, "rm_render_converging_moving", params, lens, converge,
+                                                       rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb,
+                                                       host_rgb8, report, timing, launch_converge_moving_tick);
+        tick_swept_done(ctx);
+        return st;
     });
 }
 

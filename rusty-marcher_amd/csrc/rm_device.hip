@@ -35,6 +35,9 @@
 #include "rm_converge_moving.hpp"
 #include "rm_camera.hpp"
 #include "rm_converge_camera.hpp"
+#include "rm_swept_image.hpp"
+#include "rm_swept.hpp"
+#include "rm_converge_swept.hpp"
 
 using namespace rmdev;
 
@@ -127,6 +130,7 @@ struct rm_feedback {
 
 struct rm_hostio;   // rm_hostio.inc: staging buffer, row-scatter threads, display frame
 struct rm_progressive;   // rm_motion_host.inc: staged tables, sum, mean and bytes of rm_render_progressive*, its count and frame identity
+struct rm_tick_swept;    // rm_swept_host.inc: the swept hierarchy of the moving shapes' ticks, and what it was built from
 struct rm_converging;    // rm_converge_motion_host.inc: the buffers, resident sequences, pass total and frame identity of rm_render_converging*
 
 // The classification's output for the render launches on one stream: a mask per tile.  (Launches on a
@@ -177,6 +181,7 @@ struct rm_ctx {
     uint32_t *d_redo = nullptr;
     std::vector<rm_feedback> feedback;
     uint64_t feedback_clock = 0, scene_epoch = 0;
+    uint64_t image_epoch = 0;         // counts the changes of the resident image or its pid map: what a swept hierarchy is built from (rm_swept_host.inc)
     std::vector<rm_tile_lists> tile_lists;
     uint32_t last_launch_grid = 0, last_launch_tail = 0;   // rm_launch_stats
     uint32_t last_launch_tiles = 0;   // rm_tile_stats: the last render launch's tiles, and whether they were classified
@@ -235,6 +240,10 @@ struct rm_ctx {
     // converging frames (rm_converge_motion_host.inc): made by the first rm_render_converging, rm_render_converging_motion or rm_render_converging_moving; shares nothing with `progressive`
     rm_converging *converging = nullptr;
 
+    // swept hierarchies (rm_swept_host.inc): the one the moving shapes' ticks walk, built from their velocities and shutter
+    rm_tick_swept *tick_swept = nullptr;
+    std::vector<rm_swept *> swept_handles;   // every handle rm_swept_build gave out and rm_swept_free has not taken back
+
     // post-process scratch
     unsigned long long *d_max = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -245,6 +254,7 @@ static void hostio_destroy(rm_ctx *ctx, bool device_ok);
 static bool hostio_packs(rm_ctx *ctx, size_t band_bytes);
 static void progressive_destroy(rm_ctx *ctx, bool device_ok);
 static void converging_destroy(rm_ctx *ctx, bool device_ok);
+static void tick_swept_destroy(rm_ctx *ctx, bool device_ok);
 
 static rm_status ctx_fail(rm_ctx *ctx, rm_status st, const std::string &msg) {
     if (ctx) ctx->error = msg;
@@ -337,7 +347,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera converge-moving converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy converge-moving converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -395,6 +405,7 @@ void rm_destroy(rm_ctx *ctx) {
     hostio_destroy(ctx, device_ok);
     progressive_destroy(ctx, device_ok);
     converging_destroy(ctx, device_ok);
+    tick_swept_destroy(ctx, device_ok);
     if (device_ok) {
         for (rm_frame_slot &s : ctx->slots) {
             // after a timed-out collective the slot's stream may never drain: leave it to process exit
@@ -507,6 +518,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
             RM_HIP(ctx, hipDeviceSynchronize());          // a query may still be reading the old map
             if (rm_status mst = upload_pid_map(ctx, img.pid_map)) return mst;
             resident.pid_map.swap(img.pid_map);
+            ctx->image_epoch++;
         }
         ctx->camera = d->camera;
         keep_description();
@@ -530,6 +542,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     ctx->camera = d->camera;
     ctx->have_scene = true;
     ctx->scene_epoch++;                                      // (the feedback of another scene's frames is void)
+    ctx->image_epoch++;
     keep_description();
     return RM_OK;
 }
@@ -1131,3 +1144,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_converge_motion_host.inc"
 #include "rm_converge_moving_host.inc"
 #include "rm_camera_host.inc"
+#include "rm_swept_host.inc"

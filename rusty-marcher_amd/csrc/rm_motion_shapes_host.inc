@@ -4,7 +4,8 @@
 // rm_motion_shapes.hip's.
 //
 // rm_accumulate_moving_device touches no render state and keeps none of its own: one launch on the caller's stream, nothing
-// waited for.  rm_render_progressive_moving is rm_render_progressive_motion's tick with every shape free to move.
+// waited for.  rm_render_progressive_moving is rm_render_progressive_motion's tick with every shape free to move; where the
+// resident image holds a hierarchy it walks one swept over the velocities and the shutter (rm_swept_host.inc), to the same bytes.
 
 // The launch; offsets: NULL where the scene has no lights; shape_offsets: NULL where it has no shapes.
 static rm_status launch_moving(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets) {
@@ -16,6 +17,12 @@ static rm_status launch_moving(rm_ctx *ctx, const accum_call &c, const void *off
     a.n_shapes = resident_shape_count(ctx);
     return launch_shading(ctx, shade_family{"moving shapes", rm_motion_shapes_kernel}, a.S.A.L.max_depth, lens_extent(ctx, a.S.A.L), a, c.stream);
 }
+
+// The ticks' hierarchy (rm_swept_host.inc, behind this file): made ready in front of a tick for its velocities and shutter, and the
+// launch that walks it where it is -- launch_moving where it is not
+static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter);
+static void tick_swept_done(rm_ctx *ctx);
+static rm_status launch_moving_tick(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets);
 
 extern "C" {
 
@@ -41,10 +48,13 @@ rm_status rm_accumulate_moving_device(rm_ctx *ctx, const rm_params *p, const rm_
 rm_status rm_render_progressive_moving(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *radii, uint32_t n_lights,
                                        const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart, double *host_rgb,
                                        uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
-    return guarded(ctx, "rm_render_progressive_moving", [&]() {
-        return rm_render_progressive_impl(ctx, "rm_render_progressive_moving", params, lens,
-                                          rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb, host_rgb8, n_total,
-                                          timing, launch_moving);
+    return guarded(ctx, "rm_render_progressive_moving", [&]() -> rm_status {
+        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_progressive_moving", velocities, n_shapes, shutter)) return pst;
+        const rm_status st = rm_render_progressive_impl(ctx, "rm_render_progressive_moving", params, lens,
+                                                        rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb,
+                                                        host_rgb8, n_total, timing, launch_moving_tick);
+        tick_swept_done(ctx);
+        return st;
     });
 }
 

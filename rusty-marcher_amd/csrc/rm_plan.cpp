@@ -53,6 +53,7 @@ const knob k_knobs[] = {
     {"RM_SHADOW_MASKS", &rm_knobs::shadow_masks, NOT_0},
     {"RM_DEAD_CHILDREN", &rm_knobs::dead_children, NOT_0},
     {"RM_DISABLE_BVH", &rm_knobs::disable_bvh, IS_1},
+    {"RM_SWEPT_BVH", &rm_knobs::swept_bvh, NOT_0},
     {"RM_FORCE_STACK", &rm_knobs::force_stack, ATOI},
     {"RM_FEEDBACK", &rm_knobs::feedback_mode, ONE_OR_ZERO},
     {"RM_FEEDBACK_US", &rm_knobs::feedback_us, ATOI_MIN_1},

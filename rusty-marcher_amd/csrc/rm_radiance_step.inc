@@ -68,6 +68,7 @@ struct OffsetLights {
 // the queries' pid map leads from i to the shape, a wave-uniform load in the walks.  `at` is the one place the addition stands.
 struct OffsetSpheres {
     static constexpr bool moves = true;
+    static constexpr bool swept = false;
     const double *row;                                                   // n_shapes x 3 doubles
     const uint32_t *pid_map;                                             // 2 words a pid; word 0: the shape
     __device__ __forceinline__ V3 at(double cx, double cy, double cz, uint32_t i) const {
@@ -93,6 +94,7 @@ struct OffsetSpheres {
 // whether the shape changed is a scalar branch: the triangles of a mesh are consecutive and fetch their offset once.
 struct OffsetShapes {
     static constexpr bool moves = true;
+    static constexpr bool swept = false;
     const double *row;                                                   // n_shapes x 3 doubles
     const uint32_t *pid_map;                                             // 2 words a pid; word 0: the shape
     uint32_t n_spheres, n_polygons;
@@ -126,6 +128,13 @@ struct OffsetShapes {
         __device__ __forceinline__ double z(double v) const { return v + oz; }
     };
     __device__ __forceinline__ Planar planar() const { return Planar{row, pid_map, n_spheres, n_polygons, ~0u, 0., 0., 0.}; }
+};
+
+// ... and the same rule admitted into a swept hierarchy (rm_swept.hip, rm_converge_swept.hip): the scene blob those kernels are
+// handed holds boxes refitted to every position the rule can give a primitive (rm_swept.cpp), so closest_hit and any_hit let it
+// enter them and apply it inside the leaves.  Nothing else differs.
+struct SweptShapes : OffsetShapes {
+    static constexpr bool swept = true;
 };
 
 // The un-normalised direction of the sample (sx, sy): renderer.rs:128-135 at a real-valued position, the host's

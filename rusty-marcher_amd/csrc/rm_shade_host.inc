@@ -58,6 +58,7 @@ static void fill_view(ARGS &q, const rm_ctx *ctx, const rm_params *p, const rm_c
 struct shade_family {
     const char *name;
     const void *(*pick)(bool bvh, int pow_mode, int stack);
+    const double *scene = nullptr;   // the blob its kernels are handed; NULL: the resident one (a swept one: rm_swept_host.inc)
 };
 
 // The workgroups of a shading launch: `blocks` where that is not 0 (the radiance queries: a lane an answer), else what
@@ -88,7 +89,8 @@ static rm_status launch_shading(rm_ctx *ctx, const shade_family &f, uint32_t max
         grid = rm_shading_grid(x.total, x.rays_per_pixel, ctx->prop.multiProcessorCount, per_cu, x.max_blocks);
     }
     if (rm_status bst = before()) return bst;
-    void *args[] = {(void *)&ctx->d_scene, (void *)&a};
+    const double *scene = f.scene ? f.scene : ctx->d_scene;
+    void *args[] = {(void *)&scene, (void *)&a};
     RM_HIP(ctx, hipLaunchKernel(fn, dim3(grid), dim3(64), args, 0, stream));
     return RM_OK;
 }

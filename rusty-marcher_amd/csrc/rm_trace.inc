@@ -277,6 +277,7 @@ struct StoredPlanar {
 };
 struct StoredSpheres {
     static constexpr bool moves = false;
+    static constexpr bool swept = false;                                 // (a rule that moves may enter a swept hierarchy: rm_swept.hip)
     using Planar = StoredPlanar;
     __device__ __forceinline__ SphereRec operator()(const SphereRec &s, uint32_t) const { return s; }
     __device__ __forceinline__ V3 centre(const double *sp, uint32_t) const { return mk(sp[0], sp[1], sp[2]); }
@@ -786,7 +787,8 @@ __device__ __forceinline__ void closest_triangle(const SceneView &sc, ClosestSta
 template <bool BVH, bool CULL, bool EDGES, class SPHERES = StoredSpheres>
 __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, bool on, Hit &out, bool have_mask, unsigned long long mask,
                                             const SPHERES &spheres = SPHERES()) {
-    static_assert(!SPHERES::moves || (!BVH && !CULL), "moved spheres walk flat: boxes and bundles hold for the stored centres");
+    static_assert(!SPHERES::moves || (SPHERES::swept && !CULL) || (!BVH && !CULL),
+                  "moved shapes walk flat, or a hierarchy swept over their offsets: boxes and bundles hold for the stored records");
     const double *__restrict__ S = sc.G;
     const rm_dev_header &H = sc.H;
     ClosestState c{false, 0., 0., 0u};
@@ -850,6 +852,15 @@ __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, boo
         bvh_walk(sc, H.off_bvh_spheres, rb, prune_at, off_lane, [&](uint32_t first, uint32_t cnt) {
             const SphereRec s0 = load_sphere(S, H, first), s1 = load_sphere(S, H, first + 1u);
             const SphereRec s2 = load_sphere(S, H, first + 2u), s3 = load_sphere(S, H, first + 3u);
+            if constexpr (SPHERES::moves) {
+                // a swept hierarchy: the rule stands in the leaves as in the flat loops, and is asked for the primitives the leaf
+                // holds alone -- the records behind the last leaf are padding, the pid map behind it is not there at all
+                closest_sphere<false>(sc, c, spheres(s0, first), first, o, d, on);
+                if (cnt > 1u) closest_sphere<false>(sc, c, spheres(s1, first + 1u), first + 1u, o, d, on);
+                if (cnt > 2u) closest_sphere<false>(sc, c, spheres(s2, first + 2u), first + 2u, o, d, on);
+                if (cnt > 3u) closest_sphere<false>(sc, c, spheres(s3, first + 3u), first + 3u, o, d, on);
+                return;
+            }
             closest_sphere<false>(sc, c, s0, first, o, d, on);
             if (cnt > 1u) closest_sphere<false>(sc, c, s1, first + 1u, o, d, on);
             if (cnt > 2u) closest_sphere<false>(sc, c, s2, first + 2u, o, d, on);
@@ -874,6 +885,11 @@ __device__ __forceinline__ bool closest_hit(const SceneView &sc, V3 o, V3 d, boo
     if (BVH && H.off_bvh_triangles) {
         bvh_walk(sc, H.off_bvh_triangles, rb, prune_at, off_lane, [&](uint32_t first, uint32_t cnt) {
             const TriRec t0 = load_triangle(S, H, first), t1 = load_triangle(S, H, first + 1u);
+            if constexpr (SPHERES::moves) {                              // (as the spheres' leaves above)
+                closest_triangle<false>(sc, c, t0, first, o, d, on, at.triangle(first));
+                if (cnt > 1u) closest_triangle<false>(sc, c, t1, first + 1u, o, d, on, at.triangle(first + 1u));
+                return;
+            }
             closest_triangle<false>(sc, c, t0, first, o, d, on);
             if (cnt > 1u) closest_triangle<false>(sc, c, t1, first + 1u, o, d, on);
         });
@@ -1030,7 +1046,8 @@ __device__ __forceinline__ void shadow_masks2(const SceneView &sc, bool got, uin
 template <bool BVH, bool CULL, bool EDGES, class SPHERES = StoredSpheres>
 __device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool decided, V3 through, double rho,
                                         const SPHERES &spheres = SPHERES()) {
-    static_assert(!SPHERES::moves || (!BVH && !CULL), "moved spheres walk flat: boxes and bundles hold for the stored centres");
+    static_assert(!SPHERES::moves || (SPHERES::swept && !CULL) || (!BVH && !CULL),
+                  "moved shapes walk flat, or a hierarchy swept over their offsets: boxes and bundles hold for the stored records");
     const double *__restrict__ S = sc.G;
     const rm_dev_header &H = sc.H;
     bool occ = decided;
@@ -1076,6 +1093,13 @@ __device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool de
         bvh_walk(sc, H.off_bvh_spheres, rb, no_limit, occluded, [&](uint32_t first, uint32_t cnt) {
             const SphereRec s0 = load_sphere(S, H, first), s1 = load_sphere(S, H, first + 1u);
             const SphereRec s2 = load_sphere(S, H, first + 2u), s3 = load_sphere(S, H, first + 3u);
+            if constexpr (SPHERES::moves) {                              // (a swept hierarchy: closest_hit's leaves)
+                occ = occ | shadow_sphere(spheres(s0, first), o, d, occ);
+                if (cnt > 1u) occ = occ | shadow_sphere(spheres(s1, first + 1u), o, d, occ);
+                if (cnt > 2u) occ = occ | shadow_sphere(spheres(s2, first + 2u), o, d, occ);
+                if (cnt > 3u) occ = occ | shadow_sphere(spheres(s3, first + 3u), o, d, occ);
+                return;
+            }
             occ = occ | shadow_sphere(s0, o, d, occ);
             if (cnt > 1u) occ = occ | shadow_sphere(s1, o, d, occ);
             if (cnt > 2u) occ = occ | shadow_sphere(s2, o, d, occ);
@@ -1111,6 +1135,11 @@ __device__ __forceinline__ bool any_hit(const SceneView &sc, V3 o, V3 d, bool de
             const TriRec t0 = load_triangle(S, H, first), t1 = load_triangle(S, H, first + 1u);
             double dist;
             V3 p;
+            if constexpr (SPHERES::moves) {
+                occ = occ | triangle_hit(t0, o, d, !occ, dist, p, at.triangle(first));
+                if (cnt > 1u) occ = occ | triangle_hit(t1, o, d, !occ, dist, p, at.triangle(first + 1u));
+                return;
+            }
             occ = occ | triangle_hit(t0, o, d, !occ, dist, p);
             if (cnt > 1u) occ = occ | triangle_hit(t1, o, d, !occ, dist, p);
         });

@@ -482,6 +482,35 @@ struct Renderer {
                                           double focus = 1., bool restart = false) {
         return tick_with_velocities(true, frame, sc, velocities, shutter, n_samples, radii, aperture, focus, restart);
     }
+    // A swept hierarchy of the uploaded scene (rm_swept_build): its hierarchies' boxes refitted to bound every primitive at every
+    // offset within lo[k] .. hi[k] of its shape k (three numbers a shape each).  render_progressive_moving and
+    // render_converging_moving build their own from the velocities; this one serves a host that drives the device calls itself
+    // (accumulate_swept_device below).  Stale once another scene is uploaded; hand it back with swept_free.
+    rm_swept *swept(const std::vector<double> &lo, const std::vector<double> &hi) {
+        if (lo.size() != hi.size() || lo.size() % 3 != 0) throw std::invalid_argument("swept: lo and hi hold three numbers a shape");
+        rm_swept *out = nullptr;
+        check(rm_swept_build(ctx_, lo.data(), hi.data(), (uint32_t)(lo.size() / 3), &out), ctx_);
+        return out;
+    }
+    void swept_free(rm_swept *s) { rm_swept_free(ctx_, s); }
+    // rm_accumulate_swept_device: rm_accumulate_moving_device through `s`, whose extents hold every row of the shape table; device
+    // pointers and the stream are the caller's
+    void accumulate_swept_device(const rm_params &p, const rm_lens &lens, const void *device_table, const void *device_light_offsets,
+                                 uint32_t n_lights, const void *device_shape_offsets, uint32_t n_shapes, const rm_swept *s, uint32_t n_before,
+                                 void *device_sum, void *device_mean, void *device_rgb8, void *hip_stream) {
+        check(rm_accumulate_swept_device(ctx_, &p, &lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes, s, n_before,
+                                         device_sum, device_mean, device_rgb8, hip_stream),
+              ctx_);
+    }
+    // ... and rm_accumulate_converging_swept_device, likewise
+    void accumulate_converging_swept_device(const rm_params &p, const rm_lens &lens, const rm_converge &converge, const void *device_table,
+                                            uint32_t table_rows, const void *device_light_offsets, uint32_t n_lights,
+                                            const void *device_shape_offsets, uint32_t n_shapes, const rm_swept *s, bool fresh,
+                                            const rm_converge_frame &buffers, void *hip_stream) {
+        check(rm_accumulate_converging_swept_device(ctx_, &p, &lens, &converge, device_table, table_rows, device_light_offsets, n_lights,
+                                                    device_shape_offsets, n_shapes, s, fresh ? 1 : 0, &buffers, hip_stream),
+              ctx_);
+    }
     // The tick of the two calls above; any_shape: the second
     std::string tick_with_velocities(bool any_shape, framebuffer::FrameBuffer &frame, const scene::Scene &sc,
                                      const std::vector<Vec3f> &velocities, double shutter, uint32_t n_samples, const std::vector<double> &radii,

@@ -222,6 +222,7 @@ pub struct RmCameraBasis {
 
 pub enum RmScene {}
 pub enum RmCtx {}
+pub enum RmSwept {}
 
 // Every entry point of include/rusty_marcher_amd.h, in its order (tests/test_rust_binding.py
 // checks names, arity and argument classes against the header).
@@ -335,6 +336,12 @@ extern "C" {
     fn rm_render_progressive_camera(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, motion: *const RmCameraMotion, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
     fn rm_render_converging_camera(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, motion: *const RmCameraMotion, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_render_converging_moving(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, velocities: *const RmVec3, n_shapes: u32, shutter: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
+    fn rm_swept_extents(table: *const f64, rows: u32, n_shapes: u32, lo: *mut f64, hi: *mut f64) -> c_int;
+    fn rm_swept_motion_extents(velocities: *const RmVec3, n_shapes: u32, shutter: f64, lo: *mut f64, hi: *mut f64) -> c_int;
+    fn rm_swept_build(ctx: *mut RmCtx, lo: *const f64, hi: *const f64, n_shapes: u32, out: *mut *mut RmSwept) -> c_int;
+    fn rm_swept_free(ctx: *mut RmCtx, swept: *mut RmSwept);
+    fn rm_accumulate_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_accumulate_converging_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -907,6 +914,104 @@ impl Gpu {
         check(
             unsafe {
                 rm_accumulate_moving_device(self.ctx, &p, &lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// A swept hierarchy of the uploaded scene: its hierarchies' boxes refitted to bound every primitive at every offset within
+    /// `lo[k] .. hi[k]` of its shape k (three f64 a shape each, finite, lo <= hi).  Stale once another scene is uploaded; hand it
+    /// back with `swept_free`.
+    pub fn swept(&mut self, lo: &[f64], hi: &[f64]) -> *mut RmSwept {
+        assert!(lo.len() == hi.len() && lo.len() % 3 == 0, "swept: lo and hi hold three numbers a shape");
+        let mut out: *mut RmSwept = std::ptr::null_mut();
+        check(unsafe { rm_swept_build(self.ctx, lo.as_ptr(), hi.as_ptr(), (lo.len() / 3) as u32, &mut out) }, self.ctx);
+        out
+    }
+
+    /// Releases a handle of `swept` (waits for the device).
+    pub fn swept_free(&mut self, swept: *mut RmSwept) {
+        unsafe { rm_swept_free(self.ctx, swept) };
+    }
+
+    /// The per-shape componentwise minimum and maximum of a host shape offset table of `rows` rows: (lo, hi).
+    pub fn swept_extents(table: &[f64], rows: u32, n_shapes: u32) -> (Vec<f64>, Vec<f64>) {
+        assert!(table.len() == 3 * rows as usize * n_shapes as usize, "swept_extents: the table holds rows x n_shapes x 3 numbers");
+        let (mut lo, mut hi) = (vec![0f64; 3 * n_shapes as usize], vec![0f64; 3 * n_shapes as usize]);
+        check(unsafe { rm_swept_extents(table.as_ptr(), rows, n_shapes, lo.as_mut_ptr(), hi.as_mut_ptr()) }, std::ptr::null());
+        (lo, hi)
+    }
+
+    /// The extents that hold every row of `motion_sequence(.., velocities, shutter)`: (lo, hi).
+    pub fn swept_motion_extents(velocities: &[Vec3f], shutter: f64) -> (Vec<f64>, Vec<f64>) {
+        let v: Vec<RmVec3> = velocities.iter().map(|v| RmVec3 { x: v.x, y: v.y, z: v.z }).collect();
+        let (mut lo, mut hi) = (vec![0f64; 3 * v.len()], vec![0f64; 3 * v.len()]);
+        check(unsafe { rm_swept_motion_extents(v.as_ptr(), v.len() as u32, shutter, lo.as_mut_ptr(), hi.as_mut_ptr()) }, std::ptr::null());
+        (lo, hi)
+    }
+
+    /// `accumulate_moving` through the swept hierarchy `swept`, whose extents hold every row of the shape table: the same bytes,
+    /// with the scene's hierarchies walked.
+    pub fn accumulate_swept(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        swept: *const RmSwept,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_swept_device(self.ctx, &p, &lens, device_table, device_light_offsets, n_lights, device_shape_offsets, n_shapes, swept, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// `accumulate_converging_moving` through the swept hierarchy `swept`.
+    pub fn accumulate_converging_swept(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        swept: *const RmSwept,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_swept_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, swept, if fresh { 1 } else { 0 }, &buffers, hip_stream)
             },
             self.ctx,
         );
