@@ -1454,8 +1454,12 @@ rm_status rm_render_converging_camera(rm_ctx *ctx, const rm_params *params, cons
  * build it again when the scene, a velocity or the shutter changes -- what begins the frame again
  * anyway.  RM_SWEPT_BVH=0 in the environment of rm_init makes them walk flat as before.
  *
- * Staying flat: the moving spheres' calls (..._motion) and the moving camera's calls given
- * velocities.  Not here either: the bundle cull and occluder masks under motion, rotation.
+ * The moving spheres' ticks and the moving camera's walk one too: "swept hierarchies under a moving
+ * camera", below.  Staying flat: the moving spheres' DEVICE calls (rm_accumulate_motion_device,
+ * rm_accumulate_converging_motion_device) -- a caller's table may hold non-zero rows they ignore,
+ * which no extents could be read from; a caller who wants a hierarchy there has
+ * rm_accumulate_swept_device, with rows of zero for everything but the spheres.  Not here either:
+ * the bundle cull and occluder masks under motion, rotation.
  */
 typedef struct rm_swept rm_swept;   /* a swept hierarchy of the resident scene (opaque) */
 
@@ -1472,6 +1476,66 @@ rm_status rm_accumulate_converging_swept_device(rm_ctx *ctx, const rm_params *pa
                                                 const void *device_light_offsets, uint32_t n_lights,
                                                 const void *device_shape_offsets, uint32_t n_shapes, const rm_swept *swept,
                                                 int fresh, const rm_converge_frame *buffers, void *hip_stream);
+
+/* ---- swept hierarchies under a moving camera -----------------------------------------------------
+ * A shot in which the camera pans and something in the scene moves is the ordinary motion-blur
+ * shot.  These calls are the moving camera's with a shape table, through a swept hierarchy: camera
+ * rule, moved lights and the moving shapes' rule applied inside the leaves.  Additive to ABI
+ * version 5; a host detects them by " swept-camera" in rm_build_info().
+ *
+ * Handles come from rm_swept_build, and the extents from rm_swept_extents or
+ * rm_swept_motion_extents, as they are: the boxes are in world space and bound primitives, not
+ * rays, so they hold wherever a ray starts and whichever way it looks.  No extents call takes a
+ * camera table.
+ *
+ * rm_accumulate_camera_swept_device has rm_accumulate_camera_device's argument list and checks, and
+ * rm_accumulate_converging_camera_swept_device rm_accumulate_converging_camera_device's, plus the
+ * handle behind n_shapes and its three refusals (NULL, not this context's or freed, built before the
+ * scene last changed).  A NULL device_shape_offsets is refused here: without a shape table nothing
+ * moves, and the flat calls keep the hierarchy already.  A refused call names the offender in
+ * rm_last_error and touches no buffer.  Both are asynchronous on the caller's stream and keep no
+ * state of their own.
+ *
+ * Contract: the swept calls'.  With every shape row inside the handle's extents a pass leaves byte
+ * for byte what the flat camera call leaves given the same tables -- sum, mean and display bytes;
+ * for the converging call stats, counts, list and workspace as well.  A shape row outside the
+ * extents gives unspecified pixels, never a fault: nothing read from an offset row, a box or a
+ * camera row forms an address.  For an image without a hierarchy the flat kernels run.
+ *
+ * The ticks.  Every tick that moves a shape walks a swept hierarchy where the resident image holds
+ * one: rm_render_progressive_moving and rm_render_converging_moving as before,
+ * rm_render_progressive_camera and rm_render_converging_camera given velocities, and the moving
+ * spheres' rm_render_progressive_motion and rm_render_converging_motion in a scene with spheres.
+ * The last two launch the moving shapes' swept kernels: they refuse a velocity on anything but a
+ * sphere, so their table's other rows are zeros, and such a pass writes the moving spheres' bytes
+ * ("moving shapes", zero offsets).  Signatures, frames, keys and bytes of all six stay what they
+ * were.  They share one hierarchy, kept until the scene, a velocity or the shutter changes: a
+ * camera tick behind a moving shapes' tick with the same velocities and shutter builds nothing.  A
+ * call about to be refused builds nothing.  RM_SWEPT_BVH=0 returns all six to the flat walk.
+ *
+ * rm_swept_tick_info says what the ticks did; it reads host state only and launches nothing.
+ * walked_swept: 1 where the launch of the last tick of the sampled-frame family (any
+ * rm_render_progressive* or rm_render_converging* call) walked a swept hierarchy; every such tick
+ * clears it first, so a refused, saturated or finished tick leaves 0.  builds: the hierarchies the
+ * ticks have built over the context's life (rm_swept_build's handles are not counted).
+ */
+typedef struct rm_swept_tick_report {
+    uint32_t walked_swept;
+    uint32_t builds;
+} rm_swept_tick_report;    /* 8 bytes */
+
+rm_status rm_accumulate_camera_swept_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                            const void *device_camera_rows, const void *device_light_offsets, uint32_t n_lights,
+                                            const void *device_shape_offsets, uint32_t n_shapes, const rm_swept *swept,
+                                            uint32_t n_before, void *device_sum, void *device_mean /* optional */,
+                                            void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_accumulate_converging_camera_swept_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                                       const rm_converge *converge, const void *device_table, uint32_t table_rows,
+                                                       const void *device_camera_rows, const void *device_light_offsets,
+                                                       uint32_t n_lights, const void *device_shape_offsets, uint32_t n_shapes,
+                                                       const rm_swept *swept, int fresh, const rm_converge_frame *buffers,
+                                                       void *hip_stream);
+rm_status rm_swept_tick_info(rm_ctx *ctx, rm_swept_tick_report *out);
 
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);

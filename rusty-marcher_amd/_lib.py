@@ -135,6 +135,12 @@ class rm_camera_motion(C.Structure):
     _fields_ = [("velocity", rm_vec3), ("yaw", C.c_double), ("pitch", C.c_double), ("roll", C.c_double)]
 
 
+class rm_swept_tick_report(C.Structure):
+    """What the ticks that move a shape did: whether the last sampled-frame tick's launch walked a swept hierarchy, and how many
+    hierarchies the ticks have built over the context's life (8 bytes)."""
+    _fields_ = [("walked_swept", C.c_uint32), ("builds", C.c_uint32)]
+
+
 _P = C.POINTER
 _VP = C.c_void_p
 
@@ -272,6 +278,11 @@ SIGNATURES = {
                                              _VP, _VP]),
     "rm_accumulate_converging_swept_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, C.c_uint32, _VP,
                                                         C.c_uint32, _VP, C.c_int, _P(rm_converge_frame), _VP]),
+    "rm_accumulate_camera_swept_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, C.c_uint32,
+                                                    _VP, _VP, _VP, _VP]),
+    "rm_accumulate_converging_camera_swept_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, _VP,
+                                                               C.c_uint32, _VP, C.c_uint32, _VP, C.c_int, _P(rm_converge_frame), _VP]),
+    "rm_swept_tick_info": (C.c_int, [_VP, _P(rm_swept_tick_report)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -1178,6 +1178,78 @@ class Context:
                                                       *host, C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
+    # ---- swept hierarchies under a moving camera (include/rusty_marcher_amd.h, "swept hierarchies under a moving camera") ----
+    def _camera_swept_for(self, swept, shape_offsets):
+        """_swept_for for the camera calls, whose shape table may be None: the library refuses that by name, but no handle
+        can be built from it."""
+        if swept is None and shape_offsets is None:
+            raise ValueError("shape_offsets is None and no swept handle is given: nothing moves, use the flat camera call")
+        return self._swept_for(swept, shape_offsets)
+
+    def accumulate_camera_swept_device(self, params, sum, aperture, focus, table, camera_rows, light_offsets, shape_offsets, n_before,
+                                       mean=None, rgb8=None, stream=None, swept=None):
+        """rm_accumulate_camera_swept_device: accumulate_camera_device with a shape table through a swept hierarchy -- the same
+        bytes, with the scene's hierarchies walked where it has any.  swept: a handle of Context.swept whose extents hold every
+        row of shape_offsets (the boxes are in world space: no camera row matters); None builds one from the table itself.
+        Arguments and result as accumulate_camera_device's, but that the library refuses shape_offsets None."""
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        camera_rows = _camera_rows_tensor(camera_rows, lens.n_samples, sum.device)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", lens.n_samples, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), 0
+        if shape_offsets is not None:
+            shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", lens.n_samples, sum.device)
+            n_shapes = int(shape_offsets.shape[1])
+        handle = self._camera_swept_for(swept, shape_offsets)
+        try:
+            _lib.check(self.L.rm_accumulate_camera_swept_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                                C.c_void_p(camera_rows.data_ptr()),
+                                                                C.c_void_p(light_offsets.data_ptr()) if n_lights > 0 else None, n_lights,
+                                                                C.c_void_p(shape_offsets.data_ptr()) if n_shapes > 0 else None, n_shapes,
+                                                                handle.ptr, int(n_before), C.c_void_p(sum.data_ptr()),
+                                                                C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                                C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                                C.c_void_p(self._stream(stream))), self.ptr)
+        finally:
+            if swept is None:
+                handle.close()                                  # (waits for the device: the pass is through)
+        return table, camera_rows, light_offsets, shape_offsets
+
+    def accumulate_converging_camera_swept_device(self, params, sum, stats, count, aperture, focus, n_samples, table, camera_rows,
+                                                  light_offsets, shape_offsets, tolerance, min_samples, max_samples, fresh, mean=None,
+                                                  rgb8=None, mask=None, workspace=None, stream=None, swept=None):
+        """rm_accumulate_converging_camera_swept_device: accumulate_converging_camera_device with a shape table through a swept
+        hierarchy -- the same bytes, lists and counts.  swept: as accumulate_camera_swept_device's.  Arguments and result as
+        accumulate_converging_camera_device's."""
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
+        rows = int(table.shape[0])
+        camera_rows = _camera_rows_tensor(camera_rows, rows, sum.device)
+        light_offsets = _offset_tensor(light_offsets, "light_offsets", "n_lights", rows, sum.device)
+        n_lights, n_shapes = int(light_offsets.shape[1]), 0
+        if shape_offsets is not None:
+            shape_offsets = _offset_tensor(shape_offsets, "shape_offsets", "n_shapes", rows, sum.device)
+            n_shapes = int(shape_offsets.shape[1])
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        handle = self._camera_swept_for(swept, shape_offsets)
+        try:
+            _lib.check(self.L.rm_accumulate_converging_camera_swept_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table),
+                                                                           rows, vp(camera_rows), vp(light_offsets) if n_lights > 0 else None,
+                                                                           n_lights, vp(shape_offsets) if n_shapes > 0 else None, n_shapes,
+                                                                           handle.ptr, 1 if fresh else 0, C.byref(frame),
+                                                                           C.c_void_p(self._stream(stream))), self.ptr)
+        finally:
+            if swept is None:
+                handle.close()
+        return workspace
+
+    def swept_tick_info(self):
+        """rm_swept_tick_info: what the ticks that move a shape did -> {"walked_swept": whether the last sampled-frame tick's
+        launch walked a swept hierarchy, "builds": hierarchies the ticks have built over the context's life}.  Host state only."""
+        rep = _lib.rm_swept_tick_report()
+        _lib.check(self.L.rm_swept_tick_info(self.ptr, C.byref(rep)), self.ptr)
+        return {"walked_swept": int(rep.walked_swept), "builds": int(rep.builds)}
+
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole
         patch rows), as DeviceHits of [frame_height][frame_width].  `out`: a float64 tensor of shape

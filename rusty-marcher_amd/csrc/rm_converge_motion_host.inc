@@ -32,6 +32,12 @@ static rm_status launch_converge_camera(rm_ctx *ctx, const rm_params *p, const r
                                         uint32_t table_rows, const void *offsets, const void *shape_offsets, const void *camera_rows, int fresh,
                                         const rm_converge_frame *b, hipStream_t stream);
 
+// The moving spheres' three steps over the ticks' swept hierarchy where tick_swept_prepare made it ready (rm_swept_host.inc,
+// behind this file) -- launch_converge_motion where not
+static rm_status launch_converge_motion_tick(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                             uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
+                                             const rm_converge_frame *b, hipStream_t stream);
+
 // A resident prefix of a sequence: rows [0, rows) of `columns` doubles each (the lens table: 4; an offset table: 3 a light or
 // shape; the camera table: 12)
 struct rm_resident_prefix {
@@ -122,6 +128,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                                            const rm_sampling_rules &rules, int restart, double *host_rgb, uint8_t *host_rgb8,
                                            rm_converge_report *report, rm_timing *timing, converge_motion_launch any_shape = nullptr) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    ctx->swept_walked = 0u;                                                // (until a launch of this tick walks a swept hierarchy)
     const auto t_begin = std::chrono::steady_clock::now();
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
     if (rm_status rst = check_rules(ctx, who, rules, any_shape != nullptr)) return rst;
@@ -197,8 +204,8 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                     return any_shape(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, shapes ? g.shapes.d : nullptr,
                                      g.n == 0u, &b, ctx->stream);
                 if (rules.motion)
-                    return launch_converge_motion(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr,
-                                                  shapes ? g.shapes.d : nullptr, g.n == 0u, &b, ctx->stream);
+                    return launch_converge_motion_tick(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr,
+                                                       shapes ? g.shapes.d : nullptr, g.n == 0u, &b, ctx->stream);
                 return launch_converge(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, g.n == 0u, &b, ctx->stream);
             };
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
@@ -257,7 +264,9 @@ rm_status rm_render_converging(rm_ctx *ctx, const rm_params *params, const rm_le
 rm_status rm_render_converging_motion(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
                                       const double *radii, uint32_t n_lights, const rm_vec3 *velocities, uint32_t n_shapes, double shutter,
                                       int restart, double *host_rgb, uint8_t *host_rgb8, rm_converge_report *report, rm_timing *timing) {
-    return guarded(ctx, "rm_render_converging_motion", [&]() {
+    return guarded(ctx, "rm_render_converging_motion", [&]() -> rm_status {
+        const tick_swept_scope done{ctx};
+        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_converging_motion", velocities, n_shapes, shutter, true)) return pst;
         return rm_render_converging_impl(ctx, "rm_render_converging_motion", params, lens, converge,
                                          rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb, host_rgb8, report,
                                          timing);

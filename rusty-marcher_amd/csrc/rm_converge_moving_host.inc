@@ -55,11 +55,11 @@ rm_status rm_render_converging_moving(rm_ctx *ctx, const rm_params *params, cons
                                       const double *radii, uint32_t n_lights, const rm_vec3 *velocities, uint32_t n_shapes, double shutter,
                                       int restart, double *host_rgb, uint8_t *host_rgb8, rm_converge_report *report, rm_timing *timing) {
     return guarded(ctx, "rm_render_converging_moving", [&]() -> rm_status {
-        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_converging_moving", velocities, n_shapes, shutter)) return pst;
+        const tick_swept_scope done{ctx};
+        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_converging_moving", velocities, n_shapes, shutter, false)) return pst;
         const rm_status st = rm_render_converging_impl(ctx, "rm_render_converging_moving", params, lens, converge,
                                                        rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb,
                                                        host_rgb8, report, timing, launch_converge_moving_tick);
-        tick_swept_done(ctx);
         return st;
     });
 }

@@ -38,6 +38,8 @@
 #include "rm_swept_image.hpp"
 #include "rm_swept.hpp"
 #include "rm_converge_swept.hpp"
+#include "rm_camera_swept.hpp"
+#include "rm_converge_camera_swept.hpp"
 
 using namespace rmdev;
 
@@ -240,8 +242,10 @@ struct rm_ctx {
     // converging frames (rm_converge_motion_host.inc): made by the first rm_render_converging, rm_render_converging_motion or rm_render_converging_moving; shares nothing with `progressive`
     rm_converging *converging = nullptr;
 
-    // swept hierarchies (rm_swept_host.inc): the one the moving shapes' ticks walk, built from their velocities and shutter
+    // swept hierarchies (rm_swept_host.inc): the one the ticks that move a shape walk, built from their velocities and shutter
     rm_tick_swept *tick_swept = nullptr;
+    uint32_t swept_walked = 0;               // the last sampled-frame tick's launch walked it (rm_swept_tick_info): set by the launches, cleared by the ticks
+    uint32_t swept_builds = 0;               // hierarchies tick_swept_prepare has built
     std::vector<rm_swept *> swept_handles;   // every handle rm_swept_build gave out and rm_swept_free has not taken back
 
     // post-process scratch
@@ -347,7 +351,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy converge-moving converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy swept-camera converge-moving converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1143,5 +1147,6 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_converge_host.inc"
 #include "rm_converge_motion_host.inc"
 #include "rm_converge_moving_host.inc"
-#include "rm_camera_host.inc"
 #include "rm_swept_host.inc"
+#include "rm_camera_host.inc"
+#include "rm_camera_swept_host.inc"

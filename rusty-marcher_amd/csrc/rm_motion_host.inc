@@ -29,6 +29,20 @@ using motion_launch = rm_status (*)(rm_ctx *ctx, const accum_call &c, const void
 // no shape moves
 static rm_status launch_camera(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets, const void *camera_rows);
 
+// The ticks' swept hierarchy (rm_swept_host.inc, behind this file): made ready in front of a tick that moves a shape for its
+// velocities and shutter (`spheres_only`: the moving spheres' ticks, whose rule it applies), and the moving spheres' launch that
+// walks it where it is ready -- launch_motion where it is not
+static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter,
+                                    bool spheres_only);
+static void tick_swept_done(rm_ctx *ctx);
+// ... and tick_swept_done when the scope is left, by a return or by an exception on its way to `guarded`: a hierarchy left ready
+// would be walked by the next tick that prepared none
+struct tick_swept_scope {
+    rm_ctx *ctx;
+    ~tick_swept_scope() { tick_swept_done(ctx); }
+};
+static rm_status launch_motion_tick(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets);
+
 // The basis rm_camera_get reports: the context's where it is oriented, else the fixed view's
 static rm_camera_basis reported_basis(const rm_ctx *ctx) {
     const rm_camera_basis fixed{{1., 0., 0.}, {0., 1., 0.}, {0., 0., -1.}};
@@ -83,6 +97,7 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
                                             int restart, double *host_rgb, uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing,
                                             motion_launch any_shape = nullptr) {
     if (!ctx) return ctx_fail(nullptr, RM_ERR_INVALID_ARG, std::string(who) + ": NULL ctx");
+    ctx->swept_walked = 0u;                                                // (until a launch of this tick walks a swept hierarchy)
     const auto t_begin = std::chrono::steady_clock::now();
     if (rm_status cst = check_accum(ctx, who, p, lens)) return cst;
     if (rm_status rst = check_rules(ctx, who, rules, any_shape != nullptr)) return rst;
@@ -124,7 +139,7 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
             auto launch = [&]() {
                 if (rules.camera) return launch_camera(ctx, call, lights, shapes, g.camera.d);
                 if (any_shape) return any_shape(ctx, call, lights, shapes);
-                return rules.motion ? launch_motion(ctx, call, lights, shapes) : rules.soft ? launch_soft(ctx, call, lights) : launch_accum(ctx, call);
+                return rules.motion ? launch_motion_tick(ctx, call, lights, shapes) : rules.soft ? launch_soft(ctx, call, lights) : launch_accum(ctx, call);
             };
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
             g.id = std::move(id);
@@ -179,7 +194,9 @@ rm_status rm_render_progressive_soft(rm_ctx *ctx, const rm_params *params, const
 rm_status rm_render_progressive_motion(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *radii, uint32_t n_lights,
                                        const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart, double *host_rgb,
                                        uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
-    return guarded(ctx, "rm_render_progressive_motion", [&]() {
+    return guarded(ctx, "rm_render_progressive_motion", [&]() -> rm_status {
+        const tick_swept_scope done{ctx};
+        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_progressive_motion", velocities, n_shapes, shutter, true)) return pst;
         return rm_render_progressive_impl(ctx, "rm_render_progressive_motion", params, lens,
                                           rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb, host_rgb8, n_total,
                                           timing);

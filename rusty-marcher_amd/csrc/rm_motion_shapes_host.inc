@@ -18,10 +18,8 @@ static rm_status launch_moving(rm_ctx *ctx, const accum_call &c, const void *off
     return launch_shading(ctx, shade_family{"moving shapes", rm_motion_shapes_kernel}, a.S.A.L.max_depth, lens_extent(ctx, a.S.A.L), a, c.stream);
 }
 
-// The ticks' hierarchy (rm_swept_host.inc, behind this file): made ready in front of a tick for its velocities and shutter, and the
-// launch that walks it where it is -- launch_moving where it is not
-static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter);
-static void tick_swept_done(rm_ctx *ctx);
+// The ticks' hierarchy (rm_swept_host.inc, behind this file; tick_swept_prepare and tick_swept_done are declared in
+// rm_motion_host.inc): the launch that walks it where it is ready -- launch_moving where it is not
 static rm_status launch_moving_tick(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets);
 
 extern "C" {
@@ -49,11 +47,11 @@ rm_status rm_render_progressive_moving(rm_ctx *ctx, const rm_params *params, con
                                        const rm_vec3 *velocities, uint32_t n_shapes, double shutter, int restart, double *host_rgb,
                                        uint8_t *host_rgb8, uint32_t *n_total, rm_timing *timing) {
     return guarded(ctx, "rm_render_progressive_moving", [&]() -> rm_status {
-        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_progressive_moving", velocities, n_shapes, shutter)) return pst;
+        const tick_swept_scope done{ctx};
+        if (rm_status pst = tick_swept_prepare(ctx, "rm_render_progressive_moving", velocities, n_shapes, shutter, false)) return pst;
         const rm_status st = rm_render_progressive_impl(ctx, "rm_render_progressive_moving", params, lens,
                                                         rules_with_motion(radii, n_lights, velocities, n_shapes, shutter), restart, host_rgb,
                                                         host_rgb8, n_total, timing, launch_moving_tick);
-        tick_swept_done(ctx);
         return st;
     });
 }

@@ -33,10 +33,12 @@ struct rm_knobs {
     // drain (1080p demo: 124 -> 116 us; hashed order 131 us).
     int tile_order = TILE_ORDER_REVERSE;
     bool disable_bvh = false;         // RM_DISABLE_BVH=1: brute-force walk
-    // The moving shapes' ticks (rm_render_progressive_moving, rm_render_converging_moving) walk a swept hierarchy where the
-    // resident image holds one (rm_swept_host.inc, tick_walks_swept): RM_SWEPT_BVH=0 walks flat as they always did (the A/B
-    // switch; frames are bit-equal).  On by measurement: the Cornell box's 36 triangles, the smallest hierarchy there is, take
-    // 0.50 to 0.73 of the flat pass's time (profiles/swept_figures.txt).
+    // The six ticks that move a shape -- the moving shapes' (rm_render_progressive_moving, rm_render_converging_moving), the
+    // moving camera's given velocities (rm_render_progressive_camera, rm_render_converging_camera) and the moving spheres'
+    // (rm_render_progressive_motion, rm_render_converging_motion) -- walk a swept hierarchy where the resident image holds one
+    // (rm_swept_host.inc, tick_walks_swept): RM_SWEPT_BVH=0 returns all six to the flat walk (the A/B switch; frames are
+    // bit-equal).  On by measurement: the Cornell box's 36 triangles, the smallest hierarchy there is, take 0.50 to 0.73 of the
+    // flat pass's time (profiles/swept_figures.txt; the camera's and the spheres' ticks: profiles/camera_swept_figures.txt).
     bool swept_bvh = true;
     // Ray bundles whose half-angle has at least this cosine cull primitives before a walk
     // (rm_trace.inc); wider ones take the plain walk / the hierarchy.  RM_DISABLE_CULL=1 sets 2

@@ -6,8 +6,11 @@
 // A swept hierarchy (rm_swept) is a device copy of the resident image's blob with refitted boxes, and the image epoch it was built
 // at.  The two device calls are their moving-shapes siblings with that blob in place of the resident one: they touch no render
 // state and keep none of their own, one launch (three steps for the converging call) on the caller's stream, nothing waited for.
-// The moving shapes' ticks build one of their own from the velocities and the shutter (rm_tick_swept) and keep it until the
-// image, a velocity or the shutter changes.
+// The ticks that move a shape -- the moving shapes', the moving spheres' (rm_motion_host.inc, rm_converge_motion_host.inc) and
+// the moving camera's given velocities (rm_camera_host.inc, behind this file) -- build one of their own from the velocities and
+// the shutter (rm_tick_swept) and keep it until the image, a velocity or the shutter changes: one for all six, so a camera tick
+// behind a moving shapes' tick with the same velocities and shutter builds nothing.  What the last tick's launch walked, and how
+// many were built, rm_swept_tick_info reports (rm_camera_swept_host.inc).
 
 struct rm_swept {
     double *d_blob = nullptr;
@@ -107,19 +110,22 @@ static void tick_swept_destroy(rm_ctx *ctx, bool device_ok) {
     ctx->tick_swept = nullptr;
 }
 
-// Whether the moving shapes' ticks walk a swept hierarchy over the resident image: wherever it holds a hierarchy, unless
+// Whether the ticks that move a shape walk a swept hierarchy over the resident image: wherever it holds a hierarchy, unless
 // RM_SWEPT_BVH=0 (rm_knobs::swept_bvh).  No primitive-count threshold: on the smallest hierarchy of the suite, the Cornell box's 36
-// triangles, the swept pass takes 0.50 to 0.73 of the flat pass's time (profiles/swept_figures.txt).
+// triangles, the swept pass takes 0.50 to 0.73 of the flat pass's time (profiles/swept_figures.txt; under a moving camera and for
+// the moving spheres' ticks: profiles/camera_swept_figures.txt).
 static bool tick_walks_swept(const rm_ctx *ctx) {
     const rm_dev_header &H = ctx->image.H;
     return ctx->knobs.swept_bvh && (H.off_bvh_spheres || H.off_bvh_triangles);
 }
 
-// In front of a moving shapes' tick: makes the ticks' hierarchy the one of the resident image, `velocities` and `shutter`, and
-// says so in `ready`.  Arguments the tick is about to refuse build nothing and are left for it to name; so are extents that are
-// not finite (a product that overflows): that tick walks flat.  The streams the ticks launch on were waited for, so the old blob
-// is free to go.
-static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter) {
+// In front of a tick that moves a shape: makes the ticks' hierarchy the one of the resident image, `velocities` and `shutter`, and
+// says so in `ready`.  Arguments the tick is about to refuse build nothing and are left for it to name -- with `spheres_only`
+// (the moving spheres' ticks) a velocity on anything but a sphere is among them, and a scene without spheres, where those ticks
+// need not stage a shape table, is left alone; so are extents that are not finite (a product that overflows): that tick walks
+// flat.  The streams the ticks launch on were waited for, so the old blob is free to go.
+static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter,
+                                    bool spheres_only) {
     if (!ctx) return RM_OK;
     if (!ctx->tick_swept) ctx->tick_swept = new rm_tick_swept();
     rm_tick_swept &t = *ctx->tick_swept;
@@ -127,6 +133,13 @@ static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 
     if (!ctx->have_scene || !tick_walks_swept(ctx)) return RM_OK;
     if (n_shapes != resident_shape_count(ctx) || n_shapes == 0u || !velocities) return RM_OK;
     if (rm_check_velocities(who, velocities, n_shapes, shutter) != RM_OK) return RM_OK;
+    if (spheres_only) {
+        if (ctx->image.H.n_spheres == 0u) return RM_OK;
+        for (uint32_t k = 0; k < n_shapes; k++) {                         // (check_rules' rule: only spheres move)
+            const rm_vec3 &v = velocities[k];
+            if (resident_shape(ctx, k).kind != RM_SHAPE_SPHERE && (v.x != 0. || v.y != 0. || v.z != 0.)) return RM_OK;
+        }
+    }
     const bool same = t.swept && t.swept->image_epoch == ctx->image_epoch && t.velocities.size() == n_shapes &&
                       std::memcmp(t.velocities.data(), velocities, (size_t)n_shapes * sizeof(rm_vec3)) == 0 &&
                       std::memcmp(&t.shutter, &shutter, sizeof shutter) == 0;
@@ -141,6 +154,7 @@ static rm_status tick_swept_prepare(rm_ctx *ctx, const char *who, const rm_vec3 
         if (rm_status bst = swept_build(ctx, who, lo.data(), hi.data(), n_shapes, &t.swept)) return bst;
         t.velocities.assign(velocities, velocities + n_shapes);
         t.shutter = shutter;
+        ctx->swept_builds += 1u;
     }
     t.ready = true;
     return RM_OK;
@@ -150,21 +164,52 @@ static void tick_swept_done(rm_ctx *ctx) {
     if (ctx && ctx->tick_swept) ctx->tick_swept->ready = false;
 }
 
+// The hierarchy the tick in progress may walk: the ticks' own where tick_swept_prepare made it ready and the pass has a shape
+// table, else NULL (the flat walk).  A launch that takes it says so (rm_swept_tick_info).
+static const rm_swept *tick_swept_ready(const rm_ctx *ctx, const void *shape_offsets) {
+    const rm_tick_swept *t = ctx->tick_swept;
+    return t && t->ready && shape_offsets ? t->swept : nullptr;
+}
+
 // The launches the moving shapes' ticks hand their tick bodies: the swept walk where tick_swept_prepare made one ready (and the
 // pass has a shape table), else the flat one
 static rm_status launch_moving_tick(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets) {
-    const rm_tick_swept *t = ctx->tick_swept;
-    if (t && t->ready && shape_offsets) return launch_swept(ctx, t->swept, c, offsets, shape_offsets);
+    if (const rm_swept *s = tick_swept_ready(ctx, shape_offsets)) {
+        ctx->swept_walked = 1u;
+        return launch_swept(ctx, s, c, offsets, shape_offsets);
+    }
     return launch_moving(ctx, c, offsets, shape_offsets);
+}
+
+// ... and the moving spheres' ticks theirs: check_rules refused a velocity on anything but a sphere, so the staged table's other
+// rows are zeros, and a moving shapes' pass with such rows writes the moving spheres' bytes (include/rusty_marcher_amd.h, "moving
+// shapes"): the swept walk is rm_swept.hip's, no kernel of its own
+static rm_status launch_motion_tick(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets) {
+    if (const rm_swept *s = tick_swept_ready(ctx, shape_offsets)) {
+        ctx->swept_walked = 1u;
+        return launch_swept(ctx, s, c, offsets, shape_offsets);
+    }
+    return launch_motion(ctx, c, offsets, shape_offsets);
 }
 
 static rm_status launch_converge_moving_tick(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
                                              uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
                                              const rm_converge_frame *b, hipStream_t stream) {
-    const rm_tick_swept *t = ctx->tick_swept;
-    if (t && t->ready && shape_offsets)
-        return launch_converge_swept(ctx, t->swept, p, lens, c, table, table_rows, offsets, shape_offsets, fresh, b, stream);
+    if (const rm_swept *s = tick_swept_ready(ctx, shape_offsets)) {
+        ctx->swept_walked = 1u;
+        return launch_converge_swept(ctx, s, p, lens, c, table, table_rows, offsets, shape_offsets, fresh, b, stream);
+    }
     return launch_converge_moving(ctx, p, lens, c, table, table_rows, offsets, shape_offsets, fresh, b, stream);
+}
+
+static rm_status launch_converge_motion_tick(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                             uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
+                                             const rm_converge_frame *b, hipStream_t stream) {
+    if (const rm_swept *s = tick_swept_ready(ctx, shape_offsets)) {
+        ctx->swept_walked = 1u;
+        return launch_converge_swept(ctx, s, p, lens, c, table, table_rows, offsets, shape_offsets, fresh, b, stream);
+    }
+    return launch_converge_motion(ctx, p, lens, c, table, table_rows, offsets, shape_offsets, fresh, b, stream);
 }
 
 extern "C" {

@@ -511,6 +511,32 @@ struct Renderer {
                                                     device_shape_offsets, n_shapes, s, fresh ? 1 : 0, &buffers, hip_stream),
               ctx_);
     }
+    // rm_accumulate_camera_swept_device: rm_accumulate_camera_device with a shape table through `s` (a handle of swept(); the boxes
+    // are in world space, so no camera row matters).  A NULL shape table is refused: the flat call keeps the hierarchy then.
+    void accumulate_camera_swept_device(const rm_params &p, const rm_lens &lens, const void *device_table, const void *device_camera_rows,
+                                        const void *device_light_offsets, uint32_t n_lights, const void *device_shape_offsets, uint32_t n_shapes,
+                                        const rm_swept *s, uint32_t n_before, void *device_sum, void *device_mean, void *device_rgb8,
+                                        void *hip_stream) {
+        check(rm_accumulate_camera_swept_device(ctx_, &p, &lens, device_table, device_camera_rows, device_light_offsets, n_lights,
+                                                device_shape_offsets, n_shapes, s, n_before, device_sum, device_mean, device_rgb8, hip_stream),
+              ctx_);
+    }
+    // ... and rm_accumulate_converging_camera_swept_device, likewise
+    void accumulate_converging_camera_swept_device(const rm_params &p, const rm_lens &lens, const rm_converge &converge, const void *device_table,
+                                                   uint32_t table_rows, const void *device_camera_rows, const void *device_light_offsets,
+                                                   uint32_t n_lights, const void *device_shape_offsets, uint32_t n_shapes, const rm_swept *s,
+                                                   bool fresh, const rm_converge_frame &buffers, void *hip_stream) {
+        check(rm_accumulate_converging_camera_swept_device(ctx_, &p, &lens, &converge, device_table, table_rows, device_camera_rows,
+                                                           device_light_offsets, n_lights, device_shape_offsets, n_shapes, s, fresh ? 1 : 0,
+                                                           &buffers, hip_stream),
+              ctx_);
+    }
+    // rm_swept_tick_info: whether the last sampled-frame tick's launch walked a swept hierarchy, and how many the ticks have built
+    rm_swept_tick_report swept_tick_info() {
+        rm_swept_tick_report out{};
+        check(rm_swept_tick_info(ctx_, &out), ctx_);
+        return out;
+    }
     // The tick of the two calls above; any_shape: the second
     std::string tick_with_velocities(bool any_shape, framebuffer::FrameBuffer &frame, const scene::Scene &sc,
                                      const std::vector<Vec3f> &velocities, double shutter, uint32_t n_samples, const std::vector<double> &radii,

@@ -220,6 +220,16 @@ pub struct RmCameraBasis {
     pub forward: RmVec3,
 }
 
+/// `rm_swept_tick_report`: what the ticks that move a shape did (8 bytes).
+#[repr(C)]
+#[derive(Copy, Clone, Default)]
+pub struct RmSweptTickReport {
+    /// The last sampled-frame tick's launch walked a swept hierarchy: 1, else 0.
+    pub walked_swept: u32,
+    /// Hierarchies the ticks have built over the context's life.
+    pub builds: u32,
+}
+
 pub enum RmScene {}
 pub enum RmCtx {}
 pub enum RmSwept {}
@@ -342,6 +352,9 @@ extern "C" {
     fn rm_swept_free(ctx: *mut RmCtx, swept: *mut RmSwept);
     fn rm_accumulate_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_accumulate_converging_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_accumulate_camera_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_accumulate_converging_camera_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_swept_tick_info(ctx: *mut RmCtx, out: *mut RmSweptTickReport) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
@@ -1500,6 +1513,84 @@ impl Gpu {
             },
             self.ctx,
         );
+    }
+
+    /// `accumulate_camera` with a shape table through the swept hierarchy `swept` (a handle of `swept`, whose extents hold every row
+    /// of the shape table; the boxes are in world space, so no camera row matters): the same bytes, with the scene's hierarchies
+    /// walked.  A null `device_shape_offsets` is refused: nothing moves then, and `accumulate_camera` keeps the hierarchy.
+    pub fn accumulate_camera_swept(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_camera_rows: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        swept: *const RmSwept,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_camera_swept_device(self.ctx, &p, &lens, device_table, device_camera_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, swept, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// `accumulate_converging_camera` with a shape table through the swept hierarchy `swept`.
+    pub fn accumulate_converging_camera_swept(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_camera_rows: *const c_void,
+        device_light_offsets: *const c_void,
+        n_lights: u32,
+        device_shape_offsets: *const c_void,
+        n_shapes: u32,
+        swept: *const RmSwept,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_camera_swept_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_camera_rows, device_light_offsets, n_lights, device_shape_offsets, n_shapes, swept, if fresh { 1 } else { 0 }, &buffers, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// What the ticks that move a shape did: whether the last sampled-frame tick's launch walked a swept hierarchy, and how many
+    /// hierarchies the ticks have built over the context's life.  Host state only.
+    pub fn swept_tick_info(&mut self) -> RmSweptTickReport {
+        let mut out = RmSweptTickReport::default();
+        check(unsafe { rm_swept_tick_info(self.ctx, &mut out) }, self.ctx);
+        out
     }
 
     /// Bytes of device memory the list of `accumulate_converging` needs for a frame of that size.
