@@ -1537,6 +1537,99 @@ rm_status rm_accumulate_converging_camera_swept_device(rm_ctx *ctx, const rm_par
                                                        void *hip_stream);
 rm_status rm_swept_tick_info(rm_ctx *ctx, rm_swept_tick_report *out);
 
+/* ---- variance-guided filter: an edge-avoiding filter for converging frames ------------------------
+ * A converging frame is grainy for most of the ticks it takes to settle.  These calls are the
+ * reconstruction filter for it: the spatial filter of SVGF, an edge-avoiding a-trous wavelet filter
+ * steered by the per-pixel variance the converging frames keep anyway (sum, stats, count) and, where
+ * the caller has them, by the hits under the pixels (rm_primary_hits_device).  A settled pixel has a
+ * tiny variance and passes almost untouched, a noisy one borrows from neighbours on the same surface,
+ * nothing crosses a silhouette.  Additive to ABI version 5; a host detects them by " denoise" in
+ * rm_build_info().
+ *
+ * The rule.  Every operation is IEEE binary64, rounded once, no fused multiply-add, and only
+ * + - * / and comparisons occur, so a restatement in any language gives the same bytes.  Let
+ * rows = frame_height - frame_height % 32 and W = frame_width (W % 32 == 0).  Inputs over rows
+ * [0, rows), the plain layout: sum [H][W][3] and stats [H][W][2] (Y, Q) of doubles, count [H][W]
+ * of uint32_t -- the converging frames' three -- and optionally hits [H][W] of rm_hit.
+ *
+ *   Start.  nd = (double)n.  C0 = S / nd per channel when n > 0, else 0.  With
+ *           m2 = Q - (Y*Y)/nd, m2 < 0 replaced by 0: V0 = m2 / (nd * (nd - 1.)) when n >= 2, else
+ *           V0 = fallback_variance.  V is the variance of the mean of y = (r + g) + b.
+ *   Iteration i = 0 .. iterations - 1, step s = 1 << i, from C, V to C', V', for pixel p:
+ *           y(q) = (C[q].r + C[q].g) + C[q].b.
+ *           g: the 3x3 prefilter of V about p -- taps dy = -1..1 outer, dx = -1..1 inner, one pixel
+ *           apart whatever s, those in [0, W) x [0, rows) only, weights k(dx)*k(dy) with
+ *           k = {1/4, 1/2, 1/4}; g = (sum of weight*V[q]) / (sum of weights), both sums left folds
+ *           from +0.
+ *           den = (sigma_l*sigma_l)*g + epsilon.
+ *           The taps run dy = -2..2 outer, dx = -2..2 inner, q = p + s*(dx, dy).  A tap is skipped
+ *           when q is outside [0, W) x [0, rows), when count[q] == 0, or when the guide rejects it.
+ *           Otherwise w = ((h(dx)*h(dy)) * wl) * wn * wz, multiplied left to right, with
+ *           h = {1/16, 1/4, 3/8, 1/4, 1/16}; a = y(p) - y(q); wl = den / (den + a*a), or 1. when
+ *           count[p] == 0.
+ *           The guide, where hits is given (hit != 0 is a hit).  Both pixels missed: wn = wz = 1.
+ *           Exactly one missed: skipped.  Both hit and `shape` differs: skipped (`element` is not
+ *           compared: a mesh is one surface).  Otherwise, N, P, t being the hit's normal, point
+ *           and t: d = (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z, the tap is skipped unless d > 0,
+ *           and wn is d squared normal_squarings times (wn = wn*wn);
+ *           e = (N_p.x*(P_q.x-P_p.x) + N_p.y*(P_q.y-P_p.y)) + N_p.z*(P_q.z-P_p.z),
+ *           sz = sigma_z*(1. + t_p), dz = sz*sz, wz = dz / (dz + e*e).  Without hits
+ *           wn = wz = 1. and nothing is rejected.
+ *           Left folds from +0. in tap order: sw += w; sc[c] += w*C[q][c]; sv += (w*w)*V[q].
+ *           If sw > 0: C'[p] = sc / sw, V'[p] = sv / (sw*sw); else C'[p] = C[p], V'[p] = V[p].
+ *   End.    device_out gets C and device_variance, where given, V after `iterations` iterations
+ *           (0: C0, V0), and device_rgb8, where given, the display bytes of C by the progressive
+ *           frames' rule.  Rows from `rows` on are neither read nor written in any buffer.
+ *
+ * So with iterations == 0 the output is byte for byte the mean rm_accumulate_converging_device
+ * wrote for every pixel with n > 0; a pixel with count == 0 is a hole that takes no part as a tap
+ * and is filled from the neighbours the guide admits; and two regions with different shape ids never
+ * mix -- a picture that is exactly 1. on one shape and 0. on the other comes back exactly.
+ * Nothing read from count, hits or a pixel's value forms an address: NaN, infinity or a count from
+ * elsewhere give unspecified pixels, never a fault.
+ *
+ * rm_denoise_device is asynchronous on hip_stream, neither reads nor writes render state and keeps
+ * all of its state in the caller's buffers: one prepare launch and one launch an iteration.  The
+ * workspace has rm_denoise_workspace bytes, a function of params alone (frame_width % 32 != 0:
+ * RM_ERR_DIMENSIONS), and holds nothing a later call needs.  Checked before anything is launched,
+ * the offender named in rm_last_error, no buffer touched: of params what
+ * rm_accumulate_converging_device checks of its frame (flags, band, patch_size, an empty frame,
+ * frame_width % 32, fewer than 2^31 pixels) -- the filter looks at neither the resident scene nor
+ * max_depth or the background, and asks for none --; denoise not NULL and every field in the range
+ * its line states, a NaN refused; sum, stats, count, workspace and out not NULL; out none of sum,
+ * stats, count, hits.  rows == 0 is RM_OK and does nothing.
+ *
+ * rm_render_denoised is the viewer's tick: it filters the context's converging frame -- the
+ * buffers of whichever rm_render_converging* tick ran last -- into buffers of its own, copies the
+ * rows [0, rows) of the result and its bytes where asked, and blocks.  It changes nothing of the
+ * converging state: the next converging tick continues the same frame, byte for byte as if the
+ * filter had not run.  It is refused with RM_ERR_INVALID_ARG where no converging frame exists (no
+ * tick has succeeded, or the last one failed half-way) or its frame_width x frame_height are not
+ * params'.  With guides != 0 it first fills a hit buffer of the context's with
+ * rm_primary_hits_device's launch on the context's stream (a scene must be resident, as for that
+ * call).  THE GUIDE IS THE PINHOLE VIEW FROM THE CONTEXT'S CAMERA AS IT STANDS: under a wide
+ * aperture, under a moving camera and on strongly moving shapes the picture's edges are not where
+ * the guide's are, the filter blurs wrongly, and guides should be 0.  timing->kernel_ms covers the
+ * guide's and the filter's launches.
+ */
+typedef struct rm_denoise {
+    double   sigma_l;            /* luminance edge stop, in standard errors; finite, >= 0 */
+    double   sigma_z;            /* plane-distance edge stop, relative to 1 + t; finite, > 0 */
+    double   epsilon;            /* added to the luminance denominator; finite, > 0 */
+    double   fallback_variance;  /* variance of y for a pixel with n < 2; finite, >= 0 */
+    uint32_t iterations;         /* 0..5; iteration i has step 1 << i */
+    uint32_t normal_squarings;   /* 0..8: the normal weight is dot^(2^k) */
+} rm_denoise;                    /* 40 bytes */
+
+rm_status rm_denoise_workspace(const rm_params *params, size_t *bytes);
+rm_status rm_denoise_device(rm_ctx *ctx, const rm_params *params, const rm_denoise *denoise,
+                            const void *device_sum, const void *device_stats, const void *device_count,
+                            const void *device_hits /* optional */, void *device_workspace,
+                            void *device_out /* [H][W][3] doubles */, void *device_variance /* optional [H][W] */,
+                            void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_render_denoised(rm_ctx *ctx, const rm_params *params, const rm_denoise *denoise, int guides,
+                             double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

@@ -141,6 +141,13 @@ class rm_swept_tick_report(C.Structure):
     _fields_ = [("walked_swept", C.c_uint32), ("builds", C.c_uint32)]
 
 
+class rm_denoise(C.Structure):
+    """The variance-guided filter's control: luminance and plane-distance edge stops, the luminance denominator's epsilon, the
+    variance of a pixel with fewer than two samples, iterations (0..5) and squarings of the normals' dot product (0..8) (40 bytes)."""
+    _fields_ = [("sigma_l", C.c_double), ("sigma_z", C.c_double), ("epsilon", C.c_double), ("fallback_variance", C.c_double),
+                ("iterations", C.c_uint32), ("normal_squarings", C.c_uint32)]
+
+
 _P = C.POINTER
 _VP = C.c_void_p
 
@@ -283,6 +290,9 @@ SIGNATURES = {
     "rm_accumulate_converging_camera_swept_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, _VP,
                                                                C.c_uint32, _VP, C.c_uint32, _VP, C.c_int, _P(rm_converge_frame), _VP]),
     "rm_swept_tick_info": (C.c_int, [_VP, _P(rm_swept_tick_report)]),
+    "rm_denoise_workspace": (C.c_int, [_P(rm_params), _P(C.c_size_t)]),
+    "rm_denoise_device": (C.c_int, [_VP, _P(rm_params), _P(rm_denoise), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_render_denoised": (C.c_int, [_VP, _P(rm_params), _P(rm_denoise), C.c_int, _P(C.c_double), _P(C.c_uint8), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

@@ -230,6 +230,22 @@ def _converge(tolerance, min_samples, max_samples, n_samples, table_rows=PROGRES
     return _lib.rm_converge(tolerance, int(min_samples), int(max_samples))
 
 
+def _denoise(sigma_l, sigma_z, epsilon, fallback_variance, iterations, normal_squarings):
+    """rm_denoise of a filter call: sigma_l and fallback_variance finite and >= 0, sigma_z and epsilon finite and > 0, iterations
+    an integer in 0..5, normal_squarings one in 0..8."""
+    numbers = []
+    for name, v, positive in (("sigma_l", sigma_l, False), ("sigma_z", sigma_z, True), ("epsilon", epsilon, True),
+                              ("fallback_variance", fallback_variance, False)):
+        v = float(v)
+        if not np.isfinite(v) or not (v > 0. if positive else v >= 0.):
+            raise ValueError("%s must be a finite number %s 0, got %r" % (name, ">" if positive else ">=", v))
+        numbers.append(v)
+    for name, v, most in (("iterations", iterations, 5), ("normal_squarings", normal_squarings, 8)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v <= most:
+            raise ValueError("%s must be an integer in 0..%d, got %r" % (name, most, v))
+    return _lib.rm_denoise(*numbers, int(iterations), int(normal_squarings))
+
+
 def _converging_args(ctx, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples, max_samples, mean, rgb8, mask,
                      workspace):
     """What Context.accumulate_converging_device and accumulate_converging_motion_device check of their common arguments (ctx: the
@@ -1249,6 +1265,63 @@ class Context:
         rep = _lib.rm_swept_tick_report()
         _lib.check(self.L.rm_swept_tick_info(self.ptr, C.byref(rep)), self.ptr)
         return {"walked_swept": int(rep.walked_swept), "builds": int(rep.builds)}
+
+    # ---- variance-guided filter (include/rusty_marcher_amd.h, "variance-guided filter") ----
+    def denoise_workspace(self, params):
+        """rm_denoise_workspace: bytes of device memory denoise_device needs for `params`."""
+        b = C.c_size_t(0)
+        _lib.check(self.L.rm_denoise_workspace(C.byref(params), C.byref(b)), None)
+        return b.value
+
+    def denoise_device(self, params, sum, stats, count, out, sigma_l=4., sigma_z=.1, epsilon=1e-10, fallback_variance=1., iterations=5,
+                       normal_squarings=5, hits=None, variance=None, rgb8=None, workspace=None, stream=None):
+        """rm_denoise_device: the edge-avoiding filter of a converging frame -- sum (h, w, 3) and stats (h, w, 2), contiguous
+        float64 tensors, and count (h, w), an int32 one, on the context's device, as accumulate_converging_device leaves them --
+        into out (h, w, 3) float64 and, where given, variance (h, w) float64 and rgb8 (h, w, 3) uint8.  hits: optionally the
+        guide, what primary_hits_device returned for the same params (a DeviceHits, or its raw (h, w, 9) float64 tensor); without
+        it only the variance steers the filter.  The keyword defaults are starting values, not tuned ones.  Asynchronous on
+        `stream` (torch's current one by default).  -> the workspace, a uint8 tensor that holds nothing a later call needs."""
+        torch = _torch()
+        h, w = params.frame_height, params.frame_width
+        if isinstance(hits, DeviceHits):
+            hits = hits.raw
+        for name, t, dtype, shape in (("sum", sum, torch.float64, (h, w, 3)), ("stats", stats, torch.float64, (h, w, 2)),
+                                      ("count", count, torch.int32, (h, w)), ("out", out, torch.float64, (h, w, 3)),
+                                      ("hits", hits, torch.float64, (h, w, 9)), ("variance", variance, torch.float64, (h, w)),
+                                      ("rgb8", rgb8, torch.uint8, (h, w, 3))):
+            if t is None and name in ("hits", "variance", "rgb8"):
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, shape))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
+        for name, t in (("sum", sum), ("stats", stats), ("count", count), ("hits", hits)):
+            if t is not None and out.data_ptr() == t.data_ptr():
+                raise ValueError("out must not be %s's own tensor" % name)
+        ctl = _denoise(sigma_l, sigma_z, epsilon, fallback_variance, iterations, normal_squarings)
+        need = Context.denoise_workspace(self, params)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=sum.device)
+        elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.shape[0] < need \
+                or not workspace.is_contiguous() or workspace.device != sum.device or workspace.data_ptr() % 16 != 0:
+            raise ValueError("workspace must be a contiguous uint8 torch tensor of at least %d bytes on %s, aligned to 16" % (need, sum.device))
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self.L.rm_denoise_device(self.ptr, C.byref(params), C.byref(ctl), vp(sum), vp(stats), vp(count), vp(hits), vp(workspace),
+                                            vp(out), vp(variance), vp(rgb8), C.c_void_p(self._stream(stream))), self.ptr)
+        return workspace
+
+    def render_denoised(self, params, sigma_l=4., sigma_z=.1, epsilon=1e-10, fallback_variance=1., iterations=5, normal_squarings=5,
+                        guides=True, host_rgb=None, host_rgb8=None):
+        """rm_render_denoised: the filter over the converging frame the context keeps -- whichever render_converging* tick ran
+        last -- into buffers of its own; the converging frame is left as it is and its next tick continues it.  guides: steer
+        the filter by the hits under the pixels as well, seen through a pinhole from the context's camera as it stands; turn
+        them off under a wide aperture, a moving camera or strongly moving shapes, where the picture's edges are not the
+        guide's.  The keyword defaults are starting values, not tuned ones.  -> rm_timing."""
+        ctl = _denoise(sigma_l, sigma_z, epsilon, fallback_variance, iterations, normal_squarings)
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing = _lib.rm_timing()
+        _lib.check(self.L.rm_render_denoised(self.ptr, C.byref(params), C.byref(ctl), 1 if guides else 0, *host, C.byref(timing)), self.ptr)
+        return timing
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

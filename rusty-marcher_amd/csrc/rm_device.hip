@@ -40,6 +40,7 @@
 #include "rm_converge_swept.hpp"
 #include "rm_camera_swept.hpp"
 #include "rm_converge_camera_swept.hpp"
+#include "rm_denoise.hpp"
 
 using namespace rmdev;
 
@@ -134,6 +135,7 @@ struct rm_hostio;   // rm_hostio.inc: staging buffer, row-scatter threads, displ
 struct rm_progressive;   // rm_motion_host.inc: staged tables, sum, mean and bytes of rm_render_progressive*, its count and frame identity
 struct rm_tick_swept;    // rm_swept_host.inc: the swept hierarchy of the moving shapes' ticks, and what it was built from
 struct rm_converging;    // rm_converge_motion_host.inc: the buffers, resident sequences, pass total and frame identity of rm_render_converging*
+struct rm_denoising;     // rm_denoise_host.inc: the workspace, the guide and the outputs of rm_render_denoised
 
 // The classification's output for the render launches on one stream: a mask per tile.  (Launches on a
 // stream are ordered: a render launch reads what the classification launch in front of it wrote, and the
@@ -242,6 +244,9 @@ struct rm_ctx {
     // converging frames (rm_converge_motion_host.inc): made by the first rm_render_converging, rm_render_converging_motion or rm_render_converging_moving; shares nothing with `progressive`
     rm_converging *converging = nullptr;
 
+    // the variance-guided filter (rm_denoise_host.inc): made by the first rm_render_denoised; it reads `converging`, never writes it
+    rm_denoising *denoising = nullptr;
+
     // swept hierarchies (rm_swept_host.inc): the one the ticks that move a shape walk, built from their velocities and shutter
     rm_tick_swept *tick_swept = nullptr;
     uint32_t swept_walked = 0;               // the last sampled-frame tick's launch walked it (rm_swept_tick_info): set by the launches, cleared by the ticks
@@ -258,6 +263,7 @@ static void hostio_destroy(rm_ctx *ctx, bool device_ok);
 static bool hostio_packs(rm_ctx *ctx, size_t band_bytes);
 static void progressive_destroy(rm_ctx *ctx, bool device_ok);
 static void converging_destroy(rm_ctx *ctx, bool device_ok);
+static void denoising_destroy(rm_ctx *ctx, bool device_ok);
 static void tick_swept_destroy(rm_ctx *ctx, bool device_ok);
 
 static rm_status ctx_fail(rm_ctx *ctx, rm_status st, const std::string &msg) {
@@ -351,7 +357,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy swept-camera converge-moving converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy swept-camera denoise converge-moving converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -409,6 +415,7 @@ void rm_destroy(rm_ctx *ctx) {
     hostio_destroy(ctx, device_ok);
     progressive_destroy(ctx, device_ok);
     converging_destroy(ctx, device_ok);
+    denoising_destroy(ctx, device_ok);
     tick_swept_destroy(ctx, device_ok);
     if (device_ok) {
         for (rm_frame_slot &s : ctx->slots) {
@@ -1150,3 +1157,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_swept_host.inc"
 #include "rm_camera_host.inc"
 #include "rm_camera_swept_host.inc"
+#include "rm_denoise_host.inc"

@@ -584,6 +584,41 @@ struct Renderer {
             }
         return last_report;
     }
+    // The variance-guided filter (include/rusty_marcher_amd.h, "variance-guided filter").  rm_denoise_workspace: the bytes
+    // denoise_device's workspace needs for `p`
+    static size_t denoise_workspace(const rm_params &p) {
+        size_t bytes = 0;
+        check(rm_denoise_workspace(&p, &bytes), nullptr);
+        return bytes;
+    }
+    // rm_denoise_device for a host that keeps its own device buffers: the filter over a converging frame's sum, stats and count --
+    // and, where device_hits is not NULL, the hits of rm_primary_hits_device as the guide -- into device_out and, where given,
+    // device_variance and device_rgb8.  Asynchronous on hip_stream
+    void denoise_device(const rm_params &p, const rm_denoise &denoise, const void *device_sum, const void *device_stats, const void *device_count,
+                        const void *device_hits, void *device_workspace, void *device_out, void *device_variance, void *device_rgb8,
+                        void *hip_stream) {
+        check(rm_denoise_device(ctx_, &p, &denoise, device_sum, device_stats, device_count, device_hits, device_workspace, device_out,
+                                device_variance, device_rgb8, hip_stream),
+              ctx_);
+    }
+    // The converging frame the last render_converging* call built, filtered into `frame` (rm_render_denoised); the converging
+    // frame itself is left alone and its next tick continues it.  guides: steer the filter by the hits under the pixels as well --
+    // the pinhole view: off under a wide aperture, a moving camera or strongly moving shapes.  The defaults are starting values,
+    // not tuned ones
+    std::string render_denoised(framebuffer::FrameBuffer &frame, const scene::Scene &sc,
+                                const rm_denoise &denoise = rm_denoise{4., .1, 1e-10, 1., 5u, 5u}, bool guides = true) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_denoised(ctx_, &p, &denoise, guides ? 1 : 0, flat.data(), nullptr, &last_timing), ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
     // render_converging with moving spheres (rm_render_converging_motion): shape k of the scene, a sphere, moves by velocities[k] --
     // one vector a shape, zero for what is not a sphere -- while the shutter stands open for `shutter`, and every sample sees it at
     // a time of its own; only the pixels still noisy, the blurred band among them, go on being sampled.  The frame is

@@ -255,6 +255,26 @@ class Renderer:
             report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus)
         return report
 
+    def render_denoised(self, frame, scene, sigma_l=4., sigma_z=.1, iterations=5, normal_squarings=5, guides=True, epsilon=1e-10,
+                        fallback_variance=1.):
+        """The converging frame the last render_converging* call built, filtered (rm_render_denoised): an edge-avoiding a-trous
+        filter of `iterations` (0..5) steps 1, 2, 4, ... steered by each pixel's variance -- a settled pixel passes almost
+        untouched, a noisy one borrows from neighbours whose r + g + b lies within about sigma_l standard errors -- and, with
+        `guides`, by the hits under the pixels: nothing is borrowed across a silhouette, from a surface that faces another way
+        (the normals' dot product to the power 2^normal_squarings) or from off the pixel's tangent plane (sigma_z, relative to
+        1 + the hit's distance).  The guide is the pinhole view: turn it off under a wide aperture, a moving camera or strongly
+        moving shapes.  The frame must be the one that call rendered into (same size); the converging frame itself is left
+        alone and its next tick continues it.  The keyword defaults are starting values, not tuned ones.  Prints what render()
+        does and returns its message; the samples a pixel holds stay in self.last_samples."""
+        backend._denoise(sigma_l, sigma_z, epsilon, fallback_variance, iterations, normal_squarings)
+        samples = self.last_samples
+
+        def call(ctx, p):
+            return ctx.render_denoised(p, sigma_l, sigma_z, epsilon, fallback_variance, iterations, normal_squarings, guides,
+                                       host_rgb=frame.buffer), samples
+
+        return self._tick(frame, scene, call)
+
     def render_converging_motion(self, frame, scene, velocities, shutter, tolerance, n_samples, min_samples=16, max_samples=1024,
                                  light_radii=None, aperture=0., focus=1., restart=False):
         """render_converging with moving spheres (rm_render_converging_motion): shape k of the scene, a sphere, moves by

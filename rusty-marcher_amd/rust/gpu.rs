@@ -195,6 +195,27 @@ pub struct RmConvergeReport {
     pub _pad: u32,
 }
 
+/// `rm_denoise`: the variance-guided filter's control -- the luminance edge stop in standard errors, the plane-distance edge stop
+/// relative to 1 + t, the luminance denominator's epsilon, the variance of a pixel with fewer than two samples, the iterations
+/// (0..5, iteration i has step 1 << i) and how often the normals' dot product is squared (0..8) (40 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmDenoise {
+    pub sigma_l: f64,
+    pub sigma_z: f64,
+    pub epsilon: f64,
+    pub fallback_variance: f64,
+    pub iterations: u32,
+    pub normal_squarings: u32,
+}
+
+impl Default for RmDenoise {
+    /// Starting values, not tuned ones.
+    fn default() -> RmDenoise {
+        RmDenoise { sigma_l: 4., sigma_z: 0.1, epsilon: 1e-10, fallback_variance: 1., iterations: 5, normal_squarings: 5 }
+    }
+}
+
 /// `rm_camera_motion`: how the camera moves while the shutter stands open -- world units a unit of time, and yaw, pitch and roll
 /// in radians a unit of time about the axes and with the signs of `basis_turn` (48 bytes).
 #[repr(C)]
@@ -356,6 +377,9 @@ extern "C" {
     fn rm_accumulate_converging_camera_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_swept_tick_info(ctx: *mut RmCtx, out: *mut RmSweptTickReport) -> c_int;
     fn rm_abi_version() -> u32;
+    fn rm_denoise_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
+    fn rm_denoise_device(ctx: *mut RmCtx, params: *const RmParams, denoise: *const RmDenoise, device_sum: *const c_void, device_stats: *const c_void, device_count: *const c_void, device_hits: *const c_void, device_workspace: *mut c_void, device_out: *mut c_void, device_variance: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_denoised(ctx: *mut RmCtx, params: *const RmParams, denoise: *const RmDenoise, guides: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, timing: *mut RmTiming) -> c_int;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
     fn rm_kernel_name(ctx: *mut RmCtx, params: *const RmParams, buf: *mut c_char, buflen: usize) -> c_int;
@@ -1591,6 +1615,84 @@ impl Gpu {
         let mut out = RmSweptTickReport::default();
         check(unsafe { rm_swept_tick_info(self.ctx, &mut out) }, self.ctx);
         out
+    }
+
+    /// Bytes of device memory the workspace of `denoise_device` needs for a frame of that size.
+    pub fn denoise_workspace(fov: f64, height: f64, width: f64, frame_width: usize, frame_height: usize) -> usize {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let mut bytes: usize = 0;
+        check(unsafe { rm_denoise_workspace(&p, &mut bytes) }, ptr::null());
+        bytes
+    }
+
+    /// The variance-guided filter for a host that keeps its own device buffers: an edge-avoiding a-trous filter over a
+    /// converging frame's `device_sum`, `device_stats` and `device_count` -- and, where `device_hits` is not null, the hits of
+    /// `rm_primary_hits_device` as the guide -- into `device_out` and, where not null, `device_variance` and `device_rgb8`.
+    /// `device_workspace` holds `denoise_workspace` bytes.  Asynchronous on `hip_stream`.
+    pub fn denoise_device(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        denoise: RmDenoise,
+        device_sum: *const c_void,
+        device_stats: *const c_void,
+        device_count: *const c_void,
+        device_hits: *const c_void,
+        device_workspace: *mut c_void,
+        device_out: *mut c_void,
+        device_variance: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        check(
+            unsafe {
+                rm_denoise_device(self.ctx, &p, &denoise, device_sum, device_stats, device_count, device_hits, device_workspace, device_out, device_variance, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// The converging frame the last `render_converging*` call built, filtered into `frame`; the converging frame itself is left
+    /// alone and its next tick continues it.  `guides`: steer the filter by the hits under the pixels as well -- the pinhole
+    /// view: off under a wide aperture, a moving camera or strongly moving shapes.  `RmDenoise::default()` holds starting
+    /// values, not tuned ones.
+    pub fn render_denoised(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        denoise: RmDenoise,
+        guides: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> String {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let mut timing = RmTiming::default();
+        check(unsafe { rm_render_denoised(self.ctx, &p, &denoise, if guides { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut timing) }, self.ctx);
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        Gpu::status(now, frame.width, frame.height)
     }
 
     /// Bytes of device memory the list of `accumulate_converging` needs for a frame of that size.
