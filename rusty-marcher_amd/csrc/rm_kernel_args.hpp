@@ -180,11 +180,15 @@ struct KernelArgs {
     // is rendered by the exact twin (a scene or a camera outside what the range-free sequences are proven for, or
     // RM_CHECKED_NUMERICS=0); redo_count -- the context's count of tiles rendered again because a lane's guard fired.
     uint32_t exact_only;
-    // != 0 (plain-walk kernels only): a child ray that leaves a polygon / triangle into a half-space its glass word says is
-    // empty (rm_internal.h, rm_build_empty_sides) is not walked -- the lane adds weight x background at once (render_tile)
+    // Plain-walk kernels only.  RM_DEAD_DROP: a child ray that leaves a polygon / triangle into a half-space its glass word
+    // says is empty (rm_internal.h, rm_build_empty_sides) is not walked -- the lane adds weight x background at once
+    // (render_tile).  RM_DEAD_EARLY_FATES: a refracted child beyond the depth cap, or one that leaves into such a half-space
+    // for certain, is decided before its ray is formed.
     uint32_t dead_children;
     uint32_t *redo_count;
 };
+
+static constexpr uint32_t RM_DEAD_DROP = 1u, RM_DEAD_EARLY_FATES = 2u;
 
 // What the classification launch gets besides the render launch's own arguments.
 struct ClassifyArgs {

@@ -30,6 +30,7 @@ enum knob_rule {
     TAIL_PLACE,    // int: "ev..." 1 | "e..." 2 | anything else 0
     CULL_OFF,      // double: text[0] == '1' sets 2 (no bundle is ever narrow enough)
     CULL_COS,      // double: max(0.05, atof)   (the cone tests hold for half-angles below 90 degrees)
+    DEAD_CHILDREN, // bool: text[0] != '0'; and early_fates: text[0] is neither '0' nor '1'
 };
 
 struct knob {
@@ -51,7 +52,7 @@ const knob k_knobs[] = {
     {"RM_FORCE_FAST_FP", &rm_knobs::force_fast_fp, IS_1},
     {"RM_FORCE_UNSTAGED", &rm_knobs::force_unstaged, IS_1},
     {"RM_SHADOW_MASKS", &rm_knobs::shadow_masks, NOT_0},
-    {"RM_DEAD_CHILDREN", &rm_knobs::dead_children, NOT_0},
+    {"RM_DEAD_CHILDREN", &rm_knobs::dead_children, DEAD_CHILDREN},
     {"RM_DISABLE_BVH", &rm_knobs::disable_bvh, IS_1},
     {"RM_SWEPT_BVH", &rm_knobs::swept_bvh, NOT_0},
     {"RM_FORCE_STACK", &rm_knobs::force_stack, ATOI},
@@ -122,6 +123,7 @@ rm_knobs rm_knobs_from_env() {
         case TAIL_PLACE: kn.*k.i = env[0] == 'e' && env[1] == 'v' ? 1 : env[0] == 'e' ? 2 : 0; break;
         case CULL_OFF: kn.*k.d = env[0] == '1' ? 2. : kn.*k.d; break;
         case CULL_COS: kn.*k.d = std::max(0.05, std::atof(env)); break;
+        case DEAD_CHILDREN: kn.*k.b = env[0] != '0'; kn.early_fates = env[0] != '0' && env[0] != '1'; break;
         }
     }
     if (kn.classify_min_tiles == 0u) kn.classify_min_tiles = RM_CLASSIFY_MIN_TILES_DEFAULT;
@@ -288,8 +290,10 @@ bool plan_launch(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p
     // children that leave a planar primitive into an empty half-space are not walked (render_tile): the plain-walk kernels
     // only, and -- like the occluder masks -- only while the camera is near enough for its hit points to round far below
     // the offset such a child starts with
-    a.dead_children = (kn.dead_children && !k.bvh && !k.cull && sc.dead_camera_limit > 0. &&
-                       std::fabs(sc.camera.x) + std::fabs(sc.camera.y) + std::fabs(sc.camera.z) <= sc.dead_camera_limit) ? 1u : 0u;
+    // (... and, a bit of the same word, whether a refracted child's fate is decided before its ray is formed: the knob's alone)
+    a.dead_children = ((kn.dead_children && !k.bvh && !k.cull && sc.dead_camera_limit > 0. &&
+                        std::fabs(sc.camera.x) + std::fabs(sc.camera.y) + std::fabs(sc.camera.z) <= sc.dead_camera_limit) ? RM_DEAD_DROP : 0u) |
+                      ((kn.early_fates && !k.bvh && !k.cull) ? RM_DEAD_EARLY_FATES : 0u);
     // A cull step handles 64 primitives for ~25 vector instructions, ~110 when it holds planar
     // primitives and the edge test runs; a bundle pays for every step.  The hierarchy walk finds a
     // bundle's few primitives in a few hundred instructions whatever their number, so scenes whose
@@ -669,7 +673,7 @@ extern "C" rm_status rmi_plan_dead_children(const rm_vec3 *camera, double dead_c
         rm_set_host_error("rmi_plan_dead_children: no plan");
         return RM_ERR_INVALID_ARG;
     }
-    out[0] = P.args.dead_children;
+    out[0] = P.args.dead_children & RM_DEAD_DROP;
     out[1] = (!P.k.bvh && !P.k.cull) ? 1u : 0u;
     return RM_OK;
 }

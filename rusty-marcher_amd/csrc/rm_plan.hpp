@@ -53,6 +53,9 @@ struct rm_knobs {
     // Children of a glass-like polygon / triangle that leave it into an empty half-space (rm_build_empty_sides) are not
     // walked by the plain-walk kernels: RM_DEAD_CHILDREN=0 walks them all the same (the A/B switch; frames are bit-equal)
     bool dead_children = true;
+    // ... and a refracted child's fate -- beyond the depth cap, or into a flagged side for certain -- is decided before its ray
+    // is formed (render_tile).  RM_DEAD_CHILDREN=0 and =1 form every ray and decide on its computed dot, as before
+    bool early_fates = true;
     int force_stack = 0;              // RM_FORCE_STACK=4|8|16|32: a deeper ray stack than the depth cap needs
     bool debug_empty = false;         // RM_DEBUG_EMPTY=1: measure the dispatch floor of a launch geometry
     // frame-to-frame feedback (rm_feedback): RM_FEEDBACK=0 never, 1 always, unset: launches of

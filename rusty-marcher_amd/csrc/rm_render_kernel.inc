@@ -104,7 +104,9 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
     // Children that leave a glass-like polygon / triangle into an empty half-space (rm_image.cpp rm_build_empty_sides; the
     // launch plan says whether the image's flags hold for this camera) are not walked: per-lane kernels only -- the others
     // form one fused term per step, and the sum would round differently.
-    const bool dead_children = DIV && own_sgpr(a.dead_children) != 0u;   // wave-uniform
+    // (one word, two bits -- RM_DEAD_DROP, RM_DEAD_EARLY_FATES: no second argument is live through the tile)
+    const uint32_t dead_word = DIV ? own_sgpr(a.dead_children) : 0u;     // wave-uniform
+    const bool dead_children = (dead_word & RM_DEAD_DROP) != 0u, early_fates = (dead_word & RM_DEAD_EARLY_FATES) != 0u;
     uint32_t step = 0;
     for (;; step++) {                                          // one ray step; the loop itself is wave-uniform
         // Critical-path scheduling: a launch ends with its deepest tiles (8 steps where the mean
@@ -144,10 +146,34 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
                     V3 ro, rd, to, td;
                     double dn_r, dn_t;                          // rd . normal, td . normal: the dots the children's origins were offset by
                     const bool has_r = glass & reflect_child<DIV>(dir, s, ri, inv_ri, ro, rd, dn_r);   // renderer.rs:195-222
-                    const bool has_t = glass & refract_child(dir, s, ri, inv_ri, glass, to, td, dn_t RM_SUS_ARG);   // renderer.rs:225-252
+                    bool has_t = false, fated_dead = false;     // renderer.rs:225-252
+                    if (!DIV) has_t = glass & refract_child(dir, s, ri, inv_ri, glass, to, td, dn_t RM_SUS_ARG);
                     const double wr = weight * reflection, wt = weight * (1. - reflection);
                     // a child beyond the cap returns the background (renderer.rs:262-264)
                     const bool capped = depth + 1u > max_depth;
+                    if (DIV) {
+                        // Early child fates: the refracted ray is formed only where it is walked or its computed dot decides.
+                        // Not beyond the cap (only `has_t` counts there); not where it leaves into a flagged side for certain --
+                        // d . normal is -+sqrt(cos_theta_2): with the flip it points to the normal's side, else to the other one,
+                        // and away from the critical angle the computed dot has that sign (DESIGN.md section 4).
+                        const RefractFate f = refract_fate(dir, s, ri, inv_ri);
+                        has_t = glass & f.has;
+                        bool ray = glass;
+                        if (early_fates) {
+                            const uint32_t sides = (uint32_t)s.mat[8];
+                            fated_dead = dead_children & has_t & !capped & (f.cos_theta_2 >= RM_FATE_COS2_MIN) & (f.r <= RM_FATE_R_MAX) &
+                                         ((sides & (f.flip ? 2u : 4u)) != 0u);
+                            ray = has_t & !capped & !fated_dead;
+                        }
+                        // (the ray goes where the lane's ray lives: `to` and `td` beside `orig` and `dir`, through the parking
+                        // below, were ten vector registers spilt in the ray-step loop)
+                        dn_t = 0.;
+                        if (ray) {
+                            refract_ray(dir, s, f, glass, to, td, dn_t RM_SUS_ARG);
+                            orig = to;
+                            dir = td;
+                        }
+                    }
                     w_cap = ((capped & has_r) ? wr : 0.) + ((capped & has_t) ? wt : 0.);
                     if (DIV && capped) acc = acc + scaled(bg, w_cap);
                     bool live_r = has_r & !capped, live_t = has_t & !capped;
@@ -159,7 +185,8 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
                         // ray is dropped.  d . normal == 0 leaves it alive.  The order of the pixel's terms stays what it was:
                         // the refracted child is walked first, and the reflected one is dropped only where it would be next.
                         const uint32_t sides = (uint32_t)s.mat[8];
-                        const bool dead_t = live_t & (((dn_t > 0.) & ((sides & 2u) != 0u)) | ((dn_t < 0.) & ((sides & 4u) != 0u)));
+                        // (a child whose fate was decided early has no ray and dn_t == 0: the two never overlap)
+                        const bool dead_t = fated_dead | (live_t & (((dn_t > 0.) & ((sides & 2u) != 0u)) | ((dn_t < 0.) & ((sides & 4u) != 0u))));
                         if (dead_t) acc = acc + scaled(bg, wt);
                         live_t = live_t & !dead_t;
                         if (live_r & !live_t) {
@@ -187,8 +214,8 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
                     // walk into the refracted child, else the reflected one (lanes whose ray ends
                     // here get values nobody reads: they take a parked ray or fall idle below)
                     next = live_r | live_t;
-                    orig = pick(live_t, to, ro);
-                    dir = pick(live_t, td, rd);
+                    orig = pick(live_t, DIV ? orig : to, ro);
+                    dir = pick(live_t, DIV ? dir : td, rd);
                     weight = live_t ? wt : wr;
                     depth += 1u;
                 }

@@ -1397,6 +1397,43 @@ __device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, dou
     o = s.point + scaled(s.normal, (along != flip) ? 1e-4 : -1e-4);   // :82-86: point +- flipped normal * 1e-4
     return !(cos_theta_2 < 0.);                                       // :74
 }
+// The same in two halves, for render_tile's per-lane kernels (the others, the query and the shading units keep the whole above,
+// and compile as before).  The FATE -- does the ray exist, and through which side of the surface does it leave -- is known after a
+// dozen instructions; the RAY costs a root, a normalisation, two dots and the offset origin.  One behind the other they are
+// refract_child's operations in refract_child's order; the per-lane kernels form the ray only where it is walked or its
+// computed dot is needed (DESIGN.md section 4, "early child fates").
+// `has`: the ray exists (:74); `flip`: the incident ray runs along the normal (:60-68: then c = -c, normal = -normal) -- the
+// refracted ray leaves into the side the un-flipped normal points to, else into the other one.
+struct RefractFate { double r, c, cos_theta_2; bool flip, has; };
+// From this cos_theta_2 on, with r no larger than this, the sign of the computed d . normal is the predicted one (DESIGN.md
+// section 4: before the normalisation the dot is -+sqrt(cos_theta_2) to within 3.6e-5 for a normal that is unit to 1e-6, what a
+// flagged primitive's is; tests/test_refract_fate.py).
+#define RM_FATE_COS2_MIN 0x1p-16
+#define RM_FATE_R_MAX 16.
+__device__ __forceinline__ RefractFate refract_fate(V3 incident, const Surface &s, double ri, double inv_ri) {
+    RefractFate f;
+    const double c0 = -dot(s.normal, incident);                       // optics.rs:57
+    f.flip = c0 < 0.;                                                 // :60-68
+    f.r = f.flip ? ri : inv_ri;
+    f.c = f.flip ? -c0 : c0;
+    f.cos_theta_2 = 1. - f.r * f.r * (1. - f.c * f.c);
+    f.has = !(f.cos_theta_2 < 0.);                                    // :74
+    return f;
+}
+__device__ __forceinline__ void refract_ray(V3 incident, const Surface &s, const RefractFate &f, bool glass, V3 &o, V3 &d, double &dn RM_SUS_PARAM) {
+    (void)glass;
+    // (RM_CHECKED: the root without its scaling, as the discriminants' -- a cos_theta_2 that is not zero is 2^-53 at least)
+#ifdef RM_AB_FATE_SCALED_ROOT   // (A/B build: the early fates with the compiler's own root)
+    const double k = f.r * f.c - __builtin_sqrt(f.cos_theta_2);
+#else
+    const double k = f.r * f.c - RM_SQRT_DISCRIMINANT(f.cos_theta_2);
+#endif
+    // (under total reflection k is NaN and there is no such ray: its lanes' flags do not count)
+    d = RM_NORMALIZED(scaled(incident, f.r) + scaled(s.normal, f.flip ? -k : k), glass & f.has);   // :78-79 (flipped normal * k)
+    dn = dot(d, s.normal);                                            // d . flipped normal = -(d . normal) when flipped
+    const bool along = f.flip ? (dn < 0.) : (dn > 0.);                // :82 `dir.dot(normal) > 0` with the flipped normal
+    o = s.point + scaled(s.normal, (along != f.flip) ? 1e-4 : -1e-4); // :82-86: point +- flipped normal * 1e-4
+}
 __device__ __forceinline__ bool refract_child(V3 incident, const Surface &s, double ri, double inv_ri, bool glass, V3 &o, V3 &d RM_SUS_PARAM) {
     double dn;
     return refract_child(incident, s, ri, inv_ri, glass, o, d, dn RM_SUS_ARG);
