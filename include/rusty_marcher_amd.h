@@ -1630,6 +1630,123 @@ rm_status rm_denoise_device(rm_ctx *ctx, const rm_params *params, const rm_denoi
 rm_status rm_render_denoised(rm_ctx *ctx, const rm_params *params, const rm_denoise *denoise, int guides,
                              double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */, rm_timing *timing /* optional */);
 
+/* ---- temporal reprojection: converging frames carried across camera moves --------------------------
+ * A converging frame is keyed on the camera's position and basis, so a camera move begins it again
+ * and throws away every sample the device held.  These calls are the other half of SVGF: the sums a
+ * frame held for one view are carried to another view of the same scene.  Every pixel of the new
+ * view finds the point under it in the previous view's picture, takes the samples around that
+ * position that lie on the same surface, and begins with their mean and the smallest of their
+ * counts.  Additive to ABI version 5; a host detects them by " reproject" in rm_build_info().
+ *
+ * The rule.  Every operation is IEEE binary64, rounded once, in the written order, no fused
+ * multiply-add.  Let rows = frame_height - frame_height % 32 and W = frame_width (W % 32 == 0).
+ * Buffers are rm_converge_frame's (sum [H][W][3], stats [H][W][2], count [H][W]) and
+ * rm_primary_hits_device's ([H][W] rm_hit): prev_* are the previous view's frame and its hits,
+ * cur_hits the hits of the view the new frame will be sampled from, previous_view the previous
+ * camera as rm_camera_get reported it.  For pixel p = (x, y), y < rows:
+ *
+ *   a. cur_hits[p].hit == 0: the pixel carries nothing (sky costs nothing to sample again).
+ *   b. With P, N, t the current hit's point, normal and t, and E, R, U, F the previous view's
+ *      position, right, up and forward: v = P - E; zf = (v.x*F.x + v.y*F.y) + v.z*F.z, and xr, yu
+ *      likewise with R and U.  The pixel carries nothing unless zf > 0.
+ *   c. The sample position, the inverse of the sample-ray formula of the radiance section:
+ *          sx = (((xr / zf) / ratio) / half_fov / 2. + 0.5) * width
+ *          sy = (((yu / zf) / half_fov) / -2. + 0.5) * height
+ *   d. The range check, in doubles, before any conversion to an integer: the pixel carries nothing
+ *      unless sx > -1. && sx < W && sy > -1. && sy < rows (a NaN fails every comparison).  Then
+ *      x0 = floor(sx), fx = sx - x0, y0 = floor(sy), fy = sy - y0.
+ *   e. The four bilinear taps run j = 0..1 outer, i = 0..1 inner: q = (x0 + i, y0 + j),
+ *      wb = (i ? fx : 1. - fx) * (j ? fy : 1. - fy).  A tap is skipped when wb > 0 is false; when q
+ *      is outside [0, W) x [0, rows); when prev_count[q] == 0; when prev_hits[q].hit == 0; when
+ *      prev_hits[q].shape != cur_hits[p].shape (`element` is not compared, as in the filter); when
+ *      d = (N.x*Nq.x + N.y*Nq.y) + N.z*Nq.z is not > min_normal_dot; or when e*e <= dz is false,
+ *      with e = (N.x*(Pq.x-P.x) + N.y*(Pq.y-P.y)) + N.z*(Pq.z-P.z), sz = sigma_z*(1. + t),
+ *      dz = sz*sz.
+ *   f. Left folds from +0. in tap order, nq = (double)prev_count[q]: sw += wb;
+ *      sc[c] += wb * (prev_sum[q][c] / nq); s1 += wb * (prev_stats[q][0] / nq);
+ *      s2 += wb * (prev_stats[q][1] / nq); nmin = min(nmin, prev_count[q]).
+ *   g. If sw > 0: n' = min(nmin, max_history), nd = (double)n', out_sum[p][c] = (sc[c] / sw) * nd,
+ *      out_stats[p][k] = (s_k / sw) * nd, out_count[p] = n', carried = 1.  Otherwise sum and stats
+ *      are +0., the count is 0 and carried = 0.  out_carried_total, where given, is zeroed by the
+ *      call on the stream and then receives the number of carried pixels, one atomic add a wave.
+ *   Rows from `rows` on are neither read nor written in any buffer.
+ *
+ * So: only + - * /, floor, comparisons and integer-to-double conversions occur, and a restatement
+ * in any language gives the same bytes.  A previous picture that is exactly n * 1. on one shape and
+ * n * 0. on another comes back exactly n' * 1. and n' * 0.: sc and sw are the same fold, so
+ * nothing crosses a silhouette.  A point that was hidden, outside the previous frustum or behind
+ * the previous camera carries nothing.  The carried second moment minus the square of the carried
+ * first is never negative beyond rounding, because both are convex combinations, so the standard
+ * error the converging rule forms of them stays meaningful.  Data DOES form addresses here -- that
+ * is the nature of a gather along motion, and unlike the filter -- but no address is formed before
+ * the range check in doubles: NaN, infinity or a hit buffer from elsewhere give pixels without
+ * history or unspecified values, never a fault.
+ *
+ * rm_reproject_device is asynchronous on hip_stream, reads no render state and keeps no state of
+ * its own.  Checked before anything is launched, the offender named in rm_last_error, no buffer
+ * touched: of params what rm_denoise_device checks; reproject and previous_view not NULL and every
+ * field in the range its line states, a NaN refused; a finite position and a basis
+ * rm_camera_basis_check accepts; the five inputs and out_sum, out_stats, out_count not NULL; no
+ * out_* equal to any input.  rows == 0 is RM_OK and does nothing.
+ *
+ * History in the tick.  History is a state of the context, off after rm_init;
+ * rm_converge_history(ctx, settings) turns it on (or changes its settings), NULL turns it off.
+ * While it is off every tick is byte for byte what it was: no allocation, no launch.  While it is
+ * on, rm_render_converging -- the static scene, with or without radii, and no other tick -- keeps a
+ * hit buffer for the frame's view, filled with rm_primary_hits_device's launch on the context's
+ * stream when a frame begins, or by the first tick that finds the continuing frame without one.
+ * Where the tick finds a frame other than the kept one, it reprojects rather than begins again
+ * when the identity differs ONLY in the camera's position, its basis and whether it is oriented,
+ * restart was not asked, the kept frame has run at least one pass and has a hit buffer.  It then
+ * fills a second hit buffer for the new view, runs rm_reproject_device's launch from the kept
+ * buffers and the kept view into a second set of sum, stats and count (and writes the mean
+ * out_sum / n' and its bytes for every pixel, which the pass overwrites where it samples), swaps the
+ * two sets and the two hit buffers, sets N = min(N, max_history), begins passes, listed and
+ * samples_cast of the report at 0 -- so a "finished" frame is never assumed -- and runs the pass
+ * with fresh = 0: a pixel with carried count n' casts rows n' .. n' + n_samples - 1, as any pixel
+ * with that count does.  Every other cause begins the frame again as before: the scene, params,
+ * the lens, the radii, another tick of the family.  rm_render_converging_motion, _moving and
+ * _camera keep beginning again: their history would need motion vectors, which are not built.  A
+ * refused call changes nothing of the state; a failure half-way leaves no frame, as before.  The
+ * doubled buffers exist only while history is on: rm_destroy releases them, and so does turning
+ * history off.  timing->kernel_ms covers the hit launch, the reprojection and the pass.
+ *
+ * WHAT HISTORY COSTS.  "A pixel with c samples holds what the plain frame holds after c" holds for
+ * frames that were never reprojected; A REPROJECTED FRAME TRADES THAT PROMISE FOR HISTORY: its sums
+ * are interpolated, not folded.  The guide is the pinhole view: under a wide aperture the carried
+ * history is blurred across what the guide calls one surface, as the filter's section warns.
+ * View-dependent light (mirror, glass) is carried as if it were stuck to the surface; max_history
+ * bounds how long that error lives and should stay well under max_samples.  The bindings' default
+ * of 32 is a starting value, not a tuned one.
+ *
+ * rm_converge_history_info tells a reprojected tick from one that quietly began again.
+ */
+typedef struct rm_view { rm_vec3 position; rm_camera_basis basis; } rm_view;   /* 96 bytes: a camera as rm_camera_get reports it */
+typedef struct rm_reproject {
+    double   sigma_z;          /* plane-distance gate, relative to 1 + t; finite, > 0 */
+    double   min_normal_dot;   /* a tap is admitted only when N_p.N_q > this; finite, in [-1, 1) */
+    uint32_t max_history;      /* no carried count exceeds it; 1..RM_PROGRESSIVE_MAX_SAMPLES */
+    uint32_t _pad;
+} rm_reproject;                /* 24 bytes */
+typedef struct rm_history_report {
+    uint64_t reprojections;    /* frames the ticks have begun from history since rm_init */
+    uint32_t last_reprojected; /* 1: the last rm_render_converging tick began its frame from history */
+    uint32_t carried;          /* pixels that carried history at the last reprojection */
+    uint32_t without;          /* pixels of [0, rows) that did not */
+    uint32_t _pad;
+} rm_history_report;           /* 24 bytes */
+
+rm_status rm_reproject_device(rm_ctx *ctx, const rm_params *params, const rm_reproject *reproject,
+                              const rm_view *previous_view,
+                              const void *prev_sum, const void *prev_stats, const void *prev_count, const void *prev_hits,
+                              const void *cur_hits,
+                              void *out_sum, void *out_stats, void *out_count,
+                              void *out_carried /* optional: [H][W] bytes, 1 where history was carried */,
+                              void *out_carried_total /* optional: one uint32_t on the device */,
+                              void *hip_stream);
+rm_status rm_converge_history(rm_ctx *ctx, const rm_reproject *reproject /* NULL: off */);
+rm_status rm_converge_history_info(rm_ctx *ctx, rm_history_report *report);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

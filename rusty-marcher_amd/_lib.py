@@ -148,6 +148,24 @@ class rm_denoise(C.Structure):
                 ("iterations", C.c_uint32), ("normal_squarings", C.c_uint32)]
 
 
+class rm_view(C.Structure):
+    """A camera as rm_camera_get reports it: position and basis (96 bytes)."""
+    _fields_ = [("position", rm_vec3), ("basis", rm_camera_basis)]
+
+
+class rm_reproject(C.Structure):
+    """The temporal reprojection's control: the plane-distance gate, the least dot product of the normals a tap is admitted with,
+    and the most samples a pixel may carry (24 bytes)."""
+    _fields_ = [("sigma_z", C.c_double), ("min_normal_dot", C.c_double), ("max_history", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class rm_history_report(C.Structure):
+    """What the converging tick did with its history: frames begun from history, whether the last tick was one, and the pixels
+    that carried history at the last reprojection and those that did not (24 bytes)."""
+    _fields_ = [("reprojections", C.c_uint64), ("last_reprojected", C.c_uint32), ("carried", C.c_uint32), ("without", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 _P = C.POINTER
 _VP = C.c_void_p
 
@@ -293,6 +311,9 @@ SIGNATURES = {
     "rm_denoise_workspace": (C.c_int, [_P(rm_params), _P(C.c_size_t)]),
     "rm_denoise_device": (C.c_int, [_VP, _P(rm_params), _P(rm_denoise), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_render_denoised": (C.c_int, [_VP, _P(rm_params), _P(rm_denoise), C.c_int, _P(C.c_double), _P(C.c_uint8), _P(rm_timing)]),
+    "rm_reproject_device": (C.c_int, [_VP, _P(rm_params), _P(rm_reproject), _P(rm_view), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_converge_history": (C.c_int, [_VP, _P(rm_reproject)]),
+    "rm_converge_history_info": (C.c_int, [_VP, _P(rm_history_report)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

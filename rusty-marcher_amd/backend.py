@@ -246,6 +246,29 @@ def _denoise(sigma_l, sigma_z, epsilon, fallback_variance, iterations, normal_sq
     return _lib.rm_denoise(*numbers, int(iterations), int(normal_squarings))
 
 
+def _reproject(sigma_z, min_normal_dot, max_history):
+    """rm_reproject of a reprojection: sigma_z finite and > 0, min_normal_dot in [-1, 1), max_history an integer in
+    1..PROGRESSIVE_MAX_SAMPLES."""
+    sigma_z, min_normal_dot = float(sigma_z), float(min_normal_dot)
+    if not np.isfinite(sigma_z) or not sigma_z > 0.:
+        raise ValueError("sigma_z must be a finite number > 0, got %r" % sigma_z)
+    if not -1. <= min_normal_dot < 1.:
+        raise ValueError("min_normal_dot must lie in [-1, 1), got %r" % min_normal_dot)
+    if isinstance(max_history, bool) or int(max_history) != max_history or not 1 <= max_history <= PROGRESSIVE_MAX_SAMPLES:
+        raise ValueError("max_history must be an integer in 1..%d, got %r" % (PROGRESSIVE_MAX_SAMPLES, max_history))
+    return _lib.rm_reproject(sigma_z, min_normal_dot, int(max_history), 0)
+
+
+def _view(view):
+    """rm_view of a camera: an rm_view, or (position, basis[, oriented]) as Context.camera() returns it."""
+    if isinstance(view, _lib.rm_view):
+        return view
+    position, basis = view[0], view[1]
+    position = position if isinstance(position, _lib.rm_vec3) else _lib.vec3(position)
+    basis = basis if isinstance(basis, _lib.rm_camera_basis) else _lib.camera_basis(basis)
+    return _lib.rm_view(position, basis)
+
+
 def _converging_args(ctx, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples, max_samples, mean, rgb8, mask,
                      workspace):
     """What Context.accumulate_converging_device and accumulate_converging_motion_device check of their common arguments (ctx: the
@@ -1322,6 +1345,66 @@ class Context:
         timing = _lib.rm_timing()
         _lib.check(self.L.rm_render_denoised(self.ptr, C.byref(params), C.byref(ctl), 1 if guides else 0, *host, C.byref(timing)), self.ptr)
         return timing
+
+    # ---- temporal reprojection (include/rusty_marcher_amd.h, "temporal reprojection") ----
+    def reproject_device(self, params, prev_total, prev_stats, prev_count, prev_hits, cur_hits, previous_view, out_total, out_stats, out_count,
+                         sigma_z=.1, min_normal_dot=.9, max_history=32, carried=None, carried_total=None, stream=None):
+        """rm_reproject_device: carries a converging frame -- prev_total (h, w, 3) and prev_stats (h, w, 2) float64, prev_count
+        (h, w) int32, as accumulate_converging_device leaves them, and prev_hits, what primary_hits_device returned for the view
+        they were sampled from (a DeviceHits or its raw (h, w, 9) tensor) -- to the view cur_hits was made for, into out_total,
+        out_stats and out_count of the same shapes.  previous_view: the previous camera, an rm_view or what Context.camera()
+        returned then.  carried: optionally (h, w) uint8, 1 where history was carried; carried_total: optionally one int32 on the
+        device, their number.  The keyword defaults are starting values, not tuned ones.  Asynchronous on `stream` (torch's
+        current one by default)."""
+        torch = _torch()
+        h, w = params.frame_height, params.frame_width
+        prev_hits = prev_hits.raw if isinstance(prev_hits, DeviceHits) else prev_hits
+        cur_hits = cur_hits.raw if isinstance(cur_hits, DeviceHits) else cur_hits
+        inputs = (("prev_total", prev_total, torch.float64, (h, w, 3)), ("prev_stats", prev_stats, torch.float64, (h, w, 2)),
+                  ("prev_count", prev_count, torch.int32, (h, w)), ("prev_hits", prev_hits, torch.float64, (h, w, 9)),
+                  ("cur_hits", cur_hits, torch.float64, (h, w, 9)))
+        outputs = (("out_total", out_total, torch.float64, (h, w, 3)), ("out_stats", out_stats, torch.float64, (h, w, 2)),
+                   ("out_count", out_count, torch.int32, (h, w)), ("carried", carried, torch.uint8, (h, w)),
+                   ("carried_total", carried_total, torch.int32, (1,)))
+        for name, t, dtype, shape in inputs + outputs:
+            if t is None and name in ("carried", "carried_total"):
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s torch tensor of shape %s" % (name, dtype, shape))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (the context's device), not %s" % (name, self.device, t.device))
+        for oname, o, _, _ in outputs:
+            for iname, i, _, _ in inputs:
+                if o is not None and o.data_ptr() == i.data_ptr():
+                    raise ValueError("%s must not be %s's own tensor" % (oname, iname))
+        ctl = _reproject(sigma_z, min_normal_dot, max_history)
+        view = _view(previous_view)
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self.L.rm_reproject_device(self.ptr, C.byref(params), C.byref(ctl), C.byref(view), vp(prev_total), vp(prev_stats),
+                                              vp(prev_count), vp(prev_hits), vp(cur_hits), vp(out_total), vp(out_stats), vp(out_count),
+                                              vp(carried), vp(carried_total), C.c_void_p(self._stream(stream))), self.ptr)
+
+    def converge_history(self, settings):
+        """rm_converge_history: history for render_converging.  settings: None turns it off; an rm_reproject, or a dict / tuple of
+        (sigma_z, min_normal_dot, max_history), turns it on -- a camera move then reprojects the frame rather than beginning it
+        again."""
+        if settings is None:
+            _lib.check(self.L.rm_converge_history(self.ptr, None), self.ptr)
+            return
+        if isinstance(settings, dict):
+            settings = _reproject(**settings)
+        elif not isinstance(settings, _lib.rm_reproject):
+            settings = _reproject(*settings)
+        _lib.check(self.L.rm_converge_history(self.ptr, C.byref(settings)), self.ptr)
+
+    def history_info(self):
+        """rm_converge_history_info -> {"reprojections": frames the ticks have begun from history, "last_reprojected": whether the
+        last render_converging tick did, "carried" / "without": the pixels that carried history at the last reprojection and
+        those that did not}.  Host state only."""
+        rep = _lib.rm_history_report()
+        _lib.check(self.L.rm_converge_history_info(self.ptr, C.byref(rep)), self.ptr)
+        return {"reprojections": int(rep.reprojections), "last_reprojected": int(rep.last_reprojected), "carried": int(rep.carried),
+                "without": int(rep.without)}
 
     def primary_hits_device(self, params, out=None, stream=None):
         """rm_primary_hits_device: the closest hit under every pixel rm_render_device writes with `params` (the whole

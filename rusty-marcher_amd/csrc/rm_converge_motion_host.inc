@@ -38,6 +38,11 @@ static rm_status launch_converge_motion_tick(rm_ctx *ctx, const rm_params *p, co
                                              uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
                                              const rm_converge_frame *b, hipStream_t stream);
 
+// The reprojection's launch into the tick's own buffers, mean and bytes included (rm_reproject_host.inc, behind this file)
+static rm_status launch_reproject_tick(rm_ctx *ctx, const rm_params *p, const rm_reproject *r, const rm_view *v, const void *prev_sum,
+                                       const void *prev_stats, const void *prev_count, const void *prev_hits, const void *cur_hits, void *out_sum,
+                                       void *out_stats, void *out_count, void *carried_total, void *mean, void *rgb8, hipStream_t stream);
+
 // A resident prefix of a sequence: rows [0, rows) of `columns` doubles each (the lens table: 4; an offset table: 3 a light or
 // shape; the camera table: 12)
 struct rm_resident_prefix {
@@ -61,12 +66,46 @@ struct rm_converging {
     uint64_t cast = 0;                               // samples cast over the frame's life
     rm_converge last{};                              // what the last pass ran with
     uint32_t last_ns = 0;
+    // history (rm_converge_history; include/rusty_marcher_amd.h, "temporal reprojection").  Off: nothing below is allocated or
+    // looked at.  On: rm_render_converging keeps the hits under the frame's pixels, and a second set of sum, stats and count it
+    // reprojects into and then swaps with the first
+    bool history = false;
+    rm_reproject history_rule{};
+    void *d_hits = nullptr, *d_hits_next = nullptr;  // rm_hit a pixel of the frame's view; of the view a reprojection moves to
+    size_t hits_bytes = 0, hits_next_bytes = 0;
+    bool have_hits = false;                          // d_hits holds the hits of the frame the buffers belong to
+    void *d_sum_next = nullptr, *d_stats_next = nullptr, *d_count_next = nullptr, *d_carried_total = nullptr;
+    size_t next_pixels = 0;                          // the second set has room for that many
+    uint64_t reprojections = 0;                      // rm_history_report's four
+    uint32_t last_reprojected = 0, carried = 0, without = 0;
 };
+
+// Whether two frames differ in nothing but the view: the camera's position, its basis and whether it is oriented
+static bool same_frame_but_view(const rm_frame_identity &a, const rm_frame_identity &b) {
+    rm_frame_identity c = a;
+    c.key.camera = b.key.camera;
+    c.key.basis = b.key.basis;
+    c.key.oriented = b.key.oriented;
+    return rm_same_frame(c, b);
+}
+
+// Turning the history off releases what it alone uses; the report's counters stay
+static rm_status converging_drop_history(rm_ctx *ctx, rm_converging &g) {
+    for (void **b : {&g.d_hits, &g.d_hits_next, &g.d_sum_next, &g.d_stats_next, &g.d_count_next, &g.d_carried_total}) {
+        if (*b) RM_HIP(ctx, hipFree(*b));
+        *b = nullptr;
+    }
+    g.hits_bytes = g.hits_next_bytes = 0;
+    g.next_pixels = 0;
+    g.have_hits = false;
+    return RM_OK;
+}
 
 static void converging_destroy(rm_ctx *ctx, bool device_ok) {
     rm_converging *g = ctx->converging;
     if (!g) return;
-    for (void *b : {g->table.d, g->lights.d, g->shapes.d, g->camera.d, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8})
+    for (void *b : {g->table.d, g->lights.d, g->shapes.d, g->camera.d, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8,
+                    g->d_hits, g->d_hits_next, g->d_sum_next, g->d_stats_next, g->d_count_next, g->d_carried_total})
         if (b && device_ok) (void)hipFree(b);
     delete g;
     ctx->converging = nullptr;
@@ -143,14 +182,35 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
         rm_frame_identity id = rm_frame_identity_of(*p, *lens, ctx->camera, ctx->basis, ctx->oriented, ctx->upload_copies, rules);
         if (any_shape) id.key.motion = 2u;
         const bool same = !restart && g.have_key && rm_same_frame(g.id, id);
+        // history: rm_render_converging's alone.  A frame that differs from the kept one in the view only is carried over
+        const bool keeps_hits = g.history && !rules.motion && !rules.camera && !any_shape;
+        const bool reproject = keeps_hits && !same && !restart && g.have_key && g.passes > 0u && g.have_hits && same_frame_but_view(g.id, id);
+        const size_t hit_bytes = (size_t)p->frame_height * p->frame_width * sizeof(rm_hit);
         const rm_staging staged = rm_staging_of(any_shape ? RM_TICK_CONVERGING_MOVING : RM_TICK_CONVERGING, rules, ctx->image.H.n_lights,
                                                 ctx->image.H.n_spheres, resident_shape_count(ctx));
         // a finished picture: the pass before this one, with the same rule, listed nothing -- so would this one
         const bool finished = same && g.passes > 0u && g.listed == 0u && g.last_ns == ns && std::memcmp(&g.last, c, sizeof *c) == 0;
         RM_HIP(ctx, hipSetDevice(ctx->device));
+        if (finished && keeps_hits && !g.have_hits) {
+            // the continuing frame has no hit buffer yet (history was turned on since it began): this tick fills it
+            g.have_key = false;
+            if (rm_status gst = grow_device_buffer(ctx, &g.d_hits, &g.hits_bytes, hit_bytes)) return gst;
+            if (rm_status lst = timed_launch(ctx, &kernel_ms, [&]() { return rm_primary_hits_device_impl(ctx, p, g.d_hits, ctx->stream); })) return lst;
+            g.have_hits = true;
+            g.have_key = true;
+        }
         if (!finished) {
             g.have_key = false;                                            // (until this call is through)
-            if (!same) {
+            rm_view previous_view{};
+            if (reproject) {
+                // the kept sums move to the new view: the pass total is held to max_history as every carried count is
+                previous_view.position = g.id.key.camera;
+                previous_view.basis = g.id.key.basis;
+                g.n = std::min<uint32_t>(g.n, g.history_rule.max_history);
+                g.passes = 0u; g.listed = 0u; g.cast = 0u;
+                g.id = std::move(id);
+            } else if (!same) {
+                g.have_hits = false;
                 g.n = 0u; g.passes = 0u; g.listed = 0u; g.cast = 0u;
                 // the light rows stay where they are the same sequence (the lens sequence is the same for every frame); the shape
                 // rows are a function of the velocities and the shutter: whatever began the frame again, they go
@@ -190,25 +250,64 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                     }))
                     return est;
             }
-            const rm_converge_frame b{g.d_sum, g.d_stats, g.d_count, g.d_ws, g.d_mean, g.d_rgb8, nullptr};
+            const bool fill_hits = keeps_hits && !reproject && !g.have_hits;
+            if (fill_hits || reproject)
+                if (rm_status gst = grow_device_buffer(ctx, &g.d_hits, &g.hits_bytes, hit_bytes)) return gst;
+            if (reproject) {
+                if (rm_status gst = grow_device_buffer(ctx, &g.d_hits_next, &g.hits_next_bytes, hit_bytes)) return gst;
+                if (rm_status gst = grow_frame_buffers(ctx, &g.next_pixels, pixels,
+                                                       {{&g.d_sum_next, pixels * 3u * sizeof(double)}, {&g.d_stats_next, pixels * 2u * sizeof(double)},
+                                                        {&g.d_count_next, pixels * sizeof(uint32_t)}}))
+                    return gst;
+                size_t word = g.d_carried_total ? 256u : 0u;
+                if (rm_status gst = grow_device_buffer(ctx, &g.d_carried_total, &word, 256u)) return gst;
+                g.have_hits = false;                                       // (until the swap below is through)
+            }
+            const rm_converge_frame b{reproject ? g.d_sum_next : g.d_sum, reproject ? g.d_stats_next : g.d_stats, reproject ? g.d_count_next : g.d_count,
+                                      g.d_ws, g.d_mean, g.d_rgb8, nullptr};
+            const int fresh = !reproject && g.n == 0u;
             // (the kernel is told what is resident -- at least `need` rows of every sequence -- so its clamp guards the buffers' end)
             uint32_t resident = g.table.rows;
             if (offsets) resident = std::min(resident, g.lights.rows);
             if (shapes) resident = std::min(resident, g.shapes.rows);
             if (rules.camera) resident = std::min(resident, g.camera.rows);
-            auto launch = [&]() {
+            auto launch = [&]() -> rm_status {
+                if (fill_hits)
+                    if (rm_status hst = rm_primary_hits_device_impl(ctx, p, g.d_hits, ctx->stream)) return hst;
+                if (reproject) {
+                    if (rm_status hst = rm_primary_hits_device_impl(ctx, p, g.d_hits_next, ctx->stream)) return hst;
+                    if (rm_status rst = launch_reproject_tick(ctx, p, &g.history_rule, &previous_view, g.d_sum, g.d_stats, g.d_count, g.d_hits,
+                                                              g.d_hits_next, g.d_sum_next, g.d_stats_next, g.d_count_next, g.d_carried_total,
+                                                              g.d_mean, g.d_rgb8, ctx->stream))
+                        return rst;
+                }
                 if (rules.camera)
                     return launch_converge_camera(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, shapes ? g.shapes.d : nullptr,
-                                                  g.camera.d, g.n == 0u, &b, ctx->stream);
+                                                  g.camera.d, fresh, &b, ctx->stream);
                 if (any_shape)
                     return any_shape(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, shapes ? g.shapes.d : nullptr,
-                                     g.n == 0u, &b, ctx->stream);
+                                     fresh, &b, ctx->stream);
                 if (rules.motion)
                     return launch_converge_motion_tick(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr,
-                                                       shapes ? g.shapes.d : nullptr, g.n == 0u, &b, ctx->stream);
-                return launch_converge(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, g.n == 0u, &b, ctx->stream);
+                                                       shapes ? g.shapes.d : nullptr, fresh, &b, ctx->stream);
+                return launch_converge(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, fresh, &b, ctx->stream);
             };
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
+            if (fill_hits) g.have_hits = true;
+            if (reproject) {
+                uint32_t carried = 0;
+                RM_HIP(ctx, hipMemcpy(&carried, g.d_carried_total, sizeof carried, hipMemcpyDeviceToHost));
+                std::swap(g.d_sum, g.d_sum_next);
+                std::swap(g.d_stats, g.d_stats_next);
+                std::swap(g.d_count, g.d_count_next);
+                std::swap(g.d_hits, g.d_hits_next);
+                std::swap(g.hits_bytes, g.hits_next_bytes);
+                g.pixels = g.next_pixels = std::min(g.pixels, g.next_pixels);   // (the room of either set, now that they are mixed)
+                g.have_hits = true;
+                g.reprojections += 1u;
+                g.carried = carried;
+                g.without = (uint32_t)pixels - carried;
+            }
             uint32_t listed = 0;
             RM_HIP(ctx, hipMemcpy(&listed, g.d_ws, sizeof listed, hipMemcpyDeviceToHost));
             g.listed = listed;
@@ -221,6 +320,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
             g.last_ns = ns;
             g.have_key = true;
         }
+        if (!rules.motion && !rules.camera && !any_shape) g.last_reprojected = reproject ? 1u : 0u;   // (rm_render_converging's own)
         rep.listed = finished ? 0u : g.listed;
         rep.passes = g.passes;
         rep.max_count = g.n;

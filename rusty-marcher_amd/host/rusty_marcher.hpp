@@ -601,6 +601,29 @@ struct Renderer {
                                 device_variance, device_rgb8, hip_stream),
               ctx_);
     }
+    // Temporal reprojection (include/rusty_marcher_amd.h, "temporal reprojection").  rm_reproject_device for a host that keeps
+    // its own device buffers: carries the converging frame prev_sum, prev_stats, prev_count, sampled from previous_view whose hits
+    // are prev_hits, to the view cur_hits was made for, into out_sum, out_stats, out_count; out_carried and out_carried_total may
+    // be NULL.  Asynchronous on hip_stream
+    void reproject_device(const rm_params &p, const rm_reproject &reproject, const rm_view &previous_view, const void *prev_sum,
+                          const void *prev_stats, const void *prev_count, const void *prev_hits, const void *cur_hits, void *out_sum,
+                          void *out_stats, void *out_count, void *out_carried, void *out_carried_total, void *hip_stream) {
+        check(rm_reproject_device(ctx_, &p, &reproject, &previous_view, prev_sum, prev_stats, prev_count, prev_hits, cur_hits, out_sum, out_stats,
+                                  out_count, out_carried, out_carried_total, hip_stream),
+              ctx_);
+    }
+    // History for render_converging (rm_converge_history): a camera move then carries the frame to the new view rather than
+    // beginning it again.  NULL turns it off.  The default holds starting values, not tuned ones; max_history bounds how long
+    // view-dependent light is carried as if it stuck to the surface
+    void converge_history(const rm_reproject *reproject) { check(rm_converge_history(ctx_, reproject), ctx_); }
+    void keep_history(const rm_reproject &reproject = rm_reproject{.1, .9, 32u, 0u}) { converge_history(&reproject); }
+    void drop_history() { converge_history(nullptr); }
+    // rm_converge_history_info: tells a reprojected tick from one that began again
+    rm_history_report history_info() {
+        rm_history_report out{};
+        check(rm_converge_history_info(ctx_, &out), ctx_);
+        return out;
+    }
     // The converging frame the last render_converging* call built, filtered into `frame` (rm_render_denoised); the converging
     // frame itself is left alone and its next tick continues it.  guides: steer the filter by the hits under the pixels as well --
     // the pinhole view: off under a wide aperture, a moving camera or strongly moving shapes.  The defaults are starting values,

@@ -255,6 +255,22 @@ class Renderer:
             report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus)
         return report
 
+    def keep_history(self, sigma_z=.1, min_normal_dot=.9, max_history=32):
+        """History for render_converging, render_converged and render_denoised (rm_converge_history): once the camera moves, the
+        frame is no longer begun again but carried to the new view -- every pixel finds the point under it in the previous
+        picture and begins with what the samples around it on the same surface held, at most max_history samples' worth; a
+        sample is taken only from the same shape, where the normals' dot product exceeds min_normal_dot and the point lies
+        within sigma_z (1 + distance) of the pixel's tangent plane.  Pixels that see something new begin at nothing.  Light that
+        depends on the view (mirror, glass) is carried as if it stuck to the surface: max_history bounds how long that error
+        lives and should stay well under max_samples.  The keyword defaults are starting values, not tuned ones.  The setting is
+        the device context's and holds until drop_history()."""
+        settings = backend._reproject(sigma_z, min_normal_dot, max_history)   # ValueError before the library sees anything
+        backend.default_context(self.device).converge_history(settings)
+
+    def drop_history(self):
+        """Turns keep_history off again: a camera move begins the converging frame again, as it does by default."""
+        backend.default_context(self.device).converge_history(None)
+
     def render_denoised(self, frame, scene, sigma_l=4., sigma_z=.1, iterations=5, normal_squarings=5, guides=True, epsilon=1e-10,
                         fallback_variance=1.):
         """The converging frame the last render_converging* call built, filtered (rm_render_denoised): an edge-avoiding a-trous

@@ -216,6 +216,46 @@ impl Default for RmDenoise {
     }
 }
 
+/// `rm_view`: a camera as `rm_camera_get` reports it, position and basis (96 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmView {
+    pub position: RmVec3,
+    pub basis: RmCameraBasis,
+}
+
+/// `rm_reproject`: the temporal reprojection's control -- the plane-distance gate relative to 1 + t, the dot product of the
+/// normals a tap must exceed, and the most samples a pixel may carry (24 bytes).
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct RmReproject {
+    pub sigma_z: f64,
+    pub min_normal_dot: f64,
+    pub max_history: u32,
+    pub _pad: u32,
+}
+
+impl Default for RmReproject {
+    /// Starting values, not tuned ones.
+    fn default() -> RmReproject {
+        RmReproject { sigma_z: 0.1, min_normal_dot: 0.9, max_history: 32, _pad: 0 }
+    }
+}
+
+/// `rm_history_report`: what the converging tick did with its history (24 bytes).
+#[repr(C)]
+#[derive(Copy, Clone, Default)]
+pub struct RmHistoryReport {
+    /// Frames the ticks have begun from history since the context was made.
+    pub reprojections: u64,
+    /// The last `render_converging` tick began its frame from history: 1, else 0.
+    pub last_reprojected: u32,
+    /// Pixels that carried history at the last reprojection, and those of the frame's rows that did not.
+    pub carried: u32,
+    pub without: u32,
+    pub _pad: u32,
+}
+
 /// `rm_camera_motion`: how the camera moves while the shutter stands open -- world units a unit of time, and yaw, pitch and roll
 /// in radians a unit of time about the axes and with the signs of `basis_turn` (48 bytes).
 #[repr(C)]
@@ -380,6 +420,9 @@ extern "C" {
     fn rm_denoise_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
     fn rm_denoise_device(ctx: *mut RmCtx, params: *const RmParams, denoise: *const RmDenoise, device_sum: *const c_void, device_stats: *const c_void, device_count: *const c_void, device_hits: *const c_void, device_workspace: *mut c_void, device_out: *mut c_void, device_variance: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_render_denoised(ctx: *mut RmCtx, params: *const RmParams, denoise: *const RmDenoise, guides: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, timing: *mut RmTiming) -> c_int;
+    fn rm_reproject_device(ctx: *mut RmCtx, params: *const RmParams, reproject: *const RmReproject, previous_view: *const RmView, prev_sum: *const c_void, prev_stats: *const c_void, prev_count: *const c_void, prev_hits: *const c_void, cur_hits: *const c_void, out_sum: *mut c_void, out_stats: *mut c_void, out_count: *mut c_void, out_carried: *mut c_void, out_carried_total: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_converge_history(ctx: *mut RmCtx, reproject: *const RmReproject) -> c_int;
+    fn rm_converge_history_info(ctx: *mut RmCtx, report: *mut RmHistoryReport) -> c_int;
     fn rm_build_info() -> *const c_char;
     fn rm_device_info(ctx: *mut RmCtx, name_buf: *mut c_char, buflen: usize, n_cus: *mut c_int, lds_bytes: *mut usize) -> c_int;
     fn rm_kernel_name(ctx: *mut RmCtx, params: *const RmParams, buf: *mut c_char, buflen: usize) -> c_int;
@@ -1693,6 +1736,58 @@ impl Gpu {
             }
         }
         Gpu::status(now, frame.width, frame.height)
+    }
+
+    /// Temporal reprojection for a host that keeps its own device buffers: carries the converging frame `prev_sum`, `prev_stats`,
+    /// `prev_count`, sampled from `previous_view` whose hits are `prev_hits`, to the view `cur_hits` was made for, into `out_sum`,
+    /// `out_stats` and `out_count`; `out_carried` (a byte a pixel) and `out_carried_total` (one u32 on the device) may be null.
+    /// Asynchronous on `hip_stream`.
+    pub fn reproject_device(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        reproject: RmReproject,
+        previous_view: RmView,
+        prev_sum: *const c_void,
+        prev_stats: *const c_void,
+        prev_count: *const c_void,
+        prev_hits: *const c_void,
+        cur_hits: *const c_void,
+        out_sum: *mut c_void,
+        out_stats: *mut c_void,
+        out_count: *mut c_void,
+        out_carried: *mut c_void,
+        out_carried_total: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        check(
+            unsafe {
+                rm_reproject_device(self.ctx, &p, &reproject, &previous_view, prev_sum, prev_stats, prev_count, prev_hits, cur_hits, out_sum, out_stats, out_count, out_carried, out_carried_total, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// History for `render_converging`: with `Some(settings)` a camera move no longer begins the frame again but carries it to
+    /// the new view; `None` turns that off.  `RmReproject::default()` holds starting values, not tuned ones; `max_history`
+    /// bounds how long view-dependent light is carried as if it stuck to the surface.
+    pub fn converge_history(&mut self, reproject: Option<RmReproject>) {
+        let r = match reproject.as_ref() {
+            Some(r) => r as *const RmReproject,
+            None => ptr::null(),
+        };
+        check(unsafe { rm_converge_history(self.ctx, r) }, self.ctx);
+    }
+
+    /// What the ticks did with their history: tells a reprojected tick from one that began again.
+    pub fn history_info(&mut self) -> RmHistoryReport {
+        let mut out = RmHistoryReport::default();
+        check(unsafe { rm_converge_history_info(self.ctx, &mut out) }, self.ctx);
+        out
     }
 
     /// Bytes of device memory the list of `accumulate_converging` needs for a frame of that size.
