@@ -1747,6 +1747,93 @@ rm_status rm_reproject_device(rm_ctx *ctx, const rm_params *params, const rm_rep
 rm_status rm_converge_history(rm_ctx *ctx, const rm_reproject *reproject /* NULL: off */);
 rm_status rm_converge_history_info(rm_ctx *ctx, rm_history_report *report);
 
+/* ---- diffuse bounce: one bounce of indirect light in sampled frames ----------------------------
+ * Every sampled frame shades a hit with direct light plus the constant background.  These calls
+ * give each sample of a progressive or a converging frame one more ray: where the sample's camera
+ * ray first hits a surface that is not glass, a ray leaves that point in a cosine-distributed
+ * direction, and what comes back along it, scaled by the surface's diffuse colour, is added to the
+ * sample.  The mean converges to a picture in which surfaces light each other.  Static scene,
+ * standing camera; lens and area lights as in the members underneath.  Additive to ABI version 5;
+ * a host detects them by " bounce" in rm_build_info().
+ *
+ * A bounce table is [rows][2] doubles, points of [0,1)^2.  The rule, every operation rounded once
+ * in this order, no contraction.  A sample bounces only when its camera ray (depth 1) has its first
+ * hit on a surface with is_glass_like == false; P (the hit point), N (its normal) and mat are the
+ * hit's as every sampled frame shades it, dir is the camera ray's direction.  (t0, t1) is the
+ * sample's row of the table, pix = y * frame_width + x of the sample's pixel.
+ *  1. shift:  h = pix as a 32-bit word; h ^= h>>16; h *= 0x7feb352d; h ^= h>>15; h *= 0x846ca68b;
+ *     h ^= h>>16 (mod 2^32).  sx = (double)(h & 0xffff) / 65536., sy = (double)(h >> 16) / 65536.;
+ *     x = t0 + sx, x = x - floor(x); y = t1 + sy, y = y - floor(y).  Nothing read from a buffer
+ *     forms an address.
+ *  2. disc:   a = 2.*x - 1., b = 2.*y - 1.; sA = sqrt(1. - a*a/2.), sB = sqrt(1. - b*b/2.);
+ *     u = a*sB, v = b*sA; w = sqrt(fmax(1. - (u*u + v*v), 0.)) -- the disc of rm_lens_sequence.
+ *     That map is not area preserving, so the sample carries the weight
+ *     k = 1.2732395447351628 * (sA*sB - (a*a*b*b) / (4.*sA*sB)), its Jacobian times 4/pi.  sA and
+ *     sB lie in [sqrt(1/2), 1]: nothing divides by zero, 0 <= k <= 4/pi, and the weighted samples
+ *     are cosine-distributed (the mean of k is 1, of k*w 2/3).
+ *  3. frame:  Nf = dot(dir, N) < 0. ? N : -N; sg = Nf.z < 0. ? -1. : 1.; q = -1. / (sg + Nf.z)
+ *     (|sg + Nf.z| >= 1); c = Nf.x*Nf.y*q; T = (1. + sg*Nf.x*Nf.x*q, sg*c, -sg*Nf.x);
+ *     B = (c, sg + Nf.y*Nf.y*q, -Nf.y); omega = normalized((T*u + B*v) + Nf*w);
+ *     O' = P + Nf * 1e-3.
+ *  4. light:  the sample's radiance is A + tint * S per channel, where A is what the member
+ *     underneath returns for the sample (background + direct light of the hit), tint is
+ *     mat.diffuse_color and S is cast_ray(O', omega, n_recursion = 2, max_depth) of the reference
+ *     with every term scaled by wb = (strength * mat.diffusion) * k: the sum, in the order the
+ *     kernels of every sampled frame walk a ray's tree, of weight * (background + direct light) at
+ *     a hit, weight * background where a ray leaves the scene or lies beyond the cap, with the
+ *     weight wb at the bounce ray and times reflection or (1 - reflection) at each child.  The
+ *     sample's lights (moved by its row of the offset table) shade every hit of the bounce's tree.
+ *     A bounce beyond the cap (max_depth == 1) returns the background: A + tint * (background * wb).
+ * Glass first hits, misses and max_depth == 0 are the member underneath, unchanged.  With
+ * strength == 0 nothing is cast and no operation on a value differs from the member underneath:
+ * rm_accumulate_bounce_device writes rm_accumulate_soft_device's bytes,
+ * rm_accumulate_converging_bounce_device writes rm_accumulate_converging_device's.  The tests hold
+ * a frame to the reference's cast_ray within 1e-9 a channel of the mean; the largest deviations
+ * seen are in DESIGN.md.
+ *
+ * rm_bounce_sequence fills rows first .. first + count - 1 of one fixed table, count * 2 doubles:
+ * row s = (phi_19(s), phi_23(s)), phi_b as in rm_lens_sequence.  Host arithmetic only.
+ * first + count > RM_PROGRESSIVE_MAX_SAMPLES and a NULL table with something to write are
+ * RM_ERR_INVALID_ARG; count == 0 is RM_OK, nothing is written.  The device calls take any table.
+ *
+ * rm_accumulate_bounce_device is rm_accumulate_soft_device with the bounce table and the strength:
+ * the same checks, and device_bounce must not be NULL and strength must be a finite number >= 0,
+ * else RM_ERR_INVALID_ARG.  lens->n_samples rows of device_bounce are read (with strength == 0
+ * none).  Their contents are a precondition: a non-finite entry gives unspecified pixels, never a
+ * fault.  rm_accumulate_converging_bounce_device is rm_accumulate_converging_device with the same
+ * two: table_rows rows of device_bounce are resident, and a pixel's sample takes the bounce row of
+ * its table row.
+ *
+ * rm_render_progressive_bounce and rm_render_converging_bounce are the ticks: rm_render_progressive_soft
+ * and rm_render_converging (radii NULL: point lights) on the same context-owned state, with the key
+ * extended by the strength -- a strength of 0 is not "no bounce".  So a frame begins again when the
+ * strength changes, when a caller switches between one of these and another tick in either
+ * direction, and on everything that begins the tick underneath again -- a camera move included:
+ * rm_converge_history does not reach these frames.  The progressive tick stages rows
+ * [N, N + n_samples) of rm_bounce_sequence beside the others, the converging tick keeps a third
+ * resident prefix of 2 columns.  Checked before anything else happens: what the tick underneath
+ * checks, and the strength; a refused call changes nothing.  rm_render_denoised serves the
+ * converging tick as it serves the others; its guide is still the pinhole view.
+ */
+rm_status rm_bounce_sequence(uint32_t first, uint32_t count, double *table);
+rm_status rm_accumulate_bounce_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const void *device_table,
+                                      const void *device_offsets, uint32_t n_lights, const void *device_bounce, double strength,
+                                      uint32_t n_before, void *device_sum, void *device_mean /* optional */,
+                                      void *device_rgb8 /* optional */, void *hip_stream);
+rm_status rm_accumulate_converging_bounce_device(rm_ctx *ctx, const rm_params *params, const rm_lens *lens,
+                                                 const rm_converge *converge, const void *device_table, uint32_t table_rows,
+                                                 const void *device_offsets /* optional */, uint32_t n_lights,
+                                                 const void *device_bounce, double strength, int fresh,
+                                                 const rm_converge_frame *frame, void *hip_stream);
+rm_status rm_render_progressive_bounce(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const double *radii /* optional */,
+                                       uint32_t n_lights, double strength, int restart, double *host_rgb /* optional */,
+                                       uint8_t *host_rgb8 /* optional */, uint32_t *n_total /* optional */,
+                                       rm_timing *timing /* optional */);
+rm_status rm_render_converging_bounce(rm_ctx *ctx, const rm_params *params, const rm_lens *lens, const rm_converge *converge,
+                                      const double *radii /* optional */, uint32_t n_lights, double strength, int restart,
+                                      double *host_rgb /* optional */, uint8_t *host_rgb8 /* optional */,
+                                      rm_converge_report *report /* optional */, rm_timing *timing /* optional */);
+
 /* Library / device introspection for harnesses. */
 uint32_t    rm_abi_version(void);
 const char *rm_build_info(void);

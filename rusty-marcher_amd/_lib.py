@@ -314,6 +314,15 @@ SIGNATURES = {
     "rm_reproject_device": (C.c_int, [_VP, _P(rm_params), _P(rm_reproject), _P(rm_view), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_converge_history": (C.c_int, [_VP, _P(rm_reproject)]),
     "rm_converge_history_info": (C.c_int, [_VP, _P(rm_history_report)]),
+    "rm_bounce_sequence": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_double)]),
+    "rm_accumulate_bounce_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _VP, _VP, C.c_uint32, _VP, C.c_double, C.c_uint32, _VP, _VP,
+                                              _VP, _VP]),
+    "rm_accumulate_converging_bounce_device": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _VP, C.c_uint32, _VP, C.c_uint32, _VP,
+                                                         C.c_double, C.c_int, _P(rm_converge_frame), _VP]),
+    "rm_render_progressive_bounce": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(C.c_double), C.c_uint32, C.c_double, C.c_int,
+                                               _P(C.c_double), _P(C.c_uint8), _P(C.c_uint32), _P(rm_timing)]),
+    "rm_render_converging_bounce": (C.c_int, [_VP, _P(rm_params), _P(rm_lens), _P(rm_converge), _P(C.c_double), C.c_uint32, C.c_double,
+                                              C.c_int, _P(C.c_double), _P(C.c_uint8), _P(rm_converge_report), _P(rm_timing)]),
     "rm_abi_version": (C.c_uint32, []),
     "rm_build_info": (C.c_char_p, []),
     "rm_device_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_size_t)]),

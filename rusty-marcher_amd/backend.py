@@ -215,6 +215,30 @@ def _offset_tensor(offsets, name, what, n_samples, device):
     return torch.from_numpy(off).to(device)
 
 
+def _strength(strength):
+    """The strength of a diffuse bounce: a finite number >= 0."""
+    strength = float(strength)
+    if not np.isfinite(strength) or not strength >= 0.:
+        raise ValueError("strength must be a finite number >= 0, got %r" % strength)
+    return strength
+
+
+def _bounce_tensor(bounce, n_rows, device):
+    """A bounce table as a contiguous float64 tensor (n_rows, 2) on `device`: a tensor is checked, an array is checked (finite)
+    and copied over."""
+    torch = _torch()
+    if isinstance(bounce, torch.Tensor):
+        if bounce.dtype != torch.float64 or tuple(bounce.shape) != (n_rows, 2) or not bounce.is_contiguous():
+            raise ValueError("bounce must be a contiguous float64 torch tensor of shape (%d, 2)" % n_rows)
+        if bounce.device != device:
+            raise ValueError("bounce must live on %s, not %s" % (device, bounce.device))
+        return bounce
+    rows = np.ascontiguousarray(bounce, dtype=np.float64)
+    if rows.shape != (n_rows, 2) or not np.isfinite(rows).all():
+        raise ValueError("bounce must be a finite float64 array of shape (%d, 2), got %s" % (n_rows, rows.shape))
+    return torch.from_numpy(rows).to(device)
+
+
 def _converge(tolerance, min_samples, max_samples, n_samples, table_rows=PROGRESSIVE_MAX_SAMPLES):
     """rm_converge of a converging frame: tolerance any number but NaN, min_samples an integer >= 0, max_samples an integer in
     n_samples..min(table_rows, RM_PROGRESSIVE_MAX_SAMPLES)."""
@@ -1043,6 +1067,90 @@ class Context:
                                                *host, C.byref(report), C.byref(timing)), self.ptr)
         return timing, report
 
+    # ---- diffuse bounce (include/rusty_marcher_amd.h, "diffuse bounce") ----
+    def bounce_sequence(self, first, count):
+        """backend.bounce_sequence."""
+        return bounce_sequence(first, count)
+
+    def accumulate_bounce_device(self, params, sum, aperture, focus, table, offsets, bounce, strength, n_before, mean=None, rgb8=None,
+                                 stream=None):
+        """rm_accumulate_bounce_device: accumulate_soft_device with one bounce of indirect light -- where sample row s first hits
+        a surface that is not glass, a ray leaves it in the direction row s of `bounce` gives (shifted for every pixel), and what
+        comes back, times `strength`, the surface's diffusion and its diffuse colour, is added to the sample.  bounce: a
+        contiguous float64 tensor (n_samples, 2) of points in [0, 1) on the context's device, or an array, which is checked
+        (finite) and copied over; strength: a finite number >= 0, 0 is accumulate_soft_device's frame byte for byte.
+        -> (the table's tensor, the offsets' tensor, the bounce table's tensor)."""
+        strength = _strength(strength)
+        lens, table = _accumulate_args(self.device, params, sum, aperture, focus, table, n_before, mean, rgb8)
+        offsets = _offset_tensor(offsets, "offsets", "n_lights", lens.n_samples, sum.device)
+        bounce = _bounce_tensor(bounce, lens.n_samples, sum.device)
+        n_lights = int(offsets.shape[1])
+        _lib.check(self.L.rm_accumulate_bounce_device(self.ptr, C.byref(params), C.byref(lens), C.c_void_p(table.data_ptr()),
+                                                      C.c_void_p(offsets.data_ptr()) if n_lights > 0 else None, n_lights,
+                                                      C.c_void_p(bounce.data_ptr()), strength, int(n_before),
+                                                      C.c_void_p(sum.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                                      C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+                                                      C.c_void_p(self._stream(stream))), self.ptr)
+        return table, offsets, bounce
+
+    def render_progressive_bounce(self, params, aperture, focus, n_samples, strength=1., radii=None, restart=False, host_rgb=None,
+                                  host_rgb8=None):
+        """rm_render_progressive_bounce: render_progressive_soft with a diffuse bounce of the library's sequence; radii: one radius
+        a light for area lights, None for point lights.  The frame begins again when the strength changes or the caller switches
+        between this call and another tick, and on everything that begins it again there.
+        -> (rm_timing, samples a pixel in the frame now)."""
+        lens = _lens(aperture, focus, n_samples)
+        strength = _strength(strength)
+        r = _radii(radii) if radii is not None else None
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing, total = _lib.rm_timing(), C.c_uint32(0)
+        _lib.check(self.L.rm_render_progressive_bounce(self.ptr, C.byref(params), C.byref(lens),
+                                                       r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                       r.shape[0] if r is not None else 0, strength, 1 if restart else 0,
+                                                       *host, C.byref(total), C.byref(timing)), self.ptr)
+        return timing, total.value
+
+    def accumulate_converging_bounce_device(self, params, sum, stats, count, aperture, focus, n_samples, table, bounce, strength, tolerance,
+                                            min_samples, max_samples, fresh, offsets=None, mean=None, rgb8=None, mask=None, workspace=None,
+                                            stream=None):
+        """rm_accumulate_converging_bounce_device: accumulate_converging_device with a diffuse bounce -- the sample that is row r
+        of the tables takes row r of `bounce`, (rows, 2) with the table's rows, a float64 tensor on the context's device or an
+        array.  strength: a finite number >= 0, 0 is accumulate_converging_device's pass byte for byte.
+        -> the workspace, as accumulate_converging_device."""
+        strength = _strength(strength)
+        lens, conv, table, workspace = _converging_args(self, params, sum, stats, count, aperture, focus, n_samples, table, tolerance, min_samples,
+                                                        max_samples, mean, rgb8, mask, workspace)
+        rows = int(table.shape[0])
+        bounce = _bounce_tensor(bounce, rows, sum.device)
+        n_lights = 0
+        if offsets is not None:
+            offsets = _offset_tensor(offsets, "offsets", "n_lights", rows, sum.device)
+            n_lights = int(offsets.shape[1])
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        frame = _lib.rm_converge_frame(vp(sum), vp(stats), vp(count), vp(workspace), vp(mean), vp(rgb8), vp(mask))
+        _lib.check(self.L.rm_accumulate_converging_bounce_device(self.ptr, C.byref(params), C.byref(lens), C.byref(conv), vp(table), rows,
+                                                                 vp(offsets) if n_lights > 0 else None, n_lights, vp(bounce),
+                                                                 strength, 1 if fresh else 0, C.byref(frame),
+                                                                 C.c_void_p(self._stream(stream))), self.ptr)
+        return workspace
+
+    def render_converging_bounce(self, params, aperture, focus, n_samples, tolerance, min_samples, max_samples, strength=1., radii=None,
+                                 restart=False, host_rgb=None, host_rgb8=None):
+        """rm_render_converging_bounce: render_converging with a diffuse bounce of the library's sequence.  The frame is
+        render_converging's own: beyond what begins it again there, a changed strength does, a switch between the calls does, and
+        so does every camera move (history does not reach it).  -> (rm_timing, rm_converge_report)."""
+        lens = _lens(aperture, focus, n_samples)
+        conv = _converge(tolerance, min_samples, max_samples, lens.n_samples)
+        strength = _strength(strength)
+        r = _radii(radii) if radii is not None else None
+        host = _host_outputs(params, host_rgb, host_rgb8)
+        timing, report = _lib.rm_timing(), _lib.rm_converge_report()
+        _lib.check(self.L.rm_render_converging_bounce(self.ptr, C.byref(params), C.byref(lens), C.byref(conv),
+                                                      r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+                                                      r.shape[0] if r is not None else 0, strength, 1 if restart else 0,
+                                                      *host, C.byref(report), C.byref(timing)), self.ptr)
+        return timing, report
+
     # ---- converging frames with moving spheres (include/rusty_marcher_amd.h, "converging frames with moving spheres") ----
     def accumulate_converging_motion_device(self, params, sum, stats, count, aperture, focus, n_samples, table, light_offsets, shape_offsets,
                                             tolerance, min_samples, max_samples, fresh, mean=None, rgb8=None, mask=None, workspace=None,
@@ -1561,6 +1669,15 @@ def camera_sequence(first, count, velocity, shutter, turn=(0., 0., 0.), basis=FI
     _lib.check(_lib.lib().rm_camera_sequence(int(first), int(count), C.byref(motion), C.byref(_lib.camera_basis(basis)), shutter,
                                              rows.ctypes.data_as(C.POINTER(C.c_double))))
     return rows
+
+
+def bounce_sequence(first, count):
+    """rm_bounce_sequence: rows first .. first + count - 1 of the library's bounce sequence, (count, 2) float64 points of [0, 1)
+    (the radical inverses in base 19 and 23).  Host arithmetic: needs neither a context nor a GPU."""
+    first, count = _sequence_rows(first, count)
+    t = np.zeros((int(count), 2), dtype=np.float64)
+    _lib.check(_lib.lib().rm_bounce_sequence(int(first), int(count), t.ctypes.data_as(C.POINTER(C.c_double))), None)
+    return t
 
 
 def swept_extents(table):

@@ -2,7 +2,8 @@
 // rm_soft.hip's (lights moved by the lane's row of an offset table), rm_motion.hip's (spheres moved as well) and
 // rm_motion_shapes.hip's (every shape moved).  Included
 // behind rm_radiance_step.inc.  rm_camera.hip's kernels (the camera moved as well) include it behind rm_camera_ray.inc with
-// RM_CAMERA_ROWS defined, which no other unit does: every other unit sees the tokens it always saw.
+// RM_CAMERA_ROWS defined, which no other unit does: every other unit sees the tokens it always saw.  rm_bounce.hip's kernels (a
+// diffuse bounce behind the camera ray's hit) include it with RM_BOUNCE_ROWS defined, under the same rule.
 //
 // `lights_of(s)`: the rule that says where the lights of table row s stand (rm_trace.inc, StoredLights), asked once a lane
 // before the loop over the groups; `spheres_of(s)`: the same for the spheres (StoredSpheres where none is given).  `bstack` (64 words) and `sums` (64 x 3 doubles) are the workgroup's LDS.
@@ -19,6 +20,11 @@ template <bool BVH, int POW, int STACK, class LIGHTS_OF, class SPHERES_OF = stor
 __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blob, const AccumArgs &a, uint32_t *bstack, double *sums,
 #ifdef RM_CAMERA_ROWS
                                             const double *__restrict__ camera_rows,   // [n_samples][12]: rmcamera::camera_row_ray
+#endif
+#ifdef RM_BOUNCE_ROWS
+                                            const double *__restrict__ bounce_table,  // [n_samples][2]: rmradiance::bounce_ray
+                                            double bounce_strength,
+                                            double *bounce_park,                      // 64 x 6 doubles of LDS
 #endif
                                             LIGHTS_OF lights_of, SPHERES_OF spheres_of = SPHERES_OF()) {
     const LensArgs &q = a.L;
@@ -66,7 +72,13 @@ __device__ __forceinline__ void accum_shade(const double *__restrict__ scene_blo
             }
 #endif
         }
+#ifdef RM_BOUNCE_ROWS
+        // (the row is fetched in the step that bounces: here only its index and the pixel go along)
+        const V3 acc = q.max_depth == 0u ? bg : radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights, spheres,
+                                                                               Bounce{bounce_table, bounce_strength, bounce_park, s, pix});
+#else
         const V3 acc = q.max_depth == 0u ? bg : radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights, spheres);
+#endif
         sums[lane * 3u] = acc.x; sums[lane * 3u + 1u] = acc.y; sums[lane * 3u + 2u] = acc.z;
         __syncthreads();
         if (on & (s == 0u)) {

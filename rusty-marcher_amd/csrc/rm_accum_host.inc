@@ -70,6 +70,8 @@ static rm_status check_rules(rm_ctx *ctx, const char *who, const rm_sampling_rul
         if (rm_status lst = check_soft_lights(ctx, who, r.n_lights)) return lst;
         if (rm_status rst = host_refusal(ctx, rm_check_radii(who, r.radii, r.n_lights))) return rst;
     }
+    if (r.bounce)
+        if (rm_status bst = host_refusal(ctx, rm_check_strength(who, r.strength))) return bst;
     if (r.camera) {                                                        // (the moving camera's ticks: a shutter without velocities too)
         if (rm_status mst = host_refusal(ctx, rm_check_camera_motion(who, r.camera))) return mst;
         if (!r.motion)

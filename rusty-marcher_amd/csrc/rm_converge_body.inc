@@ -11,6 +11,9 @@
 //   spheres_of(r)        the same for the spheres (StoredSpheres, OffsetSpheres) or for every shape (OffsetShapes)
 //   camera_rows          rm_converge_camera.hip alone, which defines RM_CAMERA_ROWS and includes rm_camera_ray.inc: the camera
 //                        table, [table_rows][12].  No other unit defines the symbol: each sees the tokens it always saw.
+//   bounce_table,        rm_converge_bounce.hip alone, which defines RM_BOUNCE_ROWS: the bounce table, [table_rows][2], the
+//   bounce_strength,     strength of the diffuse bounce and the workgroup's 64 x 6 doubles of LDS for it (rm_radiance_step.inc,
+//   bounce_park          Bounce).  The same holds for this symbol.
 //
 // -- the parameters of rm_accum_body.inc's accum_shade, with one difference: both rules are asked inside the loop over the
 // groups, once a lane and group, with the lane's own row r = count[pixel] + sample.  r < table_rows in every lane, idle ones
@@ -69,7 +72,12 @@
         }
         V3 acc = bg;
         if (q.max_depth != 0u)                                           // wave-uniform
+#ifdef RM_BOUNCE_ROWS
+            acc = radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights_of(r), spheres_of(r),
+                                                  Bounce{bounce_table, bounce_strength, bounce_park, r, pix});
+#else
             acc = radiance_steps<BVH, POW, STACK>(sc, orig, dir, on, bg, q.max_depth, lights_of(r), spheres_of(r));
+#endif
         sums[lane * 3u] = acc.x; sums[lane * 3u + 1u] = acc.y; sums[lane * 3u + 2u] = acc.z;
         __syncthreads();
         if (on & (s == 0u)) {

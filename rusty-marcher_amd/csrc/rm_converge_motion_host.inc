@@ -38,6 +38,11 @@ static rm_status launch_converge_motion_tick(rm_ctx *ctx, const rm_params *p, co
                                              uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
                                              const rm_converge_frame *b, hipStream_t stream);
 
+// The diffuse bounce's three steps (rm_bounce_host.inc, behind this file): launch_converge's with the bounce table and the strength
+static rm_status launch_converge_bounce(rm_ctx *ctx, const rm_params *p, const rm_lens *lens, const rm_converge *c, const void *table,
+                                        uint32_t table_rows, const void *offsets, const void *bounce, double strength, int fresh,
+                                        const rm_converge_frame *b, hipStream_t stream);
+
 // The reprojection's launch into the tick's own buffers, mean and bytes included (rm_reproject_host.inc, behind this file)
 static rm_status launch_reproject_tick(rm_ctx *ctx, const rm_params *p, const rm_reproject *r, const rm_view *v, const void *prev_sum,
                                        const void *prev_stats, const void *prev_count, const void *prev_hits, const void *cur_hits, void *out_sum,
@@ -55,6 +60,7 @@ struct rm_resident_prefix {
 struct rm_converging {
     rm_resident_prefix table{nullptr, 0u, 0u, 4u}, lights, shapes;   // of rm_lens_sequence, of rm_light_sequence (or zeros) and of rm_motion_sequence
     rm_resident_prefix camera;                       // ... and of rm_camera_sequence (the moving camera's tick)
+    rm_resident_prefix bounce{nullptr, 0u, 0u, 2u};  // ... and of rm_bounce_sequence (the diffuse bounce's tick): the same rows for every frame
     bool lights_zero = false;                        // `lights` holds zeros: a motion tick's point lights (else rm_light_sequence of id.radii)
     void *d_sum = nullptr, *d_stats = nullptr, *d_count = nullptr, *d_ws = nullptr, *d_mean = nullptr, *d_rgb8 = nullptr;
     size_t pixels = 0;                               // the six buffers have room for that many
@@ -104,7 +110,7 @@ static rm_status converging_drop_history(rm_ctx *ctx, rm_converging &g) {
 static void converging_destroy(rm_ctx *ctx, bool device_ok) {
     rm_converging *g = ctx->converging;
     if (!g) return;
-    for (void *b : {g->table.d, g->lights.d, g->shapes.d, g->camera.d, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8,
+    for (void *b : {g->table.d, g->lights.d, g->shapes.d, g->camera.d, g->bounce.d, g->d_sum, g->d_stats, g->d_count, g->d_ws, g->d_mean, g->d_rgb8,
                     g->d_hits, g->d_hits_next, g->d_sum_next, g->d_stats_next, g->d_count_next, g->d_carried_total})
         if (b && device_ok) (void)hipFree(b);
     delete g;
@@ -158,8 +164,9 @@ using converge_motion_launch = rm_status (*)(rm_ctx *ctx, const rm_params *p, co
                                              uint32_t table_rows, const void *offsets, const void *shape_offsets, int fresh,
                                              const rm_converge_frame *b, hipStream_t stream);
 
-// The tick of the four calls; `rules` says which (rules.camera: the moving camera's, rm_camera_host.inc, which keeps a prefix of
-// rm_camera_sequence as well and launches its own kernels), and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
+// The tick of the five calls; `rules` says which (rules.bounce: the diffuse bounce's, rm_bounce_host.inc, which keeps a prefix of
+// rm_bounce_sequence as well and launches its own shade kernel; its frames begin again on a camera move, history or not;
+// rules.camera: the moving camera's, rm_camera_host.inc, which keeps a prefix of rm_camera_sequence as well and launches its own kernels), and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
 // which a velocity on any shape is obeyed and a shape table is kept whenever the scene holds a shape; key.motion = 2 keeps its
 // frames apart from the moving spheres') from the moving spheres': checked here, the prefixes they ask for kept resident, the
 // launch by them.
@@ -183,7 +190,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
         if (any_shape) id.key.motion = 2u;
         const bool same = !restart && g.have_key && rm_same_frame(g.id, id);
         // history: rm_render_converging's alone.  A frame that differs from the kept one in the view only is carried over
-        const bool keeps_hits = g.history && !rules.motion && !rules.camera && !any_shape;
+        const bool keeps_hits = g.history && !rules.motion && !rules.camera && !rules.bounce && !any_shape;
         const bool reproject = keeps_hits && !same && !restart && g.have_key && g.passes > 0u && g.have_hits && same_frame_but_view(g.id, id);
         const size_t hit_bytes = (size_t)p->frame_height * p->frame_width * sizeof(rm_hit);
         const rm_staging staged = rm_staging_of(any_shape ? RM_TICK_CONVERGING_MOVING : RM_TICK_CONVERGING, rules, ctx->image.H.n_lights,
@@ -250,6 +257,8 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                     }))
                     return est;
             }
+            if (rules.bounce)
+                if (rm_status est = converging_extend(ctx, g, g.bounce, need, rm_fill_bounce_rows)) return est;
             const bool fill_hits = keeps_hits && !reproject && !g.have_hits;
             if (fill_hits || reproject)
                 if (rm_status gst = grow_device_buffer(ctx, &g.d_hits, &g.hits_bytes, hit_bytes)) return gst;
@@ -271,6 +280,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
             if (offsets) resident = std::min(resident, g.lights.rows);
             if (shapes) resident = std::min(resident, g.shapes.rows);
             if (rules.camera) resident = std::min(resident, g.camera.rows);
+            if (rules.bounce) resident = std::min(resident, g.bounce.rows);
             auto launch = [&]() -> rm_status {
                 if (fill_hits)
                     if (rm_status hst = rm_primary_hits_device_impl(ctx, p, g.d_hits, ctx->stream)) return hst;
@@ -290,6 +300,9 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
                 if (rules.motion)
                     return launch_converge_motion_tick(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr,
                                                        shapes ? g.shapes.d : nullptr, fresh, &b, ctx->stream);
+                if (rules.bounce)
+                    return launch_converge_bounce(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, g.bounce.d, rules.strength,
+                                                  fresh, &b, ctx->stream);
                 return launch_converge(ctx, p, lens, c, g.table.d, resident, offsets ? g.lights.d : nullptr, fresh, &b, ctx->stream);
             };
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;
@@ -320,7 +333,7 @@ static rm_status rm_render_converging_impl(rm_ctx *ctx, const char *who, const r
             g.last_ns = ns;
             g.have_key = true;
         }
-        if (!rules.motion && !rules.camera && !any_shape) g.last_reprojected = reproject ? 1u : 0u;   // (rm_render_converging's own)
+        if (!rules.motion && !rules.camera && !rules.bounce && !any_shape) g.last_reprojected = reproject ? 1u : 0u;   // (rm_render_converging's own)
         rep.listed = finished ? 0u : g.listed;
         rep.passes = g.passes;
         rep.max_count = g.n;

@@ -42,6 +42,7 @@
 #include "rm_converge_camera_swept.hpp"
 #include "rm_denoise.hpp"
 #include "rm_reproject.hpp"
+#include "rm_bounce.hpp"
 
 using namespace rmdev;
 
@@ -358,7 +359,7 @@ const void *rm_pick_kernel_oriented(bool fast, bool staged, bool bvh, bool cull,
 extern "C" {
 
 const char *rm_build_info(void) {
-    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy swept-camera denoise reproject converge-moving converge-motion converge";
+    return "rusty-marcher_amd " RM_BUILD_FLAVOR " gfx950 abi5 queries camera ranges radiance antialias lens progressive soft motion moving-shapes moving-camera swept-hierarchy swept-camera denoise reproject bounce converge-moving converge-motion converge";
 }
 
 const char *rm_last_error(const rm_ctx *ctx) {
@@ -1160,3 +1161,4 @@ rm_status rm_postprocess(rm_ctx *ctx, void *device_rgb, uint32_t w, uint32_t h, 
 #include "rm_camera_swept_host.inc"
 #include "rm_denoise_host.inc"
 #include "rm_reproject_host.inc"
+#include "rm_bounce_host.inc"

@@ -29,6 +29,9 @@ using motion_launch = rm_status (*)(rm_ctx *ctx, const accum_call &c, const void
 // no shape moves
 static rm_status launch_camera(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *shape_offsets, const void *camera_rows);
 
+// The diffuse bounce's launch (rm_bounce_host.inc, behind this file): launch_soft's with the bounce table and the strength
+static rm_status launch_bounce(rm_ctx *ctx, const accum_call &c, const void *offsets, const void *bounce, double strength);
+
 // The ticks' swept hierarchy (rm_swept_host.inc, behind this file): made ready in front of a tick that moves a shape for its
 // velocities and shutter (`spheres_only`: the moving spheres' ticks, whose rule it applies), and the moving spheres' launch that
 // walks it where it is ready -- launch_motion where it is not
@@ -67,12 +70,13 @@ struct rm_progressive {
     uint32_t n = 0;                          // samples a pixel in the sum
     rm_staged_slice lights, shapes;          // the slices of rm_light_sequence (or zeros) and of rm_motion_sequence
     rm_staged_slice camera;                  // ... and of rm_camera_sequence (the moving camera's tick)
+    rm_staged_slice bounce;                  // ... and of rm_bounce_sequence (the diffuse bounce's tick)
 };
 
 static void progressive_destroy(rm_ctx *ctx, bool device_ok) {
     rm_progressive *g = ctx->progressive;
     if (!g) return;
-    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->lights.d, g->shapes.d, g->camera.d})
+    for (void *b : {g->d_table, g->d_sum, g->d_mean, g->d_rgb8, g->lights.d, g->shapes.d, g->camera.d, g->bounce.d})
         if (b && device_ok) (void)hipFree(b);
     delete g;
     ctx->progressive = nullptr;
@@ -89,7 +93,8 @@ static rm_status stage_slice(rm_ctx *ctx, rm_staged_slice &s, size_t doubles, FI
     return RM_OK;
 }
 
-// The tick of the five calls; `rules` says which (rules.camera: the moving camera's, rm_camera_host.inc, which stages a slice
+// The tick of the six calls; `rules` says which (rules.bounce: the diffuse bounce's, rm_bounce_host.inc, which stages a slice of
+// rm_bounce_sequence as well and launches its own kernel; rules.camera: the moving camera's, rm_camera_host.inc, which stages a slice
 // of rm_camera_sequence as well and launches its own kernels), and `any_shape`, the moving shapes' launch, tells their tick (a motion tick in
 // which a velocity on any shape is obeyed; key.motion = 2 keeps its frames apart from the moving spheres') from the moving
 // spheres': checked here, the tables they ask for staged, the launch by them.
@@ -134,11 +139,15 @@ static rm_status rm_render_progressive_impl(rm_ctx *ctx, const char *who, const 
                     }))
                     return sst;
             }
+            if (rm_status sst = stage_slice(ctx, g.bounce, (size_t)ns * staged.bounce_columns,
+                                            [&](double *out) { return rm_fill_bounce_rows(n_before, ns, out); }))
+                return sst;
             const accum_call call{p, lens, g.d_table, n_before, g.d_sum, g.d_mean, g.d_rgb8, ctx->stream};
             const void *lights = staged.light_columns > 0u ? g.lights.d : nullptr, *shapes = staged.shape_columns > 0u ? g.shapes.d : nullptr;
             auto launch = [&]() {
                 if (rules.camera) return launch_camera(ctx, call, lights, shapes, g.camera.d);
                 if (any_shape) return any_shape(ctx, call, lights, shapes);
+                if (rules.bounce) return launch_bounce(ctx, call, lights, g.bounce.d, rules.strength);
                 return rules.motion ? launch_motion_tick(ctx, call, lights, shapes) : rules.soft ? launch_soft(ctx, call, lights) : launch_accum(ctx, call);
             };
             if (rm_status lst = timed_launch(ctx, &kernel_ms, launch)) return lst;

@@ -137,6 +137,50 @@ struct SweptShapes : OffsetShapes {
     static constexpr bool swept = true;
 };
 
+#ifdef RM_BOUNCE_ROWS
+// The diffuse bounce of a sample (include/rusty_marcher_amd.h, "diffuse bounce"; rm_bounce.hip and rm_converge_bounce.hip alone
+// define RM_BOUNCE_ROWS, every other unit sees the tokens it always saw).  What a lane carries into its walk is two words and
+// three wave-uniform values: the row's address is formed from `row`, the shift from `pix`; the row itself is fetched where the
+// camera ray's hit is shaded, so nothing of it is alive across the first step's walks.
+struct Bounce {
+    const double *table;                                                 // [rows][2], wave-uniform
+    double strength;                                                     // wave-uniform, finite and >= 0 (the host checked)
+    double *park;                                                        // the workgroup's 64 x 6 doubles of LDS (radiance_steps)
+    uint32_t row;                                                        // the lane's row, inside the table in every lane
+    uint32_t pix;                                                        // y * frame_width + x: hashed, never an address
+};
+
+// lowbias32
+__device__ __forceinline__ uint32_t bounce_hash(uint32_t h) {
+    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+    return h;
+}
+
+// Steps 1-3 of the rule for the camera ray `dir` that hit `s`: the bounce ray (o, w) and the weight k of its direction
+__device__ __forceinline__ void bounce_ray(const Bounce &b, V3 dir, const Surface &s, V3 &o, V3 &w, double &k) {
+    const double *t = b.table + 2u * (size_t)b.row;
+    const uint32_t h = bounce_hash(b.pix);
+    double x = t[0] + (double)(h & 0xffffu) / 65536.;
+    x = x - __builtin_floor(x);
+    double y = t[1] + (double)(h >> 16) / 65536.;
+    y = y - __builtin_floor(y);
+    const double a = 2. * x - 1., c = 2. * y - 1.;
+    const double sA = __builtin_sqrt(1. - a * a / 2.), sB = __builtin_sqrt(1. - c * c / 2.);
+    const double u = a * sB, v = c * sA;
+    const double z = __builtin_sqrt(__builtin_fmax(1. - (u * u + v * v), 0.));
+    k = 1.2732395447351628 * (sA * sB - (a * a * c * c) / (4. * sA * sB));
+    const V3 N = s.normal;
+    const V3 Nf = dot(dir, N) < 0. ? N : neg(N);
+    const double sg = Nf.z < 0. ? -1. : 1.;
+    const double q = -1. / (sg + Nf.z);
+    const double e = Nf.x * Nf.y * q;
+    const V3 T = mk(1. + sg * Nf.x * Nf.x * q, sg * e, -sg * Nf.x);
+    const V3 B = mk(e, sg + Nf.y * Nf.y * q, -Nf.y);
+    w = normalized((scaled(T, u) + scaled(B, v)) + scaled(Nf, z));
+    o = s.point + scaled(Nf, 1e-3);
+}
+#endif
+
 // The un-normalised direction of the sample (sx, sy): renderer.rs:128-135 at a real-valued position, the host's
 // backproject_tables operation for operation.  A: an argument block with the params' Renderer (width, height, half_fov,
 // ratio) and the context's basis (cam_r*, cam_u*, cam_f*; read where oriented).
@@ -157,7 +201,11 @@ __device__ __forceinline__ V3 sample_direction(const A &q, bool oriented, double
 // complete walk (complete_walk_view above).  The shadow rays are normalised and keep the hierarchy.
 template <bool BVH, int POW, int STACK, class LIGHTS = StoredLights, class SPHERES = StoredSpheres, bool ADMIT = false>
 __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 dir, bool on, const V3 bg, const uint32_t max_depth,
-                                             const LIGHTS &lights = LIGHTS(), const SPHERES &spheres = SPHERES()) {
+                                             const LIGHTS &lights = LIGHTS(), const SPHERES &spheres = SPHERES()
+#ifdef RM_BOUNCE_ROWS
+                                             , const Bounce &bounce = Bounce{nullptr, 0., nullptr, 0u, 0u}
+#endif
+                                             ) {
     double weight = 1.;
     uint32_t depth = 1;                                                  // renderer.rs:83
     V3 acc = mk(0., 0., 0.);
@@ -165,6 +213,18 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
     // max_depth - 1 <= STACK of them (the host picks STACK by that rule).
     StackEntry deep[STACK];
     uint32_t n_deep = 0;
+#ifdef RM_BOUNCE_ROWS
+    // A camera ray whose first hit is not glass has no children, so behind step 1 such a lane's whole tree is the bounce's
+    // subtree: the lane turns into the bounce ray with weight strength x diffusion x k at depth 2.  What it had added until then
+    // (A: background + direct light of the first hit) and the hit's diffuse colour (tint) it leaves in its own six doubles of
+    // LDS -- twelve registers that would be alive across every walk of the subtree otherwise --, begins its sum again, and
+    // answers A + tint x sum behind the loop.  A lane reads only what it stored itself: no barrier.  A lane that never
+    // bounced returns its sum as every other unit does.  The rays a bounce lane parks have distinct depths 3 .. max_depth,
+    // fewer than the max_depth - 1 the stack is sized for.
+    bool bounced = false;
+    const bool bouncing = bounce.strength != 0.;                         // wave-uniform
+    double *parked = bounce.park + 6u * (threadIdx.x & 63u);
+#endif
 
     while (__any(on)) {                                                  // one ray step; the loop itself is wave-uniform
         Hit h{0., 0u};
@@ -180,6 +240,10 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
         const double w_add = (on & (got | (depth > 1u))) ? weight : 0.;
         double w_cap = 0.;
         bool next = false;                                               // the lane goes on with a child of its ray
+#ifdef RM_BOUNCE_ROWS
+        double w_bounce_cap = 0.;
+        bool bnc = false;
+#endif
         if (__any(got)) {
             const Surface s = surface_at<false>(sc, orig, dir, h, got, spheres);
             L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, neg(normalized(dir)), s, got, h.pid, lights, spheres), bg);
@@ -209,9 +273,33 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
                 weight = live_t ? wt : live_r ? wr : weight;
                 depth += next ? 1u : 0u;
             }
+#ifdef RM_BOUNCE_ROWS
+            bnc = bouncing & got & !glass & (depth == 1u);               // the camera ray's hit alone holds depth 1
+            if (__any(bnc)) {
+                V3 bo, bw;
+                double k;
+                bounce_ray(bounce, dir, s, bo, bw, k);
+                const double wb = (bounce.strength * s.mat[0]) * k;
+                const bool live_b = bnc & !(2u > max_depth);             // beyond the cap the bounce returns the background
+                w_bounce_cap = (bnc & !live_b) ? wb : 0.;
+                if (bnc) { parked[3] = s.mat[1]; parked[4] = s.mat[2]; parked[5] = s.mat[3]; }
+                next = next | live_b;
+                orig = pick(live_b, bo, orig);
+                dir = pick(live_b, bw, dir);
+                weight = live_b ? wb : weight;
+                depth += live_b ? 1u : 0u;
+            }
+#endif
         }
         acc = acc + mk(__builtin_fma(bg.x, w_cap, L.x * w_add), __builtin_fma(bg.y, w_cap, L.y * w_add),
                        __builtin_fma(bg.z, w_cap, L.z * w_add));
+#ifdef RM_BOUNCE_ROWS
+        if (__any(bnc)) {                                                // the first hit's share is complete: the bounce's sum begins
+            if (bnc) { parked[0] = acc.x; parked[1] = acc.y; parked[2] = acc.z; }
+            acc = pick(bnc, mk(bg.x * w_bounce_cap, bg.y * w_bounce_cap, bg.z * w_bounce_cap), acc);
+            bounced = bounced | bnc;
+        }
+#endif
         // a lane whose ray ended takes its deepest parked ray
         const bool pop = on & !next & (n_deep > 0u);
         if (__any(pop)) {
@@ -224,6 +312,10 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
         }
         on = on & (next | pop);
     }
+#ifdef RM_BOUNCE_ROWS
+    if (bounced)                                                         // per-lane: the other lanes' slots hold nothing of theirs
+        acc = mk(parked[0] + parked[3] * acc.x, parked[1] + parked[4] * acc.y, parked[2] + parked[5] * acc.z);
+#endif
     return acc;
 }
 

@@ -68,6 +68,13 @@ rm_status rm_check_velocities(const char *who, const rm_vec3 *velocities, uint32
     return RM_OK;
 }
 
+rm_status rm_check_strength(const char *who, double strength) {
+    if (std::isfinite(strength) && strength >= 0.) return RM_OK;
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "%s: strength = %g is not a finite number >= 0", who, strength);
+    return refuse(buf);
+}
+
 rm_frame_identity rm_frame_identity_of(const rm_params &p, const rm_lens &lens, const rm_vec3 &camera, const rm_camera_basis &basis, bool oriented,
                                        uint64_t upload_copies, const rm_sampling_rules &rules) {
     rm_frame_identity id;
@@ -94,6 +101,10 @@ rm_frame_identity rm_frame_identity_of(const rm_params &p, const rm_lens &lens, 
         key.camera_motion = *rules.camera;
         key.shutter = rules.shutter;                                           // (with or without velocities)
     }
+    if (rules.bounce) {
+        key.bounce = 1u;
+        key.strength = rules.strength;
+    }
     return id;
 }
 
@@ -110,10 +121,13 @@ bool rm_same_frame(const rm_frame_identity &a, const rm_frame_identity &b) {
 
 rm_staging rm_staging_of(rm_tick_kind kind, const rm_sampling_rules &rules, uint32_t scene_lights, uint32_t scene_spheres, uint32_t scene_shapes) {
     rm_staging s;
-    const bool every_light = rules.motion || rules.camera != nullptr;       // kernels that read a row for every light of the scene
+    // kernels that read a row for every light of the scene (the progressive bounce kernel is the area lights'; the converging
+    // one has a form with stored lights, as the converging kernel has)
+    const bool every_light = rules.motion || rules.camera != nullptr || (rules.bounce && kind == RM_TICK_PROGRESSIVE);
     s.light_columns = every_light ? scene_lights : rules.soft ? rules.n_lights : 0u;
     s.light_zeros = every_light && !rules.soft;
     s.shape_columns = rules.motion && (kind != RM_TICK_CONVERGING || scene_spheres > 0u) ? scene_shapes : 0u;
+    s.bounce_columns = rules.bounce ? 2u : 0u;
     return s;
 }
 
@@ -171,6 +185,17 @@ rm_status rm_light_sequence(uint32_t first, uint32_t count, const double *radii,
             o[1] = radii[l] * (v * h);
             o[2] = radii[l] * (1. - 2. * r2);
         }
+    }
+    return RM_OK;
+}
+
+rm_status rm_bounce_sequence(uint32_t first, uint32_t count, double *table) {
+    if (rm_status rst = check_rows("rm_bounce_sequence", first, count)) return rst;
+    if (count == 0u) return RM_OK;
+    if (!table) return refuse("rm_bounce_sequence: NULL table");
+    for (uint32_t k = 0; k < count; k++) {
+        table[2u * (size_t)k] = radical_inverse(first + k, 19u);
+        table[2u * (size_t)k + 1u] = radical_inverse(first + k, 23u);
     }
     return RM_OK;
 }

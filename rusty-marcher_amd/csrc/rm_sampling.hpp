@@ -18,6 +18,8 @@
 // A radius is a finite number >= 0, a velocity finite, the shutter a finite number >= 0 (a NaN fails the comparisons)
 rm_status rm_check_radii(const char *who, const double *radii, uint32_t n_lights);
 rm_status rm_check_velocities(const char *who, const rm_vec3 *velocities, uint32_t n_shapes, double shutter);
+// The strength of a diffuse bounce is a finite number >= 0
+rm_status rm_check_strength(const char *who, double strength);
 
 // The sampling rules of a tick, a view of the caller's arrays.  soft: area lights of n_lights radii (0 lights' worth of radii is
 // not "no radii"); else radii is NULL and n_lights 0.  motion: moving spheres, a velocity for each of n_shapes shapes and the
@@ -33,6 +35,10 @@ struct rm_sampling_rules {
     // camera: the moving camera's ticks (rm_camera_host.inc), whose frames are their own: the motion's bytes join the key.  The
     // shutter is the one above, with velocities (motion) or without
     const rm_camera_motion *camera = nullptr;
+    // bounce: the diffuse bounce's ticks (rm_bounce_host.inc), whose frames are their own: the strength joins the key (a
+    // strength of 0 is not "no bounce")
+    bool bounce = false;
+    double strength = 0.;
 };
 
 // The view a sum belongs to, byte for byte (no padding: doubles and pairs of words)
@@ -49,6 +55,8 @@ struct rm_progressive_key {
     double shutter;                          // and the shutter; else 0, 0, 0
     uint32_t camera_moves, _pad;             // frames of the moving camera's ticks: 1 and the bytes of their rm_camera_motion; else zeros
     rm_camera_motion camera_motion;
+    uint32_t bounce, _pad2;                  // frames of the diffuse bounce's ticks: 1 and the strength; else zeros
+    double strength;
 };
 
 // The frame a tick samples: the key and, beside it, copies of the radii and the velocities it was begun with
@@ -73,11 +81,13 @@ struct rm_staging {
     uint32_t light_columns;                  // 0: no light table
     bool light_zeros;
     uint32_t shape_columns;                  // 0: no shape table
+    uint32_t bounce_columns;                 // 2: a slice of rm_bounce_sequence; 0: no bounce table
 };
 rm_staging rm_staging_of(rm_tick_kind kind, const rm_sampling_rules &rules, uint32_t scene_lights, uint32_t scene_spheres, uint32_t scene_shapes);
 
 // Rows [first, first + count) of a staged table: 4 doubles of rm_lens_sequence, light_columns x 3 of rm_light_sequence or zeros,
-// shape_columns x 3 of rm_motion_sequence
+// shape_columns x 3 of rm_motion_sequence, 2 of rm_bounce_sequence
+inline rm_status rm_fill_bounce_rows(uint32_t first, uint32_t count, double *out) { return rm_bounce_sequence(first, count, out); }
 inline rm_status rm_fill_lens_rows(uint32_t first, uint32_t count, double *out) { return rm_lens_sequence(first, count, out); }
 rm_status rm_fill_light_rows(const rm_sampling_rules &rules, const rm_staging &staged, uint32_t first, uint32_t count, double *out);
 rm_status rm_fill_shape_rows(const rm_sampling_rules &rules, uint32_t first, uint32_t count, double *out);

@@ -584,6 +584,49 @@ struct Renderer {
             }
         return last_report;
     }
+    // render_progressive_soft with one bounce of diffuse light (rm_render_progressive_bounce): where a sample first hits a surface
+    // that is not glass, one more ray leaves it in a cosine-distributed direction, and what it brings back, times `strength` and the
+    // surface's diffusion and diffuse colour, is added.  radii: one radius a light; empty: point lights.  Static scene, standing
+    // camera.  Beyond what begins a frame again in render_progressive_soft, a changed strength does, and so does a switch between
+    // the calls.
+    std::string render_progressive_bounce(framebuffer::FrameBuffer &frame, const scene::Scene &sc, uint32_t n_samples, double strength = 1.,
+                                          const std::vector<double> &radii = {}, double aperture = 0., double focus = 1., bool restart = false) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_progressive_bounce(ctx_, &p, &lens, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), strength,
+                                           restart ? 1 : 0, flat.data(), nullptr, &last_samples, &last_timing),
+              ctx_);
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return status(t0, frame.width, frame.height);
+    }
+    // render_converging with one bounce of diffuse light (rm_render_converging_bounce), as render_progressive_bounce adds it.  The
+    // frame is render_converging's own: beyond what begins it again there, a changed strength does, a switch between the two calls
+    // does, and every camera move does, history or not.  Returns the tick's report, also left in last_report.
+    rm_converge_report render_converging_bounce(framebuffer::FrameBuffer &frame, const scene::Scene &sc, const rm_converge &converge,
+                                                uint32_t n_samples, double strength = 1., const std::vector<double> &radii = {},
+                                                double aperture = 0., double focus = 1., bool restart = false) {
+        const rm_params p = prepare(frame.width, frame.height, sc);
+        const rm_lens lens{aperture, focus, n_samples, 0u};
+        const size_t rows = frame.height - frame.height % 32;
+        std::vector<double> flat(rows * frame.width * 3 + 1);                              // (+ 1: never a NULL frame)
+        check(rm_render_converging_bounce(ctx_, &p, &lens, &converge, radii.empty() ? nullptr : radii.data(), (uint32_t)radii.size(), strength,
+                                          restart ? 1 : 0, flat.data(), nullptr, &last_report, &last_timing),
+              ctx_);
+        last_samples = last_report.max_count;
+        for (size_t y = 0; y < rows; y++)
+            for (size_t x = 0; x < frame.width; x++) {
+                const double *c = &flat[(y * frame.width + x) * 3];
+                frame.buffer[y][x] = Vec3f{c[0], c[1], c[2]};
+            }
+        return last_report;
+    }
     // The variance-guided filter (include/rusty_marcher_amd.h, "variance-guided filter").  rm_denoise_workspace: the bytes
     // denoise_device's workspace needs for `p`
     static size_t denoise_workspace(const rm_params &p) {

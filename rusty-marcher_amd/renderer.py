@@ -255,6 +255,63 @@ class Renderer:
             report = self.render_converging(frame, scene, tolerance, n_samples, min_samples, max_samples, light_radii, aperture, focus)
         return report
 
+    def render_progressive_bounce(self, frame, scene, n_samples, strength=1., light_radii=None, aperture=0., focus=1., restart=False):
+        """render_progressive with one bounce of diffuse light (rm_render_progressive_bounce): where a sample first hits a surface
+        that is not glass, one more ray leaves it in a cosine-distributed direction, and what it brings back, times `strength`
+        and the surface's diffusion and diffuse colour, is added -- surfaces light each other and colours bleed.  light_radii:
+        one radius a light for area lights, None for points.  Static scene, standing camera.  Beyond what begins a frame again
+        in render_progressive_soft, a changed strength does, and so does a switch between the calls.  strength=1. is a
+        starting value, not a tuned one."""
+        backend._lens(aperture, focus, n_samples)                          # ValueError before the library sees anything
+        backend._strength(strength)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        return self._tick(frame, scene, lambda ctx, p: ctx.render_progressive_bounce(p, aperture, focus, n_samples, strength, radii, restart,
+                                                                                      host_rgb=frame.buffer))
+
+    def render_global_illumination(self, frame, scene, n_samples, strength=1.):
+        """One frame with bounce light: a restarted render_progressive_bounce ticked in slices of at most 64 until the frame holds
+        n_samples samples a pixel, through a pinhole, point lights.  Prints and returns what the last tick does."""
+        if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= backend.PROGRESSIVE_MAX_SAMPLES:
+            raise ValueError("n_samples must be an integer in 1..%d, got %r" % (backend.PROGRESSIVE_MAX_SAMPLES, n_samples))
+        left, message = int(n_samples), None
+        while left > 0:
+            step = min(left, 64)
+            message = self.render_progressive_bounce(frame, scene, step, strength, restart=left == n_samples)
+            left -= step
+        return message
+
+    def render_converging_bounce(self, frame, scene, tolerance, n_samples, strength=1., min_samples=16, max_samples=1024, light_radii=None,
+                                 aperture=0., focus=1., restart=False):
+        """render_converging with one bounce of diffuse light (rm_render_converging_bounce), as render_progressive_bounce adds it:
+        only the pixels still noisy go on being sampled.  The frame is render_converging's own: beyond what begins it again
+        there, a changed strength does, a switch between the two calls does, and every camera move does, keep_history or not.
+        Returns the tick's report, as render_converging does."""
+        backend._converge(tolerance, min_samples, max_samples, backend._lens(aperture, focus, n_samples).n_samples)
+        backend._strength(strength)
+        radii = backend._radii(light_radii, len(scene.lights)) if light_radii is not None else None
+        got = []
+
+        def call(ctx, p):
+            timing, report = ctx.render_converging_bounce(p, aperture, focus, n_samples, tolerance, min_samples, max_samples, strength, radii,
+                                                          restart, host_rgb=frame.buffer)
+            got.append(report)
+            return timing, report.max_count
+
+        self._tick(frame, scene, call)
+        self.last_report = got[0]
+        return got[0]
+
+    def render_converged_bounce(self, frame, scene, tolerance, n_samples, strength=1., min_samples=16, max_samples=1024, light_radii=None,
+                                aperture=0., focus=1.):
+        """A finished picture with bounce light: a restarted render_converging_bounce ticked until a tick lists nothing.
+        -> the last tick's report."""
+        report = self.render_converging_bounce(frame, scene, tolerance, n_samples, strength, min_samples, max_samples, light_radii, aperture,
+                                               focus, restart=True)
+        while report.listed > 0:
+            report = self.render_converging_bounce(frame, scene, tolerance, n_samples, strength, min_samples, max_samples, light_radii,
+                                                   aperture, focus)
+        return report
+
     def keep_history(self, sigma_z=.1, min_normal_dot=.9, max_history=32):
         """History for render_converging, render_converged and render_denoised (rm_converge_history): once the camera moves, the
         frame is no longer begun again but carried to the new view -- every pixel finds the point under it in the previous

@@ -416,6 +416,11 @@ extern "C" {
     fn rm_accumulate_camera_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn rm_accumulate_converging_camera_swept_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_camera_rows: *const c_void, device_light_offsets: *const c_void, n_lights: u32, device_shape_offsets: *const c_void, n_shapes: u32, swept: *const RmSwept, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
     fn rm_swept_tick_info(ctx: *mut RmCtx, out: *mut RmSweptTickReport) -> c_int;
+    fn rm_bounce_sequence(first: u32, count: u32, table: *mut f64) -> c_int;
+    fn rm_accumulate_bounce_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, device_table: *const c_void, device_offsets: *const c_void, n_lights: u32, device_bounce: *const c_void, strength: f64, n_before: u32, device_sum: *mut c_void, device_mean: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn rm_accumulate_converging_bounce_device(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, device_table: *const c_void, table_rows: u32, device_offsets: *const c_void, n_lights: u32, device_bounce: *const c_void, strength: f64, fresh: c_int, buffers: *const RmConvergeFrame, hip_stream: *mut c_void) -> c_int;
+    fn rm_render_progressive_bounce(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, radii: *const f64, n_lights: u32, strength: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, n_total: *mut u32, timing: *mut RmTiming) -> c_int;
+    fn rm_render_converging_bounce(ctx: *mut RmCtx, params: *const RmParams, lens: *const RmLens, converge: *const RmConverge, radii: *const f64, n_lights: u32, strength: f64, restart: c_int, host_rgb: *mut f64, host_rgb8: *mut u8, report: *mut RmConvergeReport, timing: *mut RmTiming) -> c_int;
     fn rm_abi_version() -> u32;
     fn rm_denoise_workspace(params: *const RmParams, bytes: *mut usize) -> c_int;
     fn rm_denoise_device(ctx: *mut RmCtx, params: *const RmParams, denoise: *const RmDenoise, device_sum: *const c_void, device_stats: *const c_void, device_count: *const c_void, device_hits: *const c_void, device_workspace: *mut c_void, device_out: *mut c_void, device_variance: *mut c_void, device_rgb8: *mut c_void, hip_stream: *mut c_void) -> c_int;
@@ -1163,6 +1168,189 @@ impl Gpu {
             }
         }
         (Gpu::status(now, frame.width, frame.height), report)
+    }
+
+    /// `render_progressive_soft` with one bounce of diffuse light: where a sample first hits a surface that is not glass, one more
+    /// ray leaves it in a cosine-distributed direction, and what it brings back, times `strength` and the surface's diffusion and
+    /// diffuse colour, is added.  `radii`: one radius a light; `None`: point lights.  Static scene, standing camera.  Beyond what
+    /// begins a frame again in `render_progressive_soft`, a changed strength does, and so does a switch between the calls.
+    pub fn render_progressive_bounce(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        strength: f64,
+        radii: Option<&[f64]>,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, u32) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut total: u32 = 0;
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_progressive_bounce(self.ctx, &p, &lens, radii_ptr, n_lights, strength, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut total, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), total)
+    }
+
+    /// `render_converging` with one bounce of diffuse light, as `render_progressive_bounce` adds it.  The frame is
+    /// `render_converging`'s own: beyond what begins it again there, a changed strength does, a switch between the two calls
+    /// does, and every camera move does, history or not.
+    pub fn render_converging_bounce(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame: &mut FrameBuffer,
+        scene: &::scene::Scene,
+        converge: RmConverge,
+        strength: f64,
+        radii: Option<&[f64]>,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        restart: bool,
+        display: Option<&mut Vec<u8>>,
+    ) -> (String, RmConvergeReport) {
+        let now = ::std::time::Instant::now();
+        self.upload(scene);
+        let p = Gpu::params(fov, height, width, frame.width, frame.height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        let rows = frame.height - frame.height % 32;
+        let mut flat = vec![0f64; rows * frame.width * 3 + 1]; // (+ 1: never a dangling frame pointer)
+        let bytes: *mut u8 = match display {
+            Some(d) => {
+                d.resize(frame.width * frame.height * 3, 0);
+                d.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let (radii_ptr, n_lights) = match radii {
+            Some(r) => (r.as_ptr(), r.len() as u32),
+            None => (ptr::null(), 0),
+        };
+        let mut report = RmConvergeReport::default();
+        let mut timing = RmTiming::default();
+        check(
+            unsafe {
+                rm_render_converging_bounce(self.ctx, &p, &lens, &converge, radii_ptr, n_lights, strength, if restart { 1 } else { 0 }, flat.as_mut_ptr(), bytes, &mut report, &mut timing)
+            },
+            self.ctx,
+        );
+        for y in 0..rows {
+            assert!(frame.buffer[y].len() == frame.width, "FrameBuffer: row {} holds {} pixels for a width of {}", y, frame.buffer[y].len(), frame.width);
+            for x in 0..frame.width {
+                let c = &flat[(y * frame.width + x) * 3..(y * frame.width + x) * 3 + 3];
+                frame.buffer[y][x] = Vec3f { x: c[0], y: c[1], z: c[2] };
+            }
+        }
+        (Gpu::status(now, frame.width, frame.height), report)
+    }
+
+    /// The device call under `render_progressive_bounce`: `accumulate_soft` with `device_bounce`, `n_samples` x 2 f64 -- rows of
+    /// `bounce_sequence`, or any points of [0, 1) of the caller's making -- and the strength.
+    pub fn accumulate_bounce(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        device_table: *const c_void,
+        device_offsets: *const c_void,
+        n_lights: u32,
+        device_bounce: *const c_void,
+        strength: f64,
+        n_before: u32,
+        device_sum: *mut c_void,
+        device_mean: *mut c_void,
+        device_rgb8: *mut c_void,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_bounce_device(self.ctx, &p, &lens, device_table, device_offsets, n_lights, device_bounce, strength, n_before, device_sum, device_mean, device_rgb8, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// The device call under `render_converging_bounce`: `accumulate_converging` with `device_bounce`, `table_rows` x 2 f64, and
+    /// the strength.
+    pub fn accumulate_converging_bounce(
+        &mut self,
+        fov: f64,
+        height: f64,
+        width: f64,
+        frame_width: usize,
+        frame_height: usize,
+        aperture: f64,
+        focus: f64,
+        n_samples: u32,
+        converge: RmConverge,
+        device_table: *const c_void,
+        table_rows: u32,
+        device_offsets: *const c_void,
+        n_lights: u32,
+        device_bounce: *const c_void,
+        strength: f64,
+        fresh: bool,
+        buffers: RmConvergeFrame,
+        hip_stream: *mut c_void,
+    ) {
+        let p = Gpu::params(fov, height, width, frame_width, frame_height);
+        let lens = RmLens { aperture: aperture, focus: focus, n_samples: n_samples, _pad: 0 };
+        check(
+            unsafe {
+                rm_accumulate_converging_bounce_device(self.ctx, &p, &lens, &converge, device_table, table_rows, device_offsets, n_lights, device_bounce, strength, if fresh { 1 } else { 0 }, &buffers, hip_stream)
+            },
+            self.ctx,
+        );
+    }
+
+    /// Rows `first .. first + count` of the library's bounce sequence: two f64 a row, points of [0, 1).
+    pub fn bounce_sequence(first: u32, count: u32) -> Vec<f64> {
+        let n = 2 * count as usize;
+        let mut table = vec![0f64; n + 1]; // (+ 1: never a dangling pointer)
+        check(unsafe { rm_bounce_sequence(first, count, table.as_mut_ptr()) }, ptr::null());
+        table.truncate(n);
+        table
     }
 
     /// The device call under `render_converging` for a host that keeps its own device buffers (`rm_buffer_alloc`): one pass
