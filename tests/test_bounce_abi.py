@@ -7,7 +7,10 @@
    text.  The new host arithmetic (rm_sampling.cpp) runs stand-alone under the sanitizers.
 3. tests/bounce_reference.py -- the yardstick of the GPU tests -- is soft_reference's frame exactly with strength 0, its
    weighted directions are cosine-distributed, and it is not vacuous: the bounce frames the GPU tests compare differ from the
-   frames without a bounce in the committed numbers of pixels, and the Cornell box bleeds."""
+   frames without a bounce in the committed numbers of pixels, and the Cornell box bleeds.
+4. What the GPU tests' inputs exercise of steps 2 and 3 (bounce_reference.counters): the fixed-view inputs meet no surface from
+   behind; every view of BR.VIEWS holds the committed counters, which meet its conditions, and no ray on a boundary; the edge
+   rows put a bouncing sample on every edge of the square, most of them where the radicand is below zero."""
 import ctypes as C
 import os
 import re
@@ -337,3 +340,100 @@ def test_the_parity_inputs_hold_no_ray_on_a_hit_miss_boundary(O, Y):
         table, bounce = PR.lens_sequence(GB.FIRST, 5), BR.bounce_sequence(GB.FIRST, 5)
         n = BR.boundary_rays(O, Y.orb, Y.scene(name)[1], Y.eye(name), None, 32, 32, depth, 0., LR.FOCUS, table, None, bounce, 1.)
         assert n == 0, "%s: %d samples sit on a boundary" % (name, n)
+
+
+@pytest.mark.parametrize("name", sorted(BR.REQUIRED))
+def test_the_views_hold_no_ray_on_a_hit_miss_boundary(pkg, O, Y, name):
+    """... nor do the views from every side, under either of their tables, through the pinhole and through the lens."""
+    import test_gpu_bounce as GB
+    scene, depth, view, focus, _ = GB.host_view(pkg, Y, name)
+    eye, basis = (Y.eye(scene), None) if view is None else view
+    table = PR.lens_sequence(GB.FIRST, 5)
+    for what, bounce in BR.view_tables(name, GB.FIRST, 5):
+        for aperture in (0., LR.APERTURE):
+            n = BR.boundary_rays(O, Y.orb, Y.scene(scene)[1], eye, basis, 32, 32, depth, aperture, focus, table, None, bounce, 1.)
+            assert n == 0, "%s, %s table, aperture %g: %d samples sit on a boundary" % (name, what, aperture, n)
+    if name in BR.CONVERGING_VIEWS:                                    # the converging case's rows: the library's first 15
+        for aperture in (0., LR.APERTURE):
+            n = BR.boundary_rays(O, Y.orb, Y.scene(scene)[1], eye, basis, 32, 32, depth, aperture, focus, PR.lens_sequence(0, 15), None,
+                                 BR.bounce_sequence(0, 15), 1.)
+            assert n == 0, "%s, rows 0 .. 14, aperture %g: %d samples sit on a boundary" % (name, aperture, n)
+
+
+# ---------------------------------------------------------------- what the inputs exercise of steps 2 and 3
+def pinned(c):
+    return tuple(c[key] for key in BR.PINNED)
+
+
+def test_the_fixed_view_inputs_meet_no_surface_from_behind(Y):
+    """The five inputs the parity tests had before the views (5 rows from FIRST, aperture 0): not one sample takes Nf = -N, the
+    Cornell box shows one orientation, and the sg = -1 half of the basis runs on a few dozen samples far from its pole."""
+    import test_gpu_bounce as GB
+    table, bounce = PR.lens_sequence(GB.FIRST, 5), BR.bounce_sequence(GB.FIRST, 5)
+    for name, want in sorted(BR.FIXED_COVERAGE.items()):
+        c = Y.counters(name, 32, 32, dict(GB.SCENES, floor=3)[name], 0., LR.FOCUS, table, None, bounce, 1.)
+        print("%s, fixed view: %s" % (name, c))
+        assert pinned(c) == want and c["back"] == 0 and c["front"] == c["bouncing"], name
+        assert c["negative"] == 0 and c["edge"] == 0 and c["min_z"] > -0.46
+    assert Y.counters("demo", 32, 32, 3, 0., LR.FOCUS, table, None, bounce, 0.)["bouncing"] == 0    # (no strength: nothing bounces)
+
+
+@pytest.mark.parametrize("name", sorted(BR.REQUIRED))
+def test_a_view_exercises_what_it_is_there_for(pkg, Y, name):
+    """The counters of every view's parity inputs, by the oracle alone under the library's host look-at: the committed numbers,
+    which meet the view's conditions; light comes back; and the frame is another picture than the fixed view's."""
+    import test_gpu_bounce as GB
+    scene, depth, view, focus, _ = GB.host_view(pkg, Y, name)
+    table = PR.lens_sequence(GB.FIRST, 5)
+    for what, bounce in BR.view_tables(name, GB.FIRST, 5):
+        c = Y.counters(scene, 32, 32, depth, 0., focus, table, None, bounce, 1., view)
+        print("%s, %s table: %s" % (name, what, c))
+        assert pinned(c) == BR.COVERAGE[name]
+        BR.assert_covers(name, c)
+        assert c["front"] + c["back"] == c["bouncing"] and c["negative"] == 0
+        lit = Y.bounce(scene, 32, 32, depth, 0., focus, table, None, bounce, 1., (5,), view)[1]
+        plain = Y.bounce(scene, 32, 32, depth, 0., focus, table, None, bounce, 0., (5,), view)[1]
+        assert (np.abs(lit - plain) > 0.05).any(axis=2).sum() > 20
+        if view is not None:
+            assert np.abs(lit - Y.bounce(scene, 32, 32, depth, 0., focus, table, None, bounce, 1., (5,))[1]).max() > 0.05
+
+
+def test_every_pixels_shift_can_be_cancelled():
+    """BR.edge_coordinate: x == 0 is within reach of every pixel of a 32 x 32 frame by a table entry of [0, 1), 1 - 2^-53 of
+    those whose shift is below a half (from there on the sum rounds to 1 and wraps to 0)."""
+    h = BR.lowbias32(np.arange(1024, dtype=np.uint32))
+    for shift16 in sorted(set((h & np.uint32(0xffff)).tolist() + (h >> np.uint32(16)).tolist() + [0, 1, 32768, 32769, 65535])):
+        near, far = BR.edge_coordinate(shift16, False), BR.edge_coordinate(shift16, True)
+        assert near is not None and 0. <= near < 1. and near == (1. - shift16 / 65536.) % 1.
+        assert (far is not None) == (shift16 < 32768), shift16
+        assert far is None or (0. <= far < 1. and far == np.nextafter(near if near > 0. else 1., 0.))
+    # the clamp is needed there: without it the yardstick's own w is NaN
+    x, y = np.zeros(4096), np.random.default_rng(5).uniform(0., 1., 4096)
+    r = BR.disc_unclamped(x, y)[2]
+    assert 0.05 < (r < 0.).mean() < 0.3 and r.min() > -1e-15 and not np.isnan(BR.disc(x, y)[2]).any()
+    with np.errstate(invalid="ignore"):
+        assert np.isnan(np.sqrt(r)).any()
+
+
+@pytest.mark.parametrize("name", BR.EDGE_VIEWS)
+def test_the_edge_rows_put_a_bouncing_sample_on_every_edge(pkg, O, Y, name):
+    """The edge cases' tables (tests/test_gpu_bounce.py): every row's target bounces and sits where the row's kind says, the
+    counters meet the case's conditions, and no sample is on a hit / miss boundary."""
+    import test_gpu_bounce as GB
+    scene, depth, view, focus, _ = GB.host_view(pkg, Y, name)
+    eye, basis = (Y.eye(scene), None) if view is None else view
+    n = len(BR.EDGE_KINDS)
+    table = PR.lens_sequence(GB.FIRST, n)
+    bouncing = Y.bouncing_pixels(scene, 32, 32, 0., focus, table, view)
+    bounce, targets = BR.edge_table(np.random.default_rng(BR.EDGE_SEED), bouncing, BR.EDGE_KINDS)
+    assert bounce.shape == (n, 2) and n <= 64 and (bounce >= 0.).all() and (bounce < 1.).all()
+    at = {"x_lo": (0, 0.), "x_hi": (0, BR.ONE_BELOW), "y_lo": (1, 0.), "y_hi": (1, BR.ONE_BELOW)}
+    for s, (kind, p) in enumerate(zip(BR.EDGE_KINDS, targets)):
+        xy = BR.shifted(bounce[s, 0], bounce[s, 1], np.array([p], dtype=np.uint32))
+        assert bouncing[p, s] and all(xy[at[e][0]][0] == at[e][1] for e in kind.split("+")), (s, kind, p)
+        assert "+" in kind or BR.disc_unclamped(*xy)[2][0] < 0.
+    c = Y.counters(scene, 32, 32, depth, 0., focus, table, None, bounce, 1., view)
+    print("%s, %d edge rows: %s" % (name, n, c))
+    BR.assert_edges(c)
+    assert (c["edge"], c["corner"], c["negative"]) == (24, 8, 20) and [c[e] for e in BR.EDGES] == [8, 8, 8, 8]
+    assert BR.boundary_rays(O, Y.orb, Y.scene(scene)[1], eye, basis, 32, 32, depth, 0., focus, table, None, bounce, 1.) == 0

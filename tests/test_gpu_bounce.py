@@ -5,7 +5,12 @@ order across passes (pinned on the CPU by tests/test_bounce_abi.py) -- and again
 
 What the header calls byte for byte is demanded byte for byte; against the yardstick every channel of every pixel of the rows
 a pass writes is demanded within TIGHT = 1e-9 of the mean (n TIGHT of a sum of n samples), no pixel left out.  Largest
-deviations observed on an MI355X are recorded in DESIGN.md section 6x."""
+deviations observed on an MI355X are recorded in DESIGN.md section 6x.
+
+The fixed view meets no surface from behind and hardly enters the sg = -1 half of the basis: sections 2b and 2c run views from
+every side (BR.VIEWS, the context turned by rm_camera_look_at) and rows that land on the edges of the square, each after
+asserting, by the oracle alone, that its inputs do exercise what they are there for."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -18,8 +23,10 @@ import lens_reference as LR
 import progressive_reference as PR
 import radiance_reference as RR
 import soft_reference as SR
+import test_camera_basis as CB
 import test_gpu_lens as GL
 import test_gpu_progressive as GP
+import test_gpu_query as GQ
 import test_gpu_soft as GS
 import workloads
 
@@ -75,6 +82,37 @@ def run_bounce(pkg, c, w, h, depth, aperture, focus, table, offsets, bounce, str
 
 def zero_offsets(Y, name, n):
     return np.zeros((n, Y.n_lights(name), 3))
+
+
+def host_view(pkg, Y, name):
+    """The view BR.VIEWS[name] by the library's host look-at (rm_camera_basis_look_at: no context, no GPU) ->
+    (scene, depth, (eye, basis) -- None for the fixed view --, the distance to the target, (eye, target, up hint) or None)."""
+    scene = BR.VIEWS[name][0]
+    scene, depth, eye, target, up = BR.look_from(name, *GQ.bounds_of(Y.scene(scene)[0].flatten().desc()))
+    if eye is None:
+        return scene, depth, None, float(np.linalg.norm(np.array(target) - np.array(Y.eye(scene)))), None
+    st, basis = CB.look_at(pkg, eye, target, up)
+    assert st == 0
+    return scene, depth, (eye, RR.basis_tuple(basis)), float(np.linalg.norm(np.array(target) - np.array(eye))), (eye, target, up)
+
+
+@contextlib.contextmanager
+def looking(pkg, c, Y, name):
+    """Uploads the scene of BR.VIEWS[name] and turns the context to the view -> (scene, depth, view, focus), view = (eye, basis)
+    as the context reports them (None: the fixed view); the fixed view again afterwards."""
+    scene, depth, host, focus, look = host_view(pkg, Y, name)
+    GL.upload(c, Y.scene(scene)[0])
+    try:
+        view = None
+        if look is not None:
+            c.look_at(*look)
+            pos, basis, on = c.camera()
+            assert on
+            view = ((pos.x, pos.y, pos.z), RR.basis_tuple(basis))
+            assert view == host                                       # the CPU pins (test_bounce_abi.py) are pins of this view
+        yield scene, depth, view, focus
+    finally:
+        c.orient(None)
 
 
 # ---------------------------------------------------------------- 1. strength 0 is the area lights' frame
@@ -153,6 +191,71 @@ def test_depth_one_returns_the_background_along_the_bounce(pkg, ctx, Y):
     flat = run_bounce(pkg, ctx, 32, 32, 0, 0., LR.FOCUS, table, offsets, bounce, 1., (5,))
     soft = GS.run_soft(pkg, ctx, 32, 32, 0, 0., LR.FOCUS, table, offsets, (5,))
     assert all(a.tobytes() == b.tobytes() for a, b in zip(flat, soft))
+
+
+# ---------------------------------------------------------------- 2b. views from every side
+@pytest.mark.parametrize("name", sorted(BR.REQUIRED))
+def test_bounce_frames_match_the_yardstick_from_every_side(pkg, ctx, Y, name):
+    """The views of BR.VIEWS: surfaces met from behind (Nf = -N), facing normals in the sg = -1 half of the basis and on both
+    of its poles exactly, front and back faces in one wave.  Each case first demands of its own inputs, by the oracle alone,
+    the counters it is there for (BR.REQUIRED), then what test_bounce_frames_match_the_yardstick demands: aperture 0 and 0.4,
+    the library's sequence and a random table, point lights -- and area lights in the Cornell box."""
+    n = 5
+    with looking(pkg, ctx, Y, name) as (scene, depth, view, focus):
+        table = ctx.lens_sequence(FIRST, n)
+        lights = [("points", zero_offsets(Y, scene, n))]
+        if scene == "cornell":
+            lights.append(("radii", ctx.light_sequence(FIRST, n, (RADII,) * Y.n_lights(scene))))
+        for what, bounce in BR.view_tables(name, FIRST, n):
+            if what == "sequence":
+                assert bounce.tobytes() == pkg.backend.bounce_sequence(FIRST, n).tobytes()
+            for aperture in (0., LR.APERTURE):
+                for how, offsets in lights:
+                    c = Y.counters(scene, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., view)
+                    if aperture == 0.:
+                        BR.assert_covers(name, c)
+                    total, mean, rgb8 = run_bounce(pkg, ctx, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., (n,))
+                    ref_sum, ref_mean = Y.bounce(scene, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., (n,), view)
+                    plain = Y.soft(scene, 32, 32, depth, aperture, focus, table, offsets, (n,), view)[1]
+                    d_mean, d_sum = GL.worst(mean, ref_mean), GL.worst(total, ref_sum)
+                    lit = int((np.abs(ref_mean - plain) > 0.05).any(axis=2).sum())
+                    print("%s, aperture %g, %s table, %s: max |delta| mean %.3e, sum %.3e (%d pixels differ from the frame without; %d samples "
+                          "bounce, %d from behind, %d with Nf.z < 0, Nf.z %.4f .. %.4f, %d / %d on the poles)" % (
+                              name, aperture, what, how, d_mean, d_sum, lit, c["bouncing"], c["back"], c["below"], c["min_z"], c["max_z"],
+                              c["pole_up"], c["pole_down"]))
+                    assert not np.isnan(mean).any() and not np.isnan(total).any()
+                    assert d_mean < TIGHT and d_sum < n * TIGHT
+                    assert rgb8.tobytes() == PR.to_bytes(mean).tobytes()
+                    assert lit > 0
+                    if view is not None:                              # another picture than the fixed view's
+                        fixed = Y.bounce(scene, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., (n,))[1]
+                        assert GL.worst(ref_mean, fixed) > 0.05
+
+
+# ---------------------------------------------------------------- 2c. the edges of the square
+@pytest.mark.parametrize("name", BR.EDGE_VIEWS)
+def test_samples_on_the_edges_of_the_square(pkg, ctx, Y, name):
+    """Rows built so that one bouncing pixel a row lands on x == 0, x == 1 - 2^-53, the same of y, or a corner, exactly
+    (BR.edge_table): where the radicand of the disc map rounds below zero and only step 2's clamp keeps the square root from NaN."""
+    n = len(BR.EDGE_KINDS)
+    with looking(pkg, ctx, Y, name) as (scene, depth, view, focus):
+        table = ctx.lens_sequence(FIRST, n)
+        bounce, _ = BR.edge_table(np.random.default_rng(BR.EDGE_SEED), Y.bouncing_pixels(scene, 32, 32, 0., focus, table, view), BR.EDGE_KINDS)
+        offsets = zero_offsets(Y, scene, n)
+        c = Y.counters(scene, 32, 32, depth, 0., focus, table, offsets, bounce, 1., view)
+        BR.assert_edges(c)
+        total, mean, rgb8 = run_bounce(pkg, ctx, 32, 32, depth, 0., focus, table, offsets, bounce, 1., (n,))
+        ref_sum, ref_mean = Y.bounce(scene, 32, 32, depth, 0., focus, table, offsets, bounce, 1., (n,), view)
+        d_mean, d_sum = GL.worst(mean, ref_mean), GL.worst(total, ref_sum)
+        print("%s, %d edge rows: max |delta| mean %.3e, sum %.3e (%d samples on an edge, %d on a corner, %d with a radicand below zero, "
+              "the lowest %.3e)" % (name, n, d_mean, d_sum, c["edge"], c["corner"], c["negative"], c["min_radicand"]))
+        assert not np.isnan(mean).any() and not np.isnan(total).any()
+        assert d_mean < TIGHT and d_sum < n * TIGHT
+        assert rgb8.tobytes() == PR.to_bytes(mean).tobytes()
+        # the edge samples are not special to a pass size: two passes are the one pass byte for byte
+        two = run_bounce(pkg, ctx, 32, 32, depth, 0., focus, table, offsets, bounce, 1., (n - 11, 11))
+        for a, b, what in zip(two, (total, mean, rgb8), ("sum", "mean", "bytes")):
+            assert a.tobytes() == b.tobytes(), what
 
 
 # ---------------------------------------------------------------- 3. folding

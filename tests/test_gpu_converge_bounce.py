@@ -121,6 +121,37 @@ def test_a_negative_tolerance_is_the_plain_bounce_run_byte_for_byte(pkg, ctx, Y,
     assert GL.worst(got["mean"], ref_mean) < TIGHT and GL.worst(got["sum"], ref_sum) < 15 * TIGHT
 
 
+@pytest.mark.parametrize("name", BR.CONVERGING_VIEWS)
+def test_a_negative_tolerance_is_the_plain_bounce_run_from_behind(pkg, ctx, Y, name):
+    """The same under two of the views of BR.VIEWS -- inside the Cornell box, where every sample bounces off a back face, and
+    behind the screens, on the basis's -z pole: through the pinhole with stored lights and through the lens with offset lights."""
+    with GB.looking(pkg, ctx, Y, name) as (scene, depth, view, focus):
+        for aperture, radii in ((0., None), (LR.APERTURE, (GB.RADII,) * Y.n_lights(scene))):
+            plain = plain_bounce_snapshots(pkg, ctx, Y, scene, depth, aperture, focus, 5, 3, radii, 1.)
+            f, tables = GC.Frame(pkg, 32, 32), bounce_tables(pkg, ctx, 16, radii)
+            for k in range(3):
+                bounce_pass(pkg, ctx, f, depth, aperture, focus, 5, -1., 16, 16, tables, 1., k == 0)
+                got, n = f.snapshot(), 5 * (k + 1)
+                assert got["listed"] == 1024 and np.all(got["count"] == n)
+                for key, ref in zip(("sum", "mean", "rgb8"), plain[n]):
+                    assert not (key != "rgb8" and np.isnan(got[key]).any())
+                    assert got[key].tobytes() == ref.tobytes(), "%s, radii %s, %d samples: %s differs in %d pixels" % (
+                        name, radii, n, key, int((got[key] != ref).any(axis=2).sum()))
+            # ... and the last of them is the yardstick's frame under the view, whose samples are the ones the view is there for
+            table, bounce = ctx.lens_sequence(0, 15), pkg.backend.bounce_sequence(0, 15)
+            offsets = GB.zero_offsets(Y, scene, 15) if radii is None else ctx.light_sequence(0, 15, radii)
+            c = Y.counters(scene, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., view)
+            if aperture == 0.:
+                BR.assert_covers(name, c)
+                assert name != "cornell-inside" or c["back"] == 15 * 1024
+            ref_sum, ref_mean = Y.bounce(scene, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., (15,), view)
+            d_mean, d_sum = GL.worst(got["mean"], ref_mean), GL.worst(got["sum"], ref_sum)
+            print("%s, aperture %g, radii %s, 3 x 5 samples: max |delta| mean %.3e, sum %.3e (%d samples bounce, %d from behind, %d on the -z pole)"
+                  % (name, aperture, radii, d_mean, d_sum, c["bouncing"], c["back"], c["pole_down"]))
+            assert d_mean < TIGHT and d_sum < 15 * TIGHT
+            assert GL.worst(ref_mean, Y.bounce(scene, 32, 32, depth, aperture, focus, table, offsets, bounce, 1., (15,))[1]) > 0.05
+
+
 # ---------------------------------------------------------------- 3. every pixel at its own count
 @pytest.mark.parametrize("name,radii", [("demo", None), ("penumbra", (GB.RADII,) * 3)])
 def test_every_pixel_holds_the_plain_bounce_run_at_its_own_count(pkg, ctx, Y, name, radii):

@@ -1,4 +1,4 @@
-"""Every instantiation of the sample-shading kernels against the oracle (-m gpu).  Six kernel families run
+"""Every instantiation of the sample-shading kernels against the oracle (-m gpu).  Eight kernel families run
 radiance_steps<BVH, POW, STACK, LIGHTS> (csrc/rm_radiance_step.inc), and each launcher picks the instantiation by the scene
 image (a hierarchy or none; integer exponents or not) and by max_depth <= 5; the converging frames also by whether light
 offsets are given.  The cells of tests/variant_matrix.py are scenes and depths at which every one of these facts matters:
@@ -6,20 +6,22 @@ tests/test_variant_matrix.py pins on the CPU that a cell takes the kernel it cla
 neighbours (12.5 against 12; one level less deep) on more than 5 % of the rays and pixels, and that a ray fills the stack.
 
 Which test launches which instantiation -- R test_radiance, F test_refine, L test_lens, P test_progressive, S test_soft,
-C test_converging[stored], O test_converging[offsets], each at the cell named on the left (`mesh-integer-5` runs the
-fifth line's kernels once more, over a triangle hierarchy):
+C test_converging[stored], O test_converging[offsets], B test_bounce, CB test_converging_bounce[stored], OB
+test_converging_bounce[offsets], each at the cell named on the left (`mesh-integer-5` runs the fifth line's kernels once
+more, over a triangle hierarchy):
 
-    cell                  BVH  POW      STACK  radiance refine lens accum soft converge converge+offsets
-    flat-integer-5        no   INTEGER   4        R       F     L    P     S     C         O
-    flat-integer-6        no   INTEGER  32        R       F     L    P     S     C         O
-    flat-generic-5        no   GENERIC   4        R       F     L    P     S     C         O
-    flat-generic-6        no   GENERIC  32        R       F     L    P     S     C         O
-    spheres-integer-5     yes  INTEGER   4        R       F     L    P     S     C         O
-    spheres-integer-6     yes  INTEGER  32        R       F     L    P     S     C         O
-    spheres-generic-5     yes  GENERIC   4        R       F     L    P     S     C         O
-    spheres-generic-6     yes  GENERIC  32        R       F     L    P     S     C         O
+    cell                  BVH  POW      STACK  radiance refine lens accum soft converge converge+offsets bounce converge-bounce +offsets
+    flat-integer-5        no   INTEGER   4        R       F     L    P     S     C         O               B       CB            OB
+    flat-integer-6        no   INTEGER  32        R       F     L    P     S     C         O               B       CB            OB
+    flat-generic-5        no   GENERIC   4        R       F     L    P     S     C         O               B       CB            OB
+    flat-generic-6        no   GENERIC  32        R       F     L    P     S     C         O               B       CB            OB
+    spheres-integer-5     yes  INTEGER   4        R       F     L    P     S     C         O               B       CB            OB
+    spheres-integer-6     yes  INTEGER  32        R       F     L    P     S     C         O               B       CB            OB
+    spheres-generic-5     yes  GENERIC   4        R       F     L    P     S     C         O               B       CB            OB
+    spheres-generic-6     yes  GENERIC  32        R       F     L    P     S     C         O               B       CB            OB
 
-8 x 5 + 8 x 2 = 56.  (C and O also launch the accum and the soft kernels of their line: the plain runs beside them.)
+8 x 5 + 8 x 2 = 56, and 8 + 8 x 2 = 24 of the diffuse bounce (rm_bounce.hip, rm_converge_bounce.hip): 80.  (C and O also
+launch the accum and the soft kernels of their line, CB and OB the bounce kernel: the plain runs beside them.)
 
 Every channel of every ray or pixel within TIGHT = 1e-9 of the oracle, nothing left out and nothing NaN; what leaves the scene
 is exactly +0; every output holds a sentinel beforehand; what the header calls byte for byte is demanded byte for byte.  The
@@ -30,13 +32,16 @@ import numpy as np
 import pytest
 
 import antialias_reference as AR
+import bounce_reference as BR
 import converge_reference as CR
 import lens_reference as LR
 import progressive_reference as PR
 import radiance_reference as RR
 import soft_reference as SR
 import test_gpu_antialias as GA
+import test_gpu_bounce as GB
 import test_gpu_converge as GC
+import test_gpu_converge_bounce as GCB
 import test_gpu_lens as GL
 import test_gpu_parity as GPAR
 import test_gpu_progressive as GP
@@ -80,6 +85,11 @@ def Y(pkg, O, orc):
 @pytest.fixture(scope="module")
 def A(pkg, O, orc):
     return AR.Yardstick(pkg, O, orc)
+
+
+@pytest.fixture(scope="module")
+def B(pkg, O, entry, orc, tmp_path_factory):
+    return BR.Yardstick(pkg, O, orc, BR.compile_helper(O, entry, tmp_path_factory.mktemp("orb_variant_matrix_gpu")))
 
 
 def load(ctx, matrix, yardstick, cell):
@@ -224,6 +234,70 @@ def test_converging(pkg, ctx, matrix, Y, cell, offsets):
             assert got[key].tobytes() == ref.tobytes(), "%s after %d samples is not the plain run's" % (key, ns * (k + 1))
     print("%s converging, %s lights: %d passes; max |delta| mean %.3e, sum / n %.3e, Y / n %.3e, Q / n %.3e (nearest decision %.3g x its margin)"
           % (VM.cell_id(cell), "offset" if offsets else "stored", len(recs), worst[0], worst[1], worst[2], worst[3], nearest))
+
+
+# ---------------------------------------------------------------- the diffuse bounce
+@cells
+def test_bounce(pkg, ctx, matrix, B, cell):
+    """rm_accumulate_bounce_device through the lens, under the area lights, rows from BOUNCE_FIRST on, strength 1."""
+    bvh, generic, depth = cell
+    name = load(ctx, matrix, B, cell)
+    first, n = VM.BOUNCE_FIRST, VM.BOUNCE_ROWS
+    table, offsets, bounce = ctx.lens_sequence(first, n), ctx.light_sequence(first, n, VM.RADII), pkg.backend.bounce_sequence(first, n)
+    assert bounce.tobytes() == BR.bounce_sequence(first, n).tobytes() and offsets.tobytes() == SR.light_sequence(first, n, VM.RADII).tobytes()
+    assert np.asarray(table).tobytes() == PR.lens_sequence(first, n).tobytes()     # the rows tests/test_variant_matrix.py pins
+    total, mean, rgb8 = GB.run_bounce(pkg, ctx, W, H, depth, VM.APERTURE, VM.FOCUS, table, offsets, bounce, 1., (5, 5))
+    ref_sum, ref_mean = B.bounce(name, W, H, depth, VM.APERTURE, VM.FOCUS, table, offsets, bounce, 1., (5, 5))
+    d_mean, d_sum = held(mean, ref_mean, "mean"), held(total, ref_sum, "sum", n * TIGHT)
+    assert rgb8.tobytes() == PR.to_bytes(mean).tobytes()
+    one = GB.run_bounce(pkg, ctx, W, H, depth, VM.APERTURE, VM.FOCUS, table, offsets, bounce, 1., (n,))
+    for a, b, what in zip((total, mean, rgb8), one, ("sum", "mean", "bytes")):
+        assert a.tobytes() == b.tobytes(), "%s after two passes of 5 is not the one pass of 10's" % what
+    soft = B.soft(name, W, H, depth, VM.APERTURE, VM.FOCUS, table, offsets, (5, 5))[1]
+    assert int((np.abs(ref_mean - soft) > 0.05).any(axis=2).sum()) > 50      # light did come back
+    # strength 0: the area lights' frame
+    still = GB.run_bounce(pkg, ctx, W, H, depth, VM.APERTURE, VM.FOCUS, table, offsets, bounce, 0., (5, 5))
+    plain = GS.run_soft(pkg, ctx, W, H, depth, VM.APERTURE, VM.FOCUS, table, offsets, (5, 5))
+    for a, b, what in zip(still, plain, ("sum", "mean", "bytes")):
+        assert a.tobytes() == b.tobytes(), "%s with strength 0 is not the soft frame's" % what
+    print("%s bounce: max |delta| mean %.3e, sum %.3e" % (VM.cell_id(cell), d_mean, d_sum))
+
+
+@pytest.mark.parametrize("offsets", [False, True], ids=["stored", "offsets"])
+@cells
+def test_converging_bounce(pkg, ctx, matrix, B, cell, offsets):
+    """rm_accumulate_converging_bounce_device with stored and with offset lights against the plain bounce run of the same cell
+    (which test_bounce holds to the oracle): tolerance < 0 byte for byte, and a real tolerance pixel by pixel at its own count."""
+    bvh, generic, depth = cell
+    ns, tol, lo, hi = VM.CONVERGE
+    radii = VM.RADII if offsets else None
+    name = load(ctx, matrix, B, cell)
+    tables = GCB.bounce_tables(pkg, ctx, hi, radii)
+    plain = GCB.plain_bounce_snapshots(pkg, ctx, B, name, depth, VM.APERTURE, VM.FOCUS, ns, hi // ns, radii, 1.)
+    f = GC.Frame(pkg, H, W)
+    for k in range(2):
+        GCB.bounce_pass(pkg, ctx, f, depth, VM.APERTURE, VM.FOCUS, ns, -1., lo, hi, tables, 1., k == 0)
+        got = f.snapshot()
+        assert got["listed"] == W * H and np.all(got["count"] == ns * (k + 1))
+        for key, ref in zip(("sum", "mean", "rgb8"), plain[ns * (k + 1)]):
+            assert not (key != "rgb8" and np.isnan(got[key]).any())
+            assert got[key].tobytes() == ref.tobytes(), "%s after %d samples is not the plain bounce run's" % (key, ns * (k + 1))
+    assert int((np.abs(got["mean"] - GC.plain_snapshots(pkg, ctx, depth, VM.APERTURE, VM.FOCUS, ns, 2, radii)[2 * ns][1]) > 0.05).any(axis=2).sum()) > 20
+    # a real tolerance: every pixel is the plain bounce run at its own count
+    g = GC.Frame(pkg, H, W)
+    for k in range(8 * (hi // ns + 2)):                                # (converge_reference.run's stop: a pixel listed late, as a neighbour, outlasts hi / ns passes)
+        GCB.bounce_pass(pkg, ctx, g, depth, VM.APERTURE, VM.FOCUS, ns, tol, lo, hi, tables, 1., k == 0)
+        last = g.snapshot()
+        if last["listed"] == 0:
+            break
+    counts = last["count"]
+    assert last["listed"] == 0 and len(np.unique(counts)) >= 3 and counts.max() <= hi and counts.min() >= lo
+    for c in np.unique(counts):
+        at = counts == c
+        for key, ref in zip(("sum", "mean", "rgb8"), plain[int(c)]):
+            assert last[key][at].tobytes() == ref[at].tobytes(), "%s of the pixels with %d samples" % (key, c)
+    print("%s converging bounce, %s lights: %d distinct counts, %d .. %d; every pixel is the plain bounce run at its own count"
+          % (VM.cell_id(cell), "offset" if offsets else "stored", len(np.unique(counts)), counts.min(), counts.max()))
 
 
 # ---------------------------------------------------------------- random scenes

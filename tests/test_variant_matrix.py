@@ -8,6 +8,7 @@ tests/test_gpu_structured_rays.py, by the host-only scene image and the oracle a
    channel on at least 5 % of the rays and of the pixels (the shares are printed);
 3. some ray of the list holds exactly max_depth - 1 live siblings at once (cast_ray's tree replayed for 64 rays);
 4. the refine threshold refines a proper subset with no contrast near it, and no select decision of a converging cell is close;
+   the light the diffuse bounce brings back tells the depths and the exponents apart by itself, with no bounce ray on a boundary;
 5. the structured rays hold the exact incidences they are there for."""
 import ctypes as C
 import os
@@ -17,9 +18,12 @@ import numpy as np
 import pytest
 
 import antialias_reference as AR
+import bounce_reference as BR
 import converge_reference as CR
+import progressive_reference as PR
 import radiance_reference as RR
 import ranged_reference
+import soft_reference as SR
 import test_gpu_query as GQ
 import test_launch_plan as LP
 import test_scene_image as SI
@@ -135,6 +139,48 @@ def test_no_select_decision_of_a_converging_cell_is_close(matrix, Y, cell, offse
     assert counts.min() == lo and counts.max() == hi and len(np.unique(counts)) >= 4     # some settle at once, some run into the cap
     listed = [int(l.sum()) for l, _ in recs]
     assert any(0 < n < VM.W * VM.H and n % 16 for n in listed)         # a list that fills no whole number of waves
+
+
+# ---------------------------------------------------------------- 4b. the bounce cells
+@pytest.fixture(scope="module")
+def B(pkg, O, entry, orc, tmp_path_factory):
+    return BR.Yardstick(pkg, O, orc, BR.compile_helper(O, entry, tmp_path_factory.mktemp("orb_variant_matrix")))
+
+
+def bounce_share(B, matrix, bvh, generic, depth, half=VM.HALF):
+    """What the bounce adds to the cell's frame (tests/test_gpu_variant_matrix.py test_bounce's inputs): the yardstick's mean at
+    strength 1 less its mean at strength 0, [pixel][3] -> (the share, the scene's name in B)."""
+    n = VM.BOUNCE_ROWS
+    name = VM.register(B, matrix.name(bvh, generic) + ("" if half == VM.HALF else "-%g" % half), matrix.pair(bvh, generic, half))
+    table, offsets = PR.lens_sequence(VM.BOUNCE_FIRST, n), SR.light_sequence(VM.BOUNCE_FIRST, n, VM.RADII)
+    bounce = BR.bounce_sequence(VM.BOUNCE_FIRST, n)
+    lit, plain = (B.bounce(name, VM.W, VM.H, depth, VM.APERTURE, VM.FOCUS, table, offsets, bounce, strength, (n,))[1] for strength in (1., 0.))
+    return (lit - plain).reshape(-1, 3), name
+
+
+@pytest.mark.parametrize("cell", VM.CELLS, ids=VM.cell_id)
+def test_the_bounce_share_tells_the_variants_apart(O, matrix, B, cell):
+    """The bounce launchers pick their instantiation as the others do (test_a_cell_takes_the_kernel_it_claims asks the
+    library's own rule).  Here: the light the bounce brings back -- not the frame underneath it -- depends on the depth and, in
+    the generic cells, on the exponent, on the committed numbers of pixels; and no sample's bounce ray lies on a hit / miss
+    boundary."""
+    bvh, generic, depth = cell
+    share, name = bounce_share(B, matrix, bvh, generic, depth)
+    differ = lambda a, b: int((np.abs(a - b) > VM.RESOLVE).any(axis=1).sum())
+    lit, shallower = differ(share, 0.), differ(share, bounce_share(B, matrix, bvh, generic, depth - 1)[0])
+    rounded = differ(share, bounce_share(B, matrix, bvh, generic, depth, 12.)[0]) if generic else None
+    print("%s bounce share: %d pixels, depth %d against %d on %d, exponent 12.5 against 12 on %s; more than 0.05 on %d" % (
+        VM.cell_id(cell), lit, depth, depth - 1, shallower, rounded, int((np.abs(share) > 0.05).any(axis=1).sum())))
+    want = VM.BOUNCE_SHARE[bvh]
+    assert lit == want[0] >= 50 and shallower == want[depth - 4] >= 1
+    assert not generic or rounded == want[3] >= 10
+    assert (share >= 0.).all()                                         # light is only added
+    n = VM.BOUNCE_ROWS
+    table, offsets = PR.lens_sequence(VM.BOUNCE_FIRST, n), SR.light_sequence(VM.BOUNCE_FIRST, n, VM.RADII)
+    assert BR.boundary_rays(O, B.orb, B.scene(name)[1], VM.EYE, None, VM.W, VM.H, depth, VM.APERTURE, VM.FOCUS, table, offsets,
+                            BR.bounce_sequence(VM.BOUNCE_FIRST, n), 1.) == 0
+    c = B.counters(name, VM.W, VM.H, depth, VM.APERTURE, VM.FOCUS, table, offsets, BR.bounce_sequence(VM.BOUNCE_FIRST, n), 1.)
+    assert c["bouncing"] > 500 and c["below"] > 10, c                 # (spheres in front of the panes: both halves of the basis)
 
 
 # ---------------------------------------------------------------- 5. the structured rays

@@ -34,6 +34,11 @@ APERTURE, FOCUS = 0.5, 12.           # the third pane (z = -12) lies in the plan
 REFINE_N, REFINE_THRESHOLD = 2, 0.25
 LENS_SAMPLES = 5                     # 12 pixels a wave, four idle lanes
 CONVERGE = (4, 0.1, 8, 32)           # samples a pass, tolerance, min_samples, max_samples
+BOUNCE_FIRST, BOUNCE_ROWS = 3, 10    # the bounce cells' rows of the three sequences: two passes of 5
+# Pixels of the 32 x 32 frame on which the bounce's share of it (the frame at strength 1 less the frame at strength 0, through
+# the lens, under the area lights) differs by more than RESOLVE, counted with the oracle alone (tests/test_variant_matrix.py):
+# scene -> (from no bounce at all, depth 5 against 4, depth 6 against 5 -- None: no such cell --, exponent 12.5 against 12)
+BOUNCE_SHARE = {"flat": (103, 9, 7, 26), "spheres": (150, 15, 10, 37), "mesh": (129, 8, None, None)}
 
 CELLS = [(bvh, generic, depth) for bvh in ("flat", "spheres") for generic in (False, True) for depth in (5, 6)] + [("mesh", False, 5)]
 SCENES = sorted({c[:2] for c in CELLS})
