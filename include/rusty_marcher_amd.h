@@ -665,11 +665,13 @@ rm_status rm_camera_basis_check(const rm_camera_basis *basis);
  *     weight times the background, and so does a child beyond the cap (renderer.rs:262-264).
  *     max_depth == 0 returns the background for every ray; max_depth > RM_MAX_DEPTH is RM_ERR_DEPTH.
  *   - Viewer direction.  direct_lighting's dir_to_viewer is normalize(origin - point)
- *     (renderer.rs:149).  A caller's direction is unit length only within the reference's assert,
- *     |d.d - 1| < 1e-4, and reflect() does not renormalise (optics.rs:4-6), so a reflected child
- *     inherits its parent's length: the specular term takes -normalized(dir) at every ray step.
- *     Everything else -- the intersection tests, the reflected and refracted children -- takes the
- *     direction as it is, as the reference does.
+ *     (renderer.rs:149), and that is what the specular term takes at every ray step, formed from
+ *     the step's own origin and hit point -- not the ray's direction turned round.  The two agree
+ *     to rounding wherever the hit lies a way down the ray; they do not for a ray that starts ON
+ *     a surface: point == origin gives the zero vector (the reference adds no specular light
+ *     there), and a hit an ulp or two from the origin gives what the rounding of
+ *     origin + dir * t left.  Everything else -- the intersection tests, the reflected and
+ *     refracted children -- takes the caller's direction as it is, as the reference does.
  *   - Shadow rays are walked without the per-primitive occluder masks of the render (they hold for
  *     rays cast from near the scene; a ray list has no such bound).  The decisions are the same.
  *   - Sample rays.  A sample (sx, sy), sx the real-valued column and sy the row, is the ray

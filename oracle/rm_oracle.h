@@ -7,13 +7,30 @@
  * bench.py's cpu_baseline leg may load this library; the product path
  * (rusty-marcher_amd/) never links or calls it.
  *
- * Parity status: PINNED for the demo scene -- orc_render + orc_normalize +
- * orc_to_vec reproduce the reference's committed engine/out.ppm (800x600,
+ * Parity status.
+ * HELD TO THE REFERENCE'S OWN OUTPUT for the demo scene: orc_render +
+ * orc_normalize + orc_to_vec reproduce its committed engine/out.ppm (800x600,
  * sha256 82d51afa...84797) byte for byte (tests/test_oracle_golden.py), and
- * the reference's unit known-answer tests are restated in
- * tests/test_oracle_kat.py.  UNPINNED for the OBJ/cornell recipe (the only
- * reference test is `load(..).is_some()`, obj.rs:229-233; tobj's source is not
- * in /root/reference) and for the build's own synthetic scene.
+ * its unit known-answer tests are restated in tests/test_oracle_kat.py.
+ * HELD TO A SECOND, INDEPENDENT READING of the Rust (tests/second_reading.py:
+ * scalar Python written from the .rs files alone, itself byte-exact on
+ * out.ppm) by tests/test_second_reading.py: orc_shape_intersect,
+ * orc_triangle_create / _intersect / _offset, orc_find_closest_intersect,
+ * orc_intersect_shape_set, orc_reflect, orc_reflect_ray, orc_refract_ray,
+ * orc_backproject and orc_normalized bit for bit -- spheres from outside,
+ * inside, tangent and behind; polygons of 3 to 8 vertices in both windings;
+ * exactly parallel and on-plane rays; the triangle's 1e-6 threshold; ties
+ * between triangles and between shapes; the u8 wrap of the shape index; both
+ * sides of total internal reflection -- and orc_render frame by frame (every
+ * first-hit decision equal, every channel within 1e-9, measured 0) on the
+ * demo, the Cornell box and the dodecahedron through the main.rs recipe, the
+ * colour ramp, moved polygons and meshes, the synthetic scene, many-sided
+ * glass polygons and twelve random scenes, from three cameras (one inside
+ * glass) at depth caps 1 to 6.
+ * UNPINNED: the .obj PARSER (tobj is a third-party crate whose source the
+ * reference does not carry; both readings take their triangles from
+ * oracle/obj_oracle.py), and Obj shading has no committed reference image --
+ * two readings that agree can still share one misreading.
  *
  * Compile with -ffp-contract=off: every operation below is one IEEE-754
  * double operation in the order the Rust source performs it.

@@ -21,9 +21,10 @@
 //                     distance hold for unit rays: a step whose wave holds a ray that is not takes the complete walk
 //                     (rm_radiance_step.inc, complete_walk_view).
 //   viewer direction  direct_lighting takes normalize(origin - point) (renderer.rs:149).  The render hands shade_direct -dir,
-//                     sound for its unit rays; a caller's direction is unit only within the reference's assert and reflect()
-//                     does not renormalise (optics.rs:4-6), so here it is neg(normalized(dir)) at every step.  Everything
-//                     else takes dir as the reference does.
+//                     sound for its unit rays from a camera that stands clear of every surface; a caller's ray may be off
+//                     unit length within the reference's assert, and it may START on a surface, where origin - point is the
+//                     zero vector or a few ulps of rounding: here it is normalized(orig - point) at every step, as the
+//                     reference has it.  Everything else takes dir as the reference does.
 //   occluder masks    the per-primitive shadow masks hold for hit points of rays cast from near the scene (rm_plan.cpp);
 //                     a ray list has no such bound: the host hands these kernels a header with off_occ = 0.
 //   sample rays       formed here from (sx, sy) with the operations backproject_tables performs on the host, exact divisions.

@@ -246,7 +246,10 @@ __device__ __forceinline__ V3 radiance_steps(const SceneView &sc, V3 orig, V3 di
 #endif
         if (__any(got)) {
             const Surface s = surface_at<false>(sc, orig, dir, h, got, spheres);
-            L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, neg(normalized(dir)), s, got, h.pid, lights, spheres), bg);
+            // renderer.rs:149 as it stands, normalize(origin - point), not the ray's own direction turned round: for a ray that
+            // starts ON a surface the two differ -- point == origin gives the zero vector (no specular light at all), and a hit
+            // an ulp or two down the ray gives whatever the rounding of origin + dir * t left (tests/test_gpu_second_reading.py)
+            L = pick(got, bg + shade_direct<POW, BVH, false, false>(sc, normalized(orig - s.point), s, got, h.pid, lights, spheres), bg);
             const bool glass = got & (s.mat[8] != 0.);                   // is_glass_like, renderer.rs:277
             if (__any(glass)) {
                 const double reflection = s.mat[6], ri = s.mat[7], inv_ri = s.mat[9];

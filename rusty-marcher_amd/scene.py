@@ -118,9 +118,12 @@ class Scene:
     def flatten(self):
         """-> SceneHandle with the current lights / shapes / camera."""
         L = _lib.lib()
+        # a shape of a library-built scene moved in place (scene.shapes[i].offset(..)) edits the list as much as an
+        # append does: its pending offsets exist only on the host object, so the prebuilt handle no longer describes it
         untouched = (self._prebuilt is not None and isinstance(self.shapes, _PrebuiltShapes)
                      and not self.shapes.touched and len(self.lights) == len(self._prebuilt_lights)
-                     and all(a is b for a, b in zip(self.lights, self._prebuilt_lights)))
+                     and all(a is b for a, b in zip(self.lights, self._prebuilt_lights))
+                     and not any(getattr(shape, "_offsets", None) for shape in self.shapes))
         if untouched:
             _lib.check(L.rm_scene_set_camera(self._prebuilt.ptr, _lib.vec3(self.camera)))
             return self._prebuilt

@@ -506,10 +506,14 @@ def _fuzz_case(pkg, O, ctx, seed):
     compare(gpu, O.render(so, w, h, max_depth=depth))
 
 
-def _fuzz_scene(pkg, O, seed):
-    """-> the product's scene, the oracle's, the camera, frame width and height, depth cap of fuzz case `seed`."""
+def fuzz_recipe(seed):
+    """Fuzz case `seed` as plain data, no API of anybody's touched: dict(shapes=[("sphere", centre, radius, material) |
+    ("polygon", vertices, material) | ("mesh", (nt, 9) float64 triangles, offset)] in scene order, lights=[(position, colour,
+    intensity)], camera, width, height, depth).  _fuzz_scene below builds the product's and the oracle's scenes from it, and
+    tests/test_second_reading.py the second reading's; the draws and their order are the fuzz's of old (that file pins the
+    oracle's frames of seeds 0-11 to the hashes they had before the recipe was lifted out)."""
     rng = np.random.default_rng(1000 + seed)
-    s, so = pkg.Scene.new(), O.OracleScene()
+    shapes, lights = [], []
 
     def material():
         glass = bool(rng.random() < 0.35)
@@ -524,8 +528,7 @@ def _fuzz_scene(pkg, O, seed):
         if rng.random() < 0.3:
             c = tuple(float(round(v)) for v in c)                     # integer coordinates: exact incidences
         r, m = float(rng.uniform(0.5, 3.0)), material()
-        s.shapes.append(pkg.sphere.create(pkg.Vec3f(*c), r, pkg.Reflectance(**m)))
-        so.add_sphere(c, r, O.reflectance(**m))
+        shapes.append(("sphere", c, r, m))
     for k in range(int(rng.integers(0, 4))):
         nv = int(rng.integers(3, 7))
         ang = np.sort(rng.uniform(0, 2 * np.pi, nv))                  # counter-clockwise in XY
@@ -535,29 +538,50 @@ def _fuzz_scene(pkg, O, seed):
         verts = [(float(cx + rad * np.cos(a)), float(cy + rad * np.sin(a)),
                   float(cz + tilt[0] * rad * np.cos(a) + tilt[1] * rad * np.sin(a))) for a in ang]
         m = material()
-        s.shapes.append(pkg.polygon.ConvexPolygon.create([pkg.Vec3f(*v) for v in verts], pkg.Reflectance(**m)))
-        so.add_polygon(verts, O.reflectance(**m))
+        shapes.append(("polygon", verts, m))
     if rng.random() < 0.7:
         nt = int(rng.integers(3, 40))
         base = rng.uniform(-10, 10, size=(nt, 1, 3)) + np.array([0., 0., -25.])
         tri = (base + rng.uniform(-3, 3, size=(nt, 3, 3))).reshape(nt, 9)
         off = (0., float(rng.integers(-2, 3)), float(rng.integers(-10, 1)))
-        mesh = pkg.obj.Obj(tri)
-        mesh.offset(pkg.Vec3f(*off))
-        s.shapes.append(mesh)
-        so.add_obj(tri, off)
+        shapes.append(("mesh", tri, off))
     for k in range(int(rng.integers(1, 4))):
         pos = tuple(float(v) for v in rng.uniform(-20, 20, 3))
         col = tuple(float(v) for v in rng.uniform(0.2, 1, 3))
         inten = float(rng.uniform(0.3, 1.))
-        s.lights.append(pkg.create_light(pkg.Vec3f(*pos), pkg.Vec3f(*col), inten))
-        so.add_light(pos, col, inten)
+        lights.append((pos, col, inten))
     cam = tuple(float(v) for v in (rng.integers(-5, 6, 3) if seed % 3 else rng.uniform(-3, 3, 3)))
-    s.camera = pkg.Vec3f(*cam)
-    so.set_camera(cam)
     w, h = int(rng.integers(1, 9)) * 32, int(rng.integers(1, 7)) * 32 + int(rng.integers(0, 2)) * 7
     depth = int(rng.integers(1, 7))
-    return s, so, cam, w, h, depth
+    return dict(shapes=shapes, lights=lights, camera=cam, width=w, height=h, depth=depth)
+
+
+def _fuzz_scene(pkg, O, seed):
+    """-> the product's scene, the oracle's, the camera, frame width and height, depth cap of fuzz case `seed`."""
+    recipe = fuzz_recipe(seed)
+    s, so = pkg.Scene.new(), O.OracleScene()
+    for shape in recipe["shapes"]:
+        if shape[0] == "sphere":
+            _, c, r, m = shape
+            s.shapes.append(pkg.sphere.create(pkg.Vec3f(*c), r, pkg.Reflectance(**m)))
+            so.add_sphere(c, r, O.reflectance(**m))
+        elif shape[0] == "polygon":
+            _, verts, m = shape
+            s.shapes.append(pkg.polygon.ConvexPolygon.create([pkg.Vec3f(*v) for v in verts], pkg.Reflectance(**m)))
+            so.add_polygon(verts, O.reflectance(**m))
+        else:
+            _, tri, off = shape
+            mesh = pkg.obj.Obj(tri)
+            mesh.offset(pkg.Vec3f(*off))
+            s.shapes.append(mesh)
+            so.add_obj(tri, off)
+    for pos, col, inten in recipe["lights"]:
+        s.lights.append(pkg.create_light(pkg.Vec3f(*pos), pkg.Vec3f(*col), inten))
+        so.add_light(pos, col, inten)
+    cam = recipe["camera"]
+    s.camera = pkg.Vec3f(*cam)
+    so.set_camera(cam)
+    return s, so, cam, recipe["width"], recipe["height"], recipe["depth"]
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("RM_FUZZ_SEQ_SEEDS", "8"))))

@@ -109,9 +109,10 @@ def test_radiance_matches_the_oracle(ctx, orc, lattice, shift):
     o, d = lattice.rays[shift]
     got = ctx.radiance(o, d, max_depth=3)
     ref = orc.cast(lattice.oscene, o, d, 3)
-    # A ray that starts on the surface it hits (t == 0: the point is the origin) is no case for cast_ray: the reference's
-    # dir_to_viewer, normalize(origin - point), is 0 / 0 there and its specular term falls to 0, while the header's takes
-    # -normalized(dir) at every step ("radiance queries", Viewer direction).  Such rays must be lit and finite, no more.
+    # A ray that starts on the surface it hits (t == 0: the point is the origin): the reference's dir_to_viewer,
+    # normalize(origin - point), is the zero vector there and its specular term falls to 0.  The radiance step forms that
+    # vector as the reference does ("radiance queries", Viewer direction), so these rays are held to the same
+    # bound as all the others -- and are still counted apart, lit and finite.
     first = lattice.ref.closest(o, d, GRQ.FULL)
     at_origin = (first["hit"] == 1) & (first["t"] == 0.)
     delta = np.abs(got - ref).max(axis=1)
@@ -120,4 +121,5 @@ def test_radiance_matches_the_oracle(ctx, orc, lattice, shift):
           % (shift, delta[~at_origin].max(), int((~at_origin).sum()), int((~gone & ~at_origin).sum()), delta[at_origin].max(), int(at_origin.sum())))
     assert not np.isnan(got).any() and delta[~at_origin].max() < TIGHT, "%d rays differ" % int((delta[~at_origin] >= TIGHT).sum())
     assert (got[at_origin] >= 0.1).all() and at_origin.sum() < 0.1 * len(o)
+    assert at_origin.sum() > 0 and delta[at_origin].max() < TIGHT, "%d rays that start on the surface they hit differ" % int((delta[at_origin] >= TIGHT).sum())
     assert gone.any() and (~gone & ~at_origin).sum() > 1000 and not got[gone].view(np.uint64).any()
