@@ -184,6 +184,7 @@ struct rm_ctx {
     // checked numerics (rm_trace.inc RM_CHECKED): the last render launch's verdict (the resident image's: image.exact_only), and
     // the tiles the context's launches rendered again because a lane's guard fired (device word, counted up by the kernels)
     bool last_launch_exact_only = false;
+    uint32_t last_launch_scene_sig = 0;   // the scene signature the last render launch's arguments carried (KernelArgs::dead_children, bits 8-15; 0: the body for any scene)
     uint32_t *d_redo = nullptr;
     std::vector<rm_feedback> feedback;
     uint64_t feedback_clock = 0, scene_epoch = 0;
@@ -520,6 +521,7 @@ static rm_status rm_scene_upload_impl(rm_ctx *ctx, const rm_scene_desc *d) {
     std::string refusal;
     if (rm_status bst = rm_build_image(d, rm_image_options{!ctx->knobs.disable_bvh, ctx->knobs.shadow_masks}, img, refusal))
         return ctx_fail(ctx, bst, refusal);
+    img.scene_sig = rm_scene_signature(img.H, img.blob.data());   // (the planner's verdict on the image: once per upload)
     rm_image &resident = ctx->image;
 
     // (a different description that builds the same device image -- an edit undone -- is not copied either)
@@ -574,6 +576,15 @@ extern "C" rm_status rmi_redone_tiles(rm_ctx *ctx, uint64_t *redone, uint32_t *l
     RM_HIP(ctx, hipMemcpy(&n, ctx->d_redo, sizeof n, hipMemcpyDeviceToHost));
     *redone = n;
     if (last_exact_only) *last_exact_only = ctx->last_launch_exact_only ? 1u : 0u;
+    return RM_OK;
+}
+
+// Test hook, not part of the ABI (tests/test_gpu_scene_sig.py): the scene signature in the argument block the context's last
+// render launch went out with -- what the kernel read, not what a plan made elsewhere says -- and the resident image's.
+extern "C" rm_status rmi_last_scene_sig(rm_ctx *ctx, uint32_t *launched, uint32_t *resident) {
+    if (!ctx || !launched || !resident) return ctx_fail(ctx, RM_ERR_INVALID_ARG, "rmi_last_scene_sig: NULL argument");
+    *launched = ctx->last_launch_scene_sig;
+    *resident = ctx->have_scene ? ctx->image.scene_sig : 0u;
     return RM_OK;
 }
 
@@ -744,7 +755,7 @@ static rm_status void_frame_check(rm_ctx *ctx, const char *who) {
 static rm_plan_scene plan_scene_of(const rm_ctx *ctx) {
     const rm_image &img = ctx->image;
     return rm_plan_scene{&img.H, ctx->scene_epoch, img.occ_camera_limit, img.integer_exponents, ctx->oriented,
-                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, img.exact_only, img.dead_camera_limit};
+                         ctx->camera, &ctx->basis, (uint32_t)ctx->prop.multiProcessorCount, img.exact_only, img.dead_camera_limit, img.scene_sig};
 }
 
 static rm_status no_kernel(rm_ctx *ctx) { return ctx_fail(ctx, RM_ERR_INVALID_ARG, "render: no kernel for this scene / depth combination"); }
@@ -906,6 +917,7 @@ static rm_status launch_render(rm_ctx *ctx, const rm_params *p, const rm_band &b
     ctx->last_launch_grid = P.grid;
     ctx->last_launch_tail = a.tail_patches;
     ctx->last_launch_exact_only = P.exact_only;
+    ctx->last_launch_scene_sig = (a.dead_children >> RM_SCENE_SIG_SHIFT) & RM_SCENE_SIG_MASK;
     if (ctx->knobs.debug_tail && P.ordered)
         if (rm_status dst = dump_order(ctx, P, stream)) return dst;
 #if defined(RM_EXP_STAMPS) || defined(RM_EXP_PHASES)

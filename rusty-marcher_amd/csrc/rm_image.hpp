@@ -18,6 +18,7 @@ struct rm_image {
     double dead_camera_limit = 0.;     // |camera|_1 beyond which the render does not use them (0: no glass word carries any)
     bool exact_only = false;           // outside what the checked numerics are proven for (rm_image.cpp scene_exact_only)
     bool integer_exponents = false;    // every material's specular_exponent is a small non-negative integer
+    uint32_t scene_sig = 0;            // the compiled-in signature its shape counts are (rm_plan.cpp rm_scene_signature; 0: none)
 };
 
 struct rm_image_options {

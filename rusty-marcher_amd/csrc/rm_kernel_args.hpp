@@ -190,6 +190,31 @@ struct KernelArgs {
 
 static constexpr uint32_t RM_DEAD_DROP = 1u, RM_DEAD_EARLY_FATES = 2u;
 
+// Scene signatures.  The walks of rm_trace.inc are written for any scene; a resident scene's shape counts change only with an
+// upload.  Where the host finds that they are a signature's (rm_plan.cpp rm_scene_signature: every field below, word for word),
+// the launch plan says so in bits 8-15 of KernelArgs::dead_children -- the signature's number, 0: none -- and the plain-walk
+// kernels render the tile with a body compiled for these counts (render_tile<.., SIG>: the same text over a copy of the scene
+// view whose header fields are ASSIGNED the constants, so a wrong verdict would be a wrong picture, never undefined behaviour).
+// One line a signature; its number is its place in the table, from 1.
+struct SceneSignature {
+    uint32_t n_spheres, n_polygons, n_triangles, n_lights, list_ordered;
+    // the vertex count of every polygon, in pid order (n_polygons <= 8).  The host compares it; the body compiled today folds
+    // NOTHING from it -- polygon_hit_num still reads a polygon's count from its record (rm_trace.inc), so a scene that differs
+    // from a signature in this field alone would be rendered right by that body and is sent to the generic one all the same.
+    // Pinned for the stage that is not built (the `nv == 3` alternative and the pentagon loop as constants), so
+    // that building it changes no verdict.
+    uint8_t polygon_nv[8];
+};
+static constexpr SceneSignature RM_SCENE_SIGNATURES[] = {
+    {4u, 2u, 0u, 2u, 1u, {3, 4}},            // the reference's default scene (scene.rs:28-211): four spheres, a triangle and a quad, two lights
+};
+static constexpr uint32_t RM_SCENE_SIG_COUNT = sizeof(RM_SCENE_SIGNATURES) / sizeof(RM_SCENE_SIGNATURES[0]);
+static constexpr uint32_t RM_SCENE_SIG_SHIFT = 8u, RM_SCENE_SIG_MASK = 0xFFu;
+// The kernels that carry the second body: every plain-walk one (an LDS scene copy, no hierarchy, no bundle cull) -- both powers,
+// every ray stack.  The planner asks the same question of its kernel choice: a launch of any other kernel never carries a
+// signature.  (One object of the four costs 55 s to compile instead of 33 and 1.60 MB instead of 1.28: profiles/r09_scene_sig.txt.)
+constexpr bool rm_scene_sig_kernel(bool staged, bool bvh, bool cull) { return staged && !bvh && !cull; }
+
 // What the classification launch gets besides the render launch's own arguments.
 struct ClassifyArgs {
     unsigned long long *tile_mask;

@@ -1,6 +1,7 @@
 // rm_plan.cpp -- the knobs' table, the kernel choice and the launch plan (rm_plan.hpp).  Host arithmetic only: no device
 // header is included here, so nothing in this unit can touch one.
 #include "rm_plan.hpp"
+#include "rm_image.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -53,6 +54,7 @@ const knob k_knobs[] = {
     {"RM_FORCE_UNSTAGED", &rm_knobs::force_unstaged, IS_1},
     {"RM_SHADOW_MASKS", &rm_knobs::shadow_masks, NOT_0},
     {"RM_DEAD_CHILDREN", &rm_knobs::dead_children, DEAD_CHILDREN},
+    {"RM_SCENE_SIG", &rm_knobs::scene_sig, NOT_0},
     {"RM_DISABLE_BVH", &rm_knobs::disable_bvh, IS_1},
     {"RM_SWEPT_BVH", &rm_knobs::swept_bvh, NOT_0},
     {"RM_FORCE_STACK", &rm_knobs::force_stack, ATOI},
@@ -148,6 +150,22 @@ static constexpr uint32_t RM_FEEDBACK_MIN_TILES = 32768;
 static constexpr uint32_t RM_CLASSIFY_MAX_COST = 4000;
 // ... and at the head of the render launch itself, where every wave behind the first round may wait for it: a quarter of that
 static constexpr uint32_t RM_CLASSIFY_IN_LAUNCH_MAX_COST = 1000;
+
+uint32_t rm_scene_signature(const rm_dev_header &H, const double *blob) {
+    if (H.off_bvh_spheres != 0u || H.off_bvh_triangles != 0u || !blob) return 0u;
+    for (uint32_t s = 0; s < RM_SCENE_SIG_COUNT; s++) {
+        const SceneSignature &g = RM_SCENE_SIGNATURES[s];
+        bool match = H.n_spheres == g.n_spheres && H.n_polygons == g.n_polygons && H.n_triangles == g.n_triangles &&
+                     H.n_lights == g.n_lights && H.list_ordered == g.list_ordered && H.n_polygons <= sizeof g.polygon_nv;
+        for (uint32_t i = 0; match && i < H.n_polygons; i++) {
+            uint32_t first_and_count[2];                              // the polygon record's seventh word (rm_internal.h)
+            std::memcpy(first_and_count, blob + H.off_polygons + (size_t)RM_POLYGON_WORDS * i + 6u, sizeof first_and_count);
+            match = first_and_count[1] == g.polygon_nv[i];
+        }
+        if (match) return s + 1u;
+    }
+    return 0u;
+}
 
 bool choose_kernel(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p, uint32_t tiles, rm_kernel_choice *k) {
     const rm_dev_header &H = *sc.H;
@@ -294,6 +312,9 @@ bool plan_launch(const rm_knobs &kn, const rm_plan_scene &sc, const rm_params &p
     a.dead_children = ((kn.dead_children && !k.bvh && !k.cull && sc.dead_camera_limit > 0. &&
                         std::fabs(sc.camera.x) + std::fabs(sc.camera.y) + std::fabs(sc.camera.z) <= sc.dead_camera_limit) ? RM_DEAD_DROP : 0u) |
                       ((kn.early_fates && !k.bvh && !k.cull) ? RM_DEAD_EARLY_FATES : 0u);
+    // (... and, in bits of the same word, the resident scene's signature: the kernels that carry a body for it take that body)
+    if (kn.scene_sig && sc.scene_sig <= RM_SCENE_SIG_COUNT && rm_scene_sig_kernel(k.staged, k.bvh, k.cull))
+        a.dead_children |= (sc.scene_sig & RM_SCENE_SIG_MASK) << RM_SCENE_SIG_SHIFT;
     // A cull step handles 64 primitives for ~25 vector instructions, ~110 when it holds planar
     // primitives and the edge test runs; a bundle pays for every step.  The hierarchy walk finds a
     // bundle's few primitives in a few hundred instructions whatever their number, so scenes whose
@@ -675,6 +696,41 @@ extern "C" rm_status rmi_plan_dead_children(const rm_vec3 *camera, double dead_c
     }
     out[0] = P.args.dead_children & RM_DEAD_DROP;
     out[1] = (!P.k.bvh && !P.k.cull) ? 1u : 0u;
+    return RM_OK;
+}
+
+// Test hook, not part of the ABI (tests/test_scene_sig.py): the scene signature of the image the upload of `d` builds, and what
+// a 96x64 launch of it with this depth cap carries, with the knobs as the environment has them now (rmi_plan_launches' cases
+// hold a scene's counts only: a signature needs the image) -- out[0] = the image's signature (rm_scene_signature), out[1] = the
+// signature in the launch's KernelArgs::dead_children, out[2] = 1 where the kernel is one that has a body for signatures.
+// No device is needed.
+extern "C" rm_status rmi_plan_scene_sig(const rm_scene_desc *d, uint32_t use_bvh, uint32_t max_depth, uint32_t fast_fp, uint32_t *out) {
+    if (!d || !out) { rm_set_host_error("rmi_plan_scene_sig: NULL argument"); return RM_ERR_INVALID_ARG; }
+    const rm_knobs kn = rm_knobs_from_env();
+    rm_image img;
+    std::string error;
+    if (rm_status st = rm_build_image(d, rm_image_options{use_bvh != 0 && !kn.disable_bvh, kn.shadow_masks}, img, error)) { rm_set_host_error(error); return st; }
+    img.scene_sig = rm_scene_signature(img.H, img.blob.data());
+    const rm_camera_basis basis{rm_vec3{1., 0., 0.}, rm_vec3{0., 1., 0.}, rm_vec3{0., 0., -1.}};
+    // (field by field, by name: what rm_device.hip's plan_scene_of takes from the context comes from the image here, and a
+    // field the struct gains later keeps its default instead of shifting these)
+    rm_plan_scene sc{};
+    sc.H = &img.H; sc.scene_epoch = 1u; sc.occ_camera_limit = img.occ_camera_limit; sc.integer_exponents = img.integer_exponents;
+    sc.oriented = false; sc.camera = d->camera; sc.basis = &basis; sc.n_cus = 256u; sc.exact_only = img.exact_only;
+    sc.dead_camera_limit = img.dead_camera_limit; sc.scene_sig = img.scene_sig;
+    rm_params p{};
+    p.half_fov = 0.75; p.height = 64.; p.width = 96.; p.ratio = 1.5;
+    p.frame_width = 96; p.frame_height = 64; p.max_depth = max_depth;
+    p.flags = fast_fp ? RM_FLAG_FAST_FP : 0u;
+    rm_band band;
+    rm_launch_plan P;
+    if (!rm_band_of(p, &band) || !plan_launch(kn, sc, p, band, rm_stream_state{}, 0u, rm_feedback_state{}, 0ull, &P)) {
+        rm_set_host_error("rmi_plan_scene_sig: no plan");
+        return RM_ERR_INVALID_ARG;
+    }
+    out[0] = img.scene_sig;
+    out[1] = (P.args.dead_children >> RM_SCENE_SIG_SHIFT) & RM_SCENE_SIG_MASK;
+    out[2] = rm_scene_sig_kernel(P.k.staged, P.k.bvh, P.k.cull) ? 1u : 0u;
     return RM_OK;
 }
 

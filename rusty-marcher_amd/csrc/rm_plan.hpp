@@ -56,6 +56,10 @@ struct rm_knobs {
     // ... and a refracted child's fate -- beyond the depth cap, or into a flagged side for certain -- is decided before its ray
     // is formed (render_tile).  RM_DEAD_CHILDREN=0 and =1 form every ray and decide on its computed dot, as before
     bool early_fates = true;
+    // A resident scene whose shape counts are a compiled-in signature's (rm_kernel_args.hpp RM_SCENE_SIGNATURES) is rendered by
+    // the plain-walk kernels' body for those counts: RM_SCENE_SIG=0 keeps every launch on the generic body (the A/B switch;
+    // frames are bit-equal)
+    bool scene_sig = true;
     int force_stack = 0;              // RM_FORCE_STACK=4|8|16|32: a deeper ray stack than the depth cap needs
     bool debug_empty = false;         // RM_DEBUG_EMPTY=1: measure the dispatch floor of a launch geometry
     // frame-to-frame feedback (rm_feedback): RM_FEEDBACK=0 never, 1 always, unset: launches of
@@ -125,7 +129,13 @@ struct rm_plan_scene {
     uint32_t n_cus;
     bool exact_only = false;          // the resident scene is outside what the checked numerics are proven for (rm_image.cpp scene_exact_only)
     double dead_camera_limit = 0.;    // cameras farther out (L1 norm) walk every child ray (0: the image has no empty half-space, rm_build_empty_sides)
+    uint32_t scene_sig = 0u;          // the resident image's signature (rm_scene_signature at its upload; 0: none)
 };
+
+// The number of the compiled-in signature (rm_kernel_args.hpp RM_SCENE_SIGNATURES, from 1) that the image of header `H` and
+// words `blob` carries, 0 where it carries none: every count, every polygon's vertex count (read from its record),
+// list_ordered, and no hierarchy.  Pure: decided once per upload, and by the tests' hook.
+uint32_t rm_scene_signature(const rm_dev_header &H, const double *blob);
 
 // Checked numerics (rm_trace.inc RM_CHECKED): a coordinate, radius, camera or light word is inside the proven range when it is
 // finite and at most this in magnitude -- no intermediate of a sphere test can then overflow -- ...

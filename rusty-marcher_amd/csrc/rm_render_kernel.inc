@@ -27,11 +27,24 @@ using namespace rmdev;
 // rays have distinct depths: at most max_depth - 1 of them (STACK = 4 / 8 / 16 / 32).
 // Returns whether the tile has to be rendered again by the exact code -- nothing of it has been stored then (RM_CHECKED, the
 // range-free numerics of rm_trace.inc: some lane met an operand outside their range); never, otherwise.
-template <int STACK, int POW, bool BVH, bool CULL, bool EDGES, bool PREFETCHED>
-__device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArgs &a, uint32_t tx0, uint32_t ty0,
+// SIG: the scene signature the body is compiled for (rm_kernel_args.hpp RM_SCENE_SIGNATURES; 0: any scene).  Under a signature the
+// body below is the same text over a copy of the scene view whose counts are the signature's constants: the walks' loops over
+// them unroll, their remainder loops, the tie keys behind list_ordered and the hierarchy alternatives go.  The values are
+// assigned, not assumed -- the host's verdict (rm_plan.cpp rm_scene_signature) makes them the image's own.
+template <int STACK, int POW, bool BVH, bool CULL, bool EDGES, bool PREFETCHED, int SIG = 0>
+__device__ __forceinline__ bool render_tile(const SceneView &sc_any, const KernelArgs &a, uint32_t tx0, uint32_t ty0,
                                             uint32_t tyf, uint32_t ty8, double bp_x, double bp_y, double *wl,
                                             double *__restrict__ frame_in, unsigned long long *stats, bool have_mask,
                                             unsigned long long first_mask, const char *kargs_of_kernel) {
+    SceneView sc_sig;
+    if constexpr (SIG != 0) {
+        constexpr SceneSignature K = RM_SCENE_SIGNATURES[SIG - 1];
+        sc_sig = sc_any;
+        sc_sig.H.n_spheres = K.n_spheres; sc_sig.H.n_polygons = K.n_polygons; sc_sig.H.n_triangles = K.n_triangles;
+        sc_sig.H.n_lights = K.n_lights; sc_sig.H.list_ordered = K.list_ordered;
+        sc_sig.H.off_bvh_spheres = 0u; sc_sig.H.off_bvh_triangles = 0u;
+    }
+    const SceneView &sc = SIG != 0 ? sc_sig : sc_any;
     const uint32_t lane = threadIdx.x & 63u;
     const V3 bg = mk(own_sgpr(a.bg_x), own_sgpr(a.bg_y), own_sgpr(a.bg_z));
     const uint32_t max_depth = own_sgpr(a.max_depth);
@@ -350,6 +363,20 @@ __device__ __forceinline__ bool render_tile(const SceneView &sc, const KernelArg
     (void)stats;
 #endif
     return false;
+}
+
+// The tile by the body for signature `sig` (wave-uniform; 0, or a number beyond the table: the body for any scene): one
+// comparison a compiled-in signature, N counting down from the table's length.
+template <int N, int STACK, int POW, bool BVH, bool CULL, bool EDGES, bool PREFETCHED>
+__device__ __forceinline__ bool render_tile_of(uint32_t sig, const SceneView &sc, const KernelArgs &a, uint32_t tx0, uint32_t ty0,
+                                               uint32_t tyf, uint32_t ty8, double bp_x, double bp_y, double *wl,
+                                               double *__restrict__ frame_in, unsigned long long *stats, bool have_mask,
+                                               unsigned long long first_mask, const char *kargs_of_kernel) {
+    if constexpr (N > 0) {
+        if (sig != (uint32_t)N)
+            return render_tile_of<N - 1, STACK, POW, BVH, CULL, EDGES, PREFETCHED>(sig, sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame_in, stats, have_mask, first_mask, kargs_of_kernel);
+    }
+    return render_tile<STACK, POW, BVH, CULL, EDGES, PREFETCHED, N>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame_in, stats, have_mask, first_mask, kargs_of_kernel);
 }
 #undef RM_SUS_PARAM
 #undef RM_SUS_ARG
@@ -931,10 +958,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(POW 
         cull_counts[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_start);
 #endif
 #ifdef RM_EXP_STAMPS
-        exact = tile_ns::render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, &tile_stats, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+        unsigned long long *const stats_to = &tile_stats;
 #else
-        exact = tile_ns::render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, nullptr, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+        unsigned long long *const stats_to = nullptr;
 #endif
+        if constexpr (rm_scene_sig_kernel(STAGED, BVH, CULL)) {
+            // The resident scene's signature (the plan's verdict, bits of a word the tile reads anyway: asked for here, used
+            // here, live nowhere else): the body compiled for its counts, or the body for any scene -- wave-uniform, once a tile.
+            const uint32_t sig = (a.dead_children >> RM_SCENE_SIG_SHIFT) & RM_SCENE_SIG_MASK;
+            exact = tile_ns::render_tile_of<RM_SCENE_SIG_COUNT, STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sig, sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, stats_to, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+        } else {
+            exact = tile_ns::render_tile<STACK, POW, BVH, CULL, EDGES, FEEDBACK || EARLY>(sc, a, tx0, ty0, tyf, ty8, bp_x, bp_y, wl, frame, stats_to, have_mask, first_mask, (const char *)__builtin_amdgcn_kernarg_segment_ptr());
+        }
         if (CHECKED && exact) {                                          // (counted: tests and profiles ask how many, rm_device.hip rmi_redone_tiles)
             const KernelArgs &b = *reinterpret_cast<const KernelArgs *>(reread_kernargs((const char *)__builtin_amdgcn_kernarg_segment_ptr()) + sizeof(const double *));
             if (b.redo_count && (threadIdx.x & 63u) == 0u) atomicAdd(b.redo_count, 1u);
